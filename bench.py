@@ -28,6 +28,10 @@ Extra objects on the JSON line:
                   aggregate (SURVEY.md 8d's B_seed per position) and the DP kernel's GCUPS beside it.
   cpu_baseline -- the CPU oracle (oracle/, a restatement: kind "port") timed on this box's host cores on the
                   same workload or a bounded sample of it (rank 0, N = 1 only).
+
+--dump-outputs DIR writes the result arrays of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all; see
+dump_outputs).  The workloads come from seeded generators, so the same arguments give the same inputs on every run and two
+builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -41,7 +45,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0   # MI355X: HBM3E 8 TB/s spec
 # DP: 3-state Gotoh, ~12 integer ops per cell: CUs * 64 lanes * clock / 12
 DP_PEAK_GCUPS = 256 * 64 * 2.4 / 12.0
 
@@ -266,6 +270,48 @@ def kernel_profile(rn, weight, nprof=3, params=None):
     return roofline, kern_ms
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0x4D41555645
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: the arrays the timed step hands its caller (the result of its last run), as <out_dir>/<name>.npy in float64 --
+    every value is an integer below 2^53, so the conversion is exact.  While all of them fit DUMP_LIMIT_BYTES they are written whole;
+    otherwise the larger ones are cut down to a fixed, seeded sample of their rows (same shapes -> same rows), written with the row
+    indices beside them as <name>_sample_rows.npy.  -> {name: [full shape, rows written]}"""
+    arrays = {k: v for k, v in res.items() if isinstance(v, np.ndarray)}
+    if isinstance(res.get("tree"), tuple):                 # the progressive path's guide tree
+        arrays["tree_left"], arrays["tree_right"] = res["tree"]
+    arrays = {k: np.asarray(v) for k, v in sorted(arrays.items())}
+    for k, a in arrays.items():
+        if a.size and a.dtype.kind in "iu" and a.dtype.itemsize == 8 and max(abs(int(a.min())), abs(int(a.max()))) >= 1 << 53:
+            raise ValueError("--dump-outputs: %s holds values float64 cannot represent exactly" % k)
+    rows = {k: (a.shape[0] if a.ndim else 1) for k, a in arrays.items()}
+    row_bytes = {k: 8 * (int(np.prod(a.shape[1:])) if a.ndim else 1) for k, a in arrays.items()}
+    # water-filling: the smallest arrays are written whole, the rest share what is left equally
+    left = DUMP_LIMIT_BYTES - 2 * 4096 * len(arrays)         # (room for the .npy headers)
+    keep = {}
+    order = sorted(arrays, key=lambda k: rows[k] * row_bytes[k])
+    for i, k in enumerate(order):
+        share = left // (len(order) - i)
+        if rows[k] * row_bytes[k] <= share:
+            keep[k] = rows[k]
+        else:
+            keep[k] = share // (row_bytes[k] + 8)               # + the row index of each sampled row
+        left -= keep[k] * row_bytes[k] + (8 * keep[k] if keep[k] < rows[k] else 0)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in arrays.items():
+        a = a.reshape(1) if a.ndim == 0 else a
+        if keep[k] < rows[k]:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows[k], keep[k], replace=False))
+            np.save(os.path.join(out_dir, k + "_sample_rows.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float64))
+        written[k] = [list(arrays[k].shape), int(keep[k])]
+    return written
+
+
 KEYS_ALIGN = ("anchor_start", "anchor_length", "left", "right", "reverse", "col_off", "cols", "dp_score")
 KEYS_PROG = ("left", "right", "reverse", "col_off", "cols", "dp_score")
 
@@ -401,7 +447,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", "--only-primary", dest="no_secondary", action="store_true",
                     help="skip the side measurements (the other configs, the pass with the other lcb_extension setting, the backbone call)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the result arrays of the last timed step to DIR/<name>.npy (float64; at most 64 MB, larger ones as a seeded sample of rows)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -474,6 +524,9 @@ def main():
     else:
         elapsed, res = rn.time_host(args.steps, args.warmup)
     sizes = {k: v for k, v in res.items() if isinstance(v, int)}
+    dumped = None
+    if args.dump_outputs and rank == 0:           # before any later pass overwrites the result buffers the step fetched into
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(res, args.dump_outputs)}
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -595,6 +648,8 @@ def main():
             "stages_ms": stages, "kernels_ms": kern_ms, "result_sizes": sizes, "upload_ms": round(t_upload * 1e3, 2), "device": ctx.device_name(),
             "prng": "xoshiro256** seeded through splitmix64, base seed 0x4D41555645 + config id (SURVEY 8d; mauvealigner_amd/synth.py, csrc/synth_rng.c)",
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         out.update(extras)
         out.update(legs)
         print(json.dumps(out, default=lambda o: o.tolist() if hasattr(o, 'tolist') else repr(o)))

@@ -59,8 +59,9 @@ def score_alignment_reference(aln, origins):
                         i in no calculated interval shared with j -> FN ("unaligned", :349-353)
       truth base-gap:   calculated a base -> FN (:424-425); a gap or unaligned -> TN
     -> dict(tp, tn, fp, fn, total, sensitivity = TP/(TP+FN), specificity = TN/(TN+FP)), the tool's first two lines.
-    tests/test_accuracy.py runs the tool itself (built from its source on the mirror) and compares all four counts; the
-    tool's interval lookup misbehaves when an interval lacks a sequence, so it is run on N-way intervals only."""
+    tests/test_accuracy.py compares all four counts with what the tool itself (built from its source on the mirror) printed
+    on the same inputs (tests/golden/reference_tools.json); the tool's interval lookup misbehaves when an interval lacks a
+    sequence, so it is run on N-way intervals only."""
     N = len(origins)
     left, right, rev = np.asarray(aln["left"]), np.asarray(aln["right"]), np.asarray(aln["reverse"])
     col_off, cols = np.asarray(aln["col_off"]), np.asarray(aln["cols"])

@@ -1,6 +1,8 @@
 """Alignment accuracy against the generator's truth (the measurement of src/scoreAlignment.cpp:172-457).  The frozen
 semantics are this repository's own, so besides bit-parity between the HIP path and the oracle we
 check that what both compute is a *correct* alignment of the synthetic genomes."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -50,35 +52,44 @@ def test_gpu_alignment_is_accurate_at_scale():
         ctx.close()
 
 
-REFERENCE = "/root/reference/src"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_tools.json")
+# (seed, genomes, length, divergence); seed 3 of the four-genome case is left out: the tool leaves its main path for a few columns there, its
+# interval lookup's quirk
+SCORE_CASES = [(1, 2, 5000, 0.05), (2, 3, 6000, 0.10), (5, 4, 4000, 0.15), (4, 3, 8000, 0.2)]
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present")
+def score_case(seed, n, length, div):
+    """-> (truth XMFA, oracle XMFA, oracle result, origins): the two files src/scoreAlignment.cpp is run on for one case"""
+    gs, org = synth.star_genomes(n, length, div, seed, inversions=0, track=True)
+    names = ["g%d.fa" % g for g in range(n)]
+    r = O.align(gs, O.default_params(add_unaligned=0), names=names, want_xmfa=True)      # N-way intervals only (see accuracy.py)
+    return accuracy.truth_xmfa(gs, org, names), r["xmfa"], r, org
+
+
+def sha256(text):
+    return hashlib.sha256(text.encode()).hexdigest()
+
+
 def test_counts_equal_the_reference_tool():
     """src/scoreAlignment.cpp, built from its own source against the mirror and run on <truth XMFA> <oracle XMFA>, prints
     the figures accuracy.score_alignment_reference computes from the interval table: sensitivity, specificity and the
-    correct fraction agree to the six digits the tool prints, for 2..4 genomes at 5-20 % divergence."""
+    correct fraction agree to the six digits the tool prints, for 2..4 genomes at 5-20 % divergence.  What the tool printed
+    on each case is stored in tests/golden/reference_tools.json (tests/golden/make_reference_golden.py), beside digests of
+    the two files it read, so the test checks that today's inputs are those files."""
     import re
-    import subprocess
-    import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with tempfile.TemporaryDirectory() as td:
-        tool = os.path.join(td, "scoreAlignment")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-I" + os.path.join(root, "include"), os.path.join(REFERENCE, "scoreAlignment.cpp"), "-o", tool,
-                               "-L" + os.path.join(root, "mauvealigner_amd"), "-lmauve_hip", "-Wl,-rpath," + os.path.join(root, "mauvealigner_amd")])
-        for seed, n, length, div in [(1, 2, 5000, 0.05), (2, 3, 6000, 0.10), (5, 4, 4000, 0.15), (4, 3, 8000, 0.2)]:     # (seed 3 of the four-genome case: the tool leaves its main path for a few columns, its interval lookup's quirk)
-            gs, org = synth.star_genomes(n, length, div, seed, inversions=0, track=True)
-            names = ["g%d.fa" % g for g in range(n)]
-            r = O.align(gs, O.default_params(add_unaligned=0), names=names, want_xmfa=True)      # N-way intervals only (see accuracy.py)
-            t, c = os.path.join(td, "t.xmfa"), os.path.join(td, "c.xmfa")
-            open(t, "w").write(accuracy.truth_xmfa(gs, org, names))
-            open(c, "w").write(r["xmfa"])
-            out = subprocess.run([tool, t, c], capture_output=True, text=True).stdout
-            v = [float(x) for x in re.findall(r"= ([0-9.e+-]+)$", out, re.M)]
-            a = accuracy.score_alignment_reference(r["aln"], org)
-            want = [a["sensitivity"], a["specificity"], (a["tp"] + a["tn"]) / a["total"], (a["fp"] + a["fn"]) / a["total"]]
-            assert len(v) >= 6 and v[5] == 0                      # bad_context: the tool took its main path everywhere
-            for got, w in zip(v[:4], want):
-                assert abs(got - w) <= 6e-6 * max(1.0, abs(w)), (seed, out, a)
-            # the pair-based figures of score_alignment bracket the same alignment: same true positives
-            assert accuracy.score_alignment(r["aln"], org)["tp"] == a["tp"]
+    with open(GOLDEN) as f:
+        ref = json.load(f)["score_alignment"]
+    assert [tuple(c["case"]) for c in ref] == SCORE_CASES
+    for c in ref:
+        t, x, r, org = score_case(*c["case"])
+        assert sha256(t) == c["truth_sha256"] and sha256(x) == c["calculated_sha256"], \
+            "%s: the inputs differ from those the stored tool output was made on (tests/golden/make_reference_golden.py)" % (c["case"],)
+        out = c["stdout"]
+        v = [float(x) for x in re.findall(r"= ([0-9.e+-]+)$", out, re.M)]
+        a = accuracy.score_alignment_reference(r["aln"], org)
+        want = [a["sensitivity"], a["specificity"], (a["tp"] + a["tn"]) / a["total"], (a["fp"] + a["fn"]) / a["total"]]
+        assert len(v) >= 6 and v[5] == 0                      # bad_context: the tool took its main path everywhere
+        for got, w in zip(v[:4], want):
+            assert abs(got - w) <= 6e-6 * max(1.0, abs(w)), (c["case"], out, a)
+        # the pair-based figures of score_alignment bracket the same alignment: same true positives
+        assert accuracy.score_alignment(r["aln"], org)["tp"] == a["tp"]

@@ -172,6 +172,22 @@ def test_stage_seam_formats_round_trip(name):
 
 
 REFERENCE = "/root/reference/src"
+# The source-compatibility tests below compile the reference's own programs, where they lie, against include/ (nothing of them
+# is stored here).  What the two programs the other tests need printed and wrote (scoreAlignment, mfa2xmfa) is stored in
+# tests/golden/reference_tools.json by tests/golden/make_reference_golden.py.
+GOLDEN_TOOLS = os.path.join(ROOT, "tests", "golden", "reference_tools.json")
+
+
+def _tool_golden(name):
+    import json
+    with open(GOLDEN_TOOLS) as f:
+        return json.load(f)[name]
+
+
+def _sha256(text):
+    import hashlib
+    return hashlib.sha256(text.encode()).hexdigest()
+
 
 REF_UNIT = r'''
 // The in-tree plug-ins, included from where they lie, compiled against the mirror -- unmodified.
@@ -221,12 +237,8 @@ def test_reference_tools_compile_unmodified(tool):
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-w", "-I" + os.path.join(ROOT, "include"), os.path.join(REFERENCE, tool)])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present")
-def test_reference_mfa2xmfa_runs_on_the_mirror():
-    """src/mfa2xmfa.cpp -- the in-tree twin of the XMFA writer -- built from its own source against the mirror's
-    libGenome and RUN: the XMFA it writes is read by IntervalList::ReadStandardAlignment and written back byte for byte
-    by WriteStandardAlignment (80-column wrap, deflines, header, terminator), and the FastA it writes through
-    gnFASSource::Write is the ungapped input."""
+def mfa2xmfa_rows():
+    """the gapped rows of the multi-FastA test_reference_mfa2xmfa_runs_on_the_mirror hands to src/mfa2xmfa.cpp"""
     rng = np.random.default_rng(3)
     rows = []
     L = 437                                                   # several wrapped lines and a ragged last one
@@ -235,69 +247,82 @@ def test_reference_mfa2xmfa_runs_on_the_mirror():
         gaps = rng.random(L) < (0.05 + 0.1 * g)
         r[gaps] = "-"
         rows.append("".join(r)[:L - 7 * g])                   # shorter entries: the tool pads them with gaps
+    return rows
+
+
+def mfa2xmfa_input(rows):
+    return "".join(">seq_%d some words\n" % g + "".join(r[p:p + 61] + "\n" for p in range(0, len(r), 61)) for g, r in enumerate(rows))
+
+
+def test_reference_mfa2xmfa_runs_on_the_mirror():
+    """src/mfa2xmfa.cpp -- the in-tree twin of the XMFA writer -- built from its own source against the mirror's
+    libGenome and run (`mfa2xmfa in.mfa out.xmfa un.fa`; what it wrote is stored in tests/golden/reference_tools.json):
+    the XMFA it writes is read by IntervalList::ReadStandardAlignment and written back byte for byte by
+    WriteStandardAlignment (80-column wrap, deflines, header, terminator), and the FastA it writes through
+    gnFASSource::Write is the ungapped input."""
+    rows = mfa2xmfa_rows()
+    ref = _tool_golden("mfa2xmfa")
+    assert _sha256(mfa2xmfa_input(rows)) == ref["input_sha256"], "the input differs from the one the stored output was made on"
+    inc = os.path.join(ROOT, "include")
     with tempfile.TemporaryDirectory() as td:
-        mfa = os.path.join(td, "in.mfa")
-        with open(mfa, "w") as f:
-            for g, r in enumerate(rows):
-                f.write(">seq_%d some words\n" % g)
-                for p in range(0, len(r), 61):
-                    f.write(r[p:p + 61] + "\n")
-        inc = os.path.join(ROOT, "include")
-        tool = os.path.join(td, "mfa2xmfa")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-I" + inc, os.path.join(REFERENCE, "mfa2xmfa.cpp"), "-o", tool])
-        xmfa, fa = os.path.join(td, "out.xmfa"), os.path.join(td, "un.fa")
-        subprocess.check_call([tool, mfa, xmfa, fa])
-        text = open(xmfa).read()
-        assert text.startswith("#FormatVersion Mauve1\n#Sequence1File\t" + fa + "\n#Sequence1Entry\t1\n#Sequence1Format\tFastA\n")
+        xmfa = os.path.join(td, "out.xmfa")
+        with open(xmfa, "w") as f:
+            f.write(ref["xmfa"])
+        with open(os.path.join(td, "un.fa"), "w") as f:           # the sequence file the XMFA header names, relative to td
+            f.write(ref["fa"])
+        text = ref["xmfa"]
+        assert text.startswith("#FormatVersion Mauve1\n#Sequence1File\tun.fa\n#Sequence1Entry\t1\n#Sequence1Format\tFastA\n")
         for g, r in enumerate(rows):
             assert "> %d:1-%d + seq_%d some words\n" % (g + 1, len(r.replace("-", "")), g) in text
         assert text.endswith("=\n")
-        got = open(fa).read().split(">")[1:]
+        got = ref["fa"].split(">")[1:]
         assert ["".join(x.split("\n")[1:]) for x in got] == [r.replace("-", "") for r in rows]
         rt = os.path.join(td, "rt")
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + inc, os.path.join(ROOT, "tests", "cpp", "xmfa_roundtrip.cpp"), "-o", rt,
                                "-L" + os.path.join(ROOT, "mauvealigner_amd"), "-lmauve_hip", "-Wl,-rpath," + os.path.join(ROOT, "mauvealigner_amd")])
-        r = subprocess.run([rt, xmfa], capture_output=True, text=True)
+        r = subprocess.run([rt, xmfa], capture_output=True, text=True, cwd=td)
         assert r.returncode == 0 and r.stdout == text, r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present")
-def test_oracle_xmfa_blocks_equal_what_mfa2xmfa_writes():
-    """The oracle's XMFA writer against the reference's own formatting code: every all-forward block of an oracle
-    alignment, handed to src/mfa2xmfa.cpp (built on the mirror's libGenome) as a multi-FastA of its gapped rows, comes
-    back as the same block text -- deflines, 80-column wrap, terminator -- up to the coordinates, which mfa2xmfa counts
-    from 1."""
+def oracle_xmfa_blocks():
+    """-> [(block text, its rows as the multi-FastA mfa2xmfa is handed, the block's deflines)]: every all-forward block of
+    at least two genomes of an oracle alignment"""
     import re
     from oracle import pyoracle as O
-    from mauvealigner_amd import synth
     gs = synth.make_config("C1", scale=0.05)
     names = ["genomeA.fa", "genomeB.fa"]
     text = O.align(gs, O.default_params(), names=names, want_xmfa=True)["xmfa"]
     body = text[text.index("> "):]
-    blocks = [b for b in body.split("=\n") if b.strip()]
+    out = []
+    for b in (b for b in body.split("=\n") if b.strip()):
+        heads = re.findall(r"^> (\d+):(\d+)-(\d+) ([+-]) (.*)$", b, re.M)
+        if len(heads) < 2 or any(h[3] == "-" for h in heads):
+            continue
+        parts = re.split(r"^> .*$", b, flags=re.M)[1:]
+        rows = ["".join(p.split()) for p in parts]
+        out.append((b, "".join(">%s\n%s\n" % (h[4], r) for h, r in zip(heads, rows)), heads))
+    return out
+
+
+def test_oracle_xmfa_blocks_equal_what_mfa2xmfa_writes():
+    """The oracle's XMFA writer against the reference's own formatting code: every all-forward block of an oracle
+    alignment, handed to src/mfa2xmfa.cpp (built on the mirror's libGenome) as a multi-FastA of its gapped rows, comes
+    back as the same block text -- deflines, 80-column wrap, terminator -- up to the coordinates, which mfa2xmfa counts
+    from 1.  What the tool wrote for each block is stored in tests/golden/reference_tools.json, under the digest of the
+    multi-FastA it read."""
+    import re
+    ref = _tool_golden("mfa2xmfa_blocks")
     checked = 0
-    with tempfile.TemporaryDirectory() as td:
-        tool = os.path.join(td, "mfa2xmfa")
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-I" + os.path.join(ROOT, "include"), os.path.join(REFERENCE, "mfa2xmfa.cpp"), "-o", tool])
-        for b in blocks:
-            heads = re.findall(r"^> (\d+):(\d+)-(\d+) ([+-]) (.*)$", b, re.M)
-            if len(heads) < 2 or any(h[3] == "-" for h in heads):
-                continue
-            parts = re.split(r"^> .*$", b, flags=re.M)[1:]
-            rows = ["".join(p.split()) for p in parts]
-            mfa = os.path.join(td, "b.mfa")
-            with open(mfa, "w") as f:
-                for h, r in zip(heads, rows):
-                    f.write(">%s\n%s\n" % (h[4], r))
-            out = os.path.join(td, "b.xmfa")
-            subprocess.check_call([tool, mfa, out])
-            want = re.sub(r"^> (\d+):(\d+)-(\d+) ", lambda m: "> %s:1-%d " % (m.group(1), int(m.group(3)) - int(m.group(2)) + 1), b, flags=re.M) + "=\n"
-            # mfa2xmfa numbers the rows 1..k in file order; the oracle's block may skip absent genomes
-            got = open(out).read()
-            for k, h in enumerate(heads):
-                got = got.replace("> %d:1-" % (k + 1), "> %s:1-" % h[0], 1) if str(k + 1) != h[0] else got
-            assert got == want
-            checked += 1
+    for b, mfa, heads in oracle_xmfa_blocks():
+        key = _sha256(mfa)
+        assert key in ref, "no stored mfa2xmfa output for this block: the oracle's blocks differ from those it was made on"
+        want = re.sub(r"^> (\d+):(\d+)-(\d+) ", lambda m: "> %s:1-%d " % (m.group(1), int(m.group(3)) - int(m.group(2)) + 1), b, flags=re.M) + "=\n"
+        # mfa2xmfa numbers the rows 1..k in file order; the oracle's block may skip absent genomes
+        got = ref[key]
+        for k, h in enumerate(heads):
+            got = got.replace("> %d:1-" % (k + 1), "> %s:1-" % h[0], 1) if str(k + 1) != h[0] else got
+        assert got == want
+        checked += 1
     assert checked >= 1
 
 
