@@ -13,6 +13,7 @@
 // the scatter, wave64 ballots for ranking and for the extension walk.  No MFMA by design.
 #include "common.hpp"
 #include "dev_scan.hpp"
+#include "small_sort.hpp"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -283,24 +284,7 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
 // ------------------------------------------------------------------------------------------------
 // radix sort (LSD, 8-bit digits, stable): histogram / row scan / scatter per pass
 // ------------------------------------------------------------------------------------------------
-// block-wide exclusive scan of one value per thread (256 threads); returns the exclusive prefix, *total
-// receives the block sum.  One global atomic per block instead of one per wave keeps a single output
-// counter far below its ~12 ns-per-atomic serial rate (MI355X_MICROARCH.md "fanin").
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total, uint32_t *lds /*[8]*/)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { uint32_t c = lds[w]; if (w < wave) wbase += c; tot += c; }
-    __syncthreads();
-    *total = tot;
-    return wbase + inc - v;
-}
+// (block_excl_scan: small_sort.hpp)
 
 // ------------------------------------------------------------------------------------------------
 // Masked seed passes (guide-tree nodes below the root, LCB extension): most windows touch a masked base and
@@ -374,10 +358,8 @@ __global__ void __launch_bounds__(256) seed_extract_compact(const uint64_t *__re
     }
 }
 
-constexpr int RS_THREADS = 256;
-constexpr int RS_ITEMS = 16;
+constexpr int RS_ITEMS = 16;                     // (RS_THREADS, the tile ranking rs_scatter_tile: small_sort.hpp)
 constexpr int RS_TILE = RS_THREADS * RS_ITEMS;   // 4096 keys per workgroup
-constexpr int RS_WAVES = RS_THREADS / 64;
 
 template <typename KeyT>
 __global__ void __launch_bounds__(RS_THREADS) rs_hist(const KeyT *__restrict__ keys, uint32_t n, int shift,
@@ -457,85 +439,6 @@ __global__ void __launch_bounds__(256) rs_rowscan(uint32_t *__restrict__ hist, u
     if (threadIdx.x == 0) totals[blockIdx.x] = total;
 }
 
-// One tile of the scatter.  FULL: the tile holds RS_TILE keys, so no lane is ever predicated off (all tiles but the
-// last) -- the loads, ballots and stores compile without exec-mask branches.
-template <typename KeyT, bool FULL>
-__device__ __forceinline__ void rs_scatter_tile(const KeyT *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
-                                                KeyT *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
-                                                uint32_t tile_base, uint32_t tile_n, int shift, KeyT *s_keys, uint32_t *s_vals,
-                                                uint32_t (*wcount)[256], const uint32_t *gbase, uint32_t *tstart, uint32_t *scan)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // load (wave-striped: wave w owns [w*1024, (w+1)*1024), item i of lane l is index i*64+l)
-    KeyT k[RS_ITEMS]; uint32_t v[RS_ITEMS]; uint32_t rank[RS_ITEMS];
-    const uint32_t wbase = wave * (64 * RS_ITEMS);
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++) {
-        const uint32_t li = wbase + i * 64 + lane;
-        const bool ok = FULL || li < tile_n;
-        k[i] = ok ? keys_in[tile_base + li] : (KeyT)0;
-        v[i] = ok ? vals_in[tile_base + li] : 0u;
-    }
-    // wave-level multisplit ranking, stable in (i, lane) order.  peers = lanes of row i with the same digit, built
-    // as two 32-bit halves from eight ballots (one 3-input bit op per half and bit).  The wave owns
-    // wcount[wave][]: every peer reads the running count, then the first peer bumps it -- LDS operations of one
-    // wave stay in order, so no atomic and no broadcast is needed.
-    uint32_t *wc = wcount[wave];
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++) {
-        const uint32_t li = wbase + i * 64 + lane;
-        const bool ok = FULL || li < tile_n;
-        const uint32_t d = (uint32_t)(k[i] >> shift) & 255u;
-        uint32_t plo, phi;
-        if (FULL) { plo = 0xffffffffu; phi = 0xffffffffu; }
-        else { const uint64_t a = __ballot(ok); plo = (uint32_t)a; phi = (uint32_t)(a >> 32); }
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const uint64_t m = FULL ? __ballot((d >> b) & 1) : __ballot(ok && ((d >> b) & 1));
-            const uint32_t sb = (uint32_t)((int32_t)(d << (31 - b)) >> 31);     // all ones when bit b of d is set
-            plo &= ~((uint32_t)m ^ sb); phi &= ~((uint32_t)(m >> 32) ^ sb);
-        }
-        const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-        const uint32_t old = ok ? wc[d] : 0u;
-        if (ok && below == 0) wc[d] = old + (uint32_t)__popc(plo) + (uint32_t)__popc(phi);
-        rank[i] = old + below;
-    }
-    __syncthreads();
-    // per-digit prefix over the waves, then the tile-level digit starts
-    uint32_t c[RS_WAVES], sum = 0;
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) { c[w] = wcount[w][tid]; }
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) { uint32_t t = c[w]; wcount[w][tid] = sum; sum += t; }
-    {
-        uint32_t dummy;
-        tstart[tid] = block_excl_scan(sum, &dummy, scan);
-    }
-    __syncthreads();
-    // stage in LDS at the tile-sorted position
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++) {
-        const uint32_t li = wbase + i * 64 + lane;
-        if (FULL || li < tile_n) {
-            const uint32_t d = (uint32_t)(k[i] >> shift) & 255u;
-            const uint32_t pos = tstart[d] + wc[d] + rank[i];
-            s_keys[pos] = k[i]; s_vals[pos] = v[i];
-        }
-    }
-    __syncthreads();
-    // coalesced write-out: consecutive threads write consecutive addresses inside a digit's run
-#pragma unroll
-    for (int i = 0; i < RS_ITEMS; i++) {
-        const uint32_t pos = i * RS_THREADS + tid;
-        if (FULL || pos < tile_n) {
-            const KeyT kk = s_keys[pos];
-            const uint32_t d = (uint32_t)(kk >> shift) & 255u;
-            const uint32_t dst = gbase[d] + (pos - tstart[d]);
-            keys_out[dst] = kk; vals_out[dst] = s_vals[pos];
-        }
-    }
-}
-
 // RAW: `hist` holds the raw per-tile digit counts (no rs_rowscan ran): every workgroup sums its digit's row for itself --
 // the sorts of the chain / DP front / canonical order have at most a few dozen tiles, where the row scan is one more
 // launch of pure latency.
@@ -573,9 +476,9 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict_
     }
     __syncthreads();
     if (tile_n == RS_TILE)
-        rs_scatter_tile<KeyT, true>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
+        rs_scatter_tile<KeyT, RS_ITEMS, true>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
     else
-        rs_scatter_tile<KeyT, false>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
+        rs_scatter_tile<KeyT, RS_ITEMS, false>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1653,6 +1556,14 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
     // per-kernel figures of the main sort)
     const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scan = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCAN,
               k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
+    static const bool small_on = [] { const char *e = getenv("MAUVE_SMALL_SORT"); return !(e && e[0] == '0'); }();   // A/B switch
+    if (small_on && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
+        HIPCHK(ctx, ctx->hist.ensure(ss_ws_words(n) * sizeof(uint32_t)));
+        small_sort<KeyT>(ctx->stream, n, key_bits, shift_lo, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
+                         [&](bool scatter, auto &&launch) { KernelTimer t(ctx, scatter ? k_scat : k_hist, n); launch(); });
+        HIPCHK(ctx, hipGetLastError());
+        return MAUVE_OK;
+    }
     uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
     HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
     HIPCHK(ctx, ctx->totals.ensure(256 * sizeof(uint32_t)));
