@@ -11,6 +11,11 @@
 
 namespace mems {
 
+// libMems' global behind --repeat-penalty=<negative|zero> (progressiveMauve.cpp:295,606-609: the call site sets it true unless "zero").
+// Frozen form DESIGN.md S11d.  It starts false here, so that no program that never sets it changes; ProgressiveAligner::align maps
+// true to MAUVE_REPEAT_PENALTY_NEGATIVE and false to MAUVE_REPEAT_PENALTY_OFF (mauve_set_repeat_penalty).
+inline bool penalize_repeats = false;
+
 // ---- ProgressiveAligner: setters and align() as called at progressiveMauve.cpp:575-710 -------------------
 // The guide tree and the progressive anchoring run on the device (mauve_progressive_align); the extant
 // sum-of-pairs LCB scoring is DESIGN.md S11, the penalty scaling by conservation and breakpoint distance S11b / S11c, the
@@ -83,6 +88,7 @@ public:
         HipContext &hc = HipContext::global();
         MatchList tmp; tmp.seq_table = seq_table;
         tmp.upload(hc);
+        hc.check(mauve_set_repeat_penalty(hc.get(), penalize_repeats ? MAUVE_REPEAT_PENALTY_NEGATIVE : MAUVE_REPEAT_PENALTY_OFF), "mauve_set_repeat_penalty");
         std::vector<int64_t> dist;
         if (!input_tree_fn_.empty()) {
             std::ifstream in(input_tree_fn_.c_str());

@@ -43,6 +43,12 @@ extern "C" {
 #define MAUVE_LCB_SCORE_LENGTH 0
 #define MAUVE_LCB_SCORE_SP 1
 
+/* repeat penalty on sum-of-pairs anchor scores (progressiveMauve --repeat-penalty, progressiveMauve.cpp:295,606-609; the libMems
+   global penalize_repeats; frozen form DESIGN.md S11d) */
+#define MAUVE_REPEAT_PENALTY_OFF 0
+#define MAUVE_REPEAT_PENALTY_NEGATIVE 1
+#define MAUVE_REPEAT_PENALTY_ZERO 2
+
 typedef struct mauve_ctx mauve_ctx;
 
 typedef struct {
@@ -216,6 +222,23 @@ int mauve_dp_batch_banded(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t 
         1-based on the resident genomes, scores[n] out. ---- */
 int mauve_match_sp_scores(mauve_ctx *ctx, int64_t n, const int64_t *length, const int64_t *start, const mauve_scoring *sc,
                           int64_t *scores);
+
+/* ---- repeat penalty: the libMems global penalize_repeats that progressiveMauve sets from --repeat-penalty=<negative|zero>
+        (progressiveMauve.cpp:295,606-609; libMems-internal, frozen form DESIGN.md S11d).  The mode is held by the context (it
+        survives mauve_set_genomes*) and applies wherever sum-of-pairs LCB scoring is in force (lcb_scoring = MAUVE_LCB_SCORE_SP in
+        mauve_align, mauve_align_matches, mauve_align_begin* and at every node of mauve_progressive_align*): a positive pair score S
+        of a column becomes S*(2-r)/r (NEGATIVE) or S/r (ZERO), r = the larger base multiplicity of the two positions.  Default
+        MAUVE_REPEAT_PENALTY_OFF: every result as without this call.  An unknown mode is MAUVE_ERR_ARG. ---- */
+int mauve_set_repeat_penalty(mauve_ctx *ctx, int mode);
+/* Base multiplicity of one resident genome (the repeat count RepeatHash-style k-mer counting gives a position; S11d): for every
+   0-based position p the minimum, over the valid windows of `pattern` covering p, of the number of valid windows of the genome with
+   the same canonical mer (both strands), saturated at 255; 1 where no valid window covers p.  mult: lens[seq] bytes.  Arguments
+   and errors as mauve_sorted_mer_list. */
+int mauve_seed_multiplicity(mauve_ctx *ctx, int seq, uint64_t pattern, uint8_t *mult);
+/* mauve_match_sp_scores with the repeat penalty of `mode` (multiplicities of `pattern`, S11d); mode MAUVE_REPEAT_PENALTY_OFF
+   returns exactly mauve_match_sp_scores.  The context's own mode is neither read nor changed. */
+int mauve_match_sp_scores_repeat(mauve_ctx *ctx, uint64_t pattern, int mode, int64_t n, const int64_t *length, const int64_t *start,
+                                 const mauve_scoring *sc, int64_t *scores);
 
 /* ---- whole path: doAlignment's hot section (mauveAligner.cpp:523-531,585,629-698,746-760):
         multi-MUMs -> N-way filter -> overlap elimination -> LCBs -> recursive anchoring -> gapped

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libmauve_hip.so")
 
 MODE_MEM, MODE_UNIQUE, MODE_PAIRWISE = 0, 1, 2
 CODING_SEED, SOLID_SEED = 3, 0x7FFFFFFF
+REPEAT_PENALTY_OFF, REPEAT_PENALTY_NEGATIVE, REPEAT_PENALTY_ZERO = 0, 1, 2    # DESIGN.md S11d (progressiveMauve --repeat-penalty)
 K_EXTRACT, K_SORT_HIST, K_SORT_SCAN, K_SORT_SCATTER, K_JOIN, K_EXTEND, K_DP, K_RUNS = range(8)
 KERNEL_NAMES = ["seed_extract", "rs_hist", "rs_rowscan", "rs_scatter", "mum_join", "mum_extend", "dp_step", "mum_runs", "canon_sort", "misc_sort"]
 
@@ -29,6 +30,7 @@ EXPORTS = [
     "mauve_guide_tree", "mauve_breakpoint_counts", "mauve_hmm_params_from", "mauve_apply_homology", "mauve_apply_homology_alignment", "mauve_progressive_align", "mauve_progressive_align_tree",
     "mauve_backbone", "mauve_backbone_alignment", "mauve_backbone_fetch", "mauve_merge_matches",
     "mauve_write_xmfa", "mauve_profile_enable", "mauve_profile_reset", "mauve_profile_get", "mauve_last_stage_times",
+    "mauve_set_repeat_penalty", "mauve_seed_multiplicity", "mauve_match_sp_scores_repeat",
 ]
 
 
@@ -462,6 +464,27 @@ class Context:
         out = np.zeros(max(len(length), 1), np.int64)
         self._chk(self.L.mauve_match_sp_scores(self.h, C.c_int64(len(length)), _p(length, C.c_int64), _p(start, C.c_int64),
                                                C.byref(sc), _p(out, C.c_int64)), "mauve_match_sp_scores")
+        return out[:len(length)].copy()
+
+    def set_repeat_penalty(self, mode):
+        """mauve_set_repeat_penalty: REPEAT_PENALTY_OFF / _NEGATIVE / _ZERO for the sum-of-pairs anchor scores of later calls (S11d)"""
+        self._chk(self.L.mauve_set_repeat_penalty(self.h, int(mode)), "mauve_set_repeat_penalty")
+
+    def seed_multiplicity(self, seq, pattern):
+        """base multiplicities of resident genome `seq` for `pattern` (mauve_seed_multiplicity): uint8[lens[seq]]"""
+        n = self.lens[seq] if 0 <= seq < len(self.lens) else 0      # (an index out of range is the library's to refuse)
+        out = np.zeros(max(n, 1), np.uint8)
+        self._chk(self.L.mauve_seed_multiplicity(self.h, int(seq), C.c_uint64(pattern), _p(out, C.c_uint8)), "mauve_seed_multiplicity")
+        return out[:n].copy()
+
+    def match_sp_scores_repeat(self, pattern, mode, length, start, scoring=None):
+        """repeat-penalized sum-of-pairs scores of ungapped matches (mauve_match_sp_scores_repeat; mode 0 = match_sp_scores)"""
+        sc = scoring or default_scoring()
+        length = np.ascontiguousarray(length, dtype=np.int64)
+        start = np.ascontiguousarray(start, dtype=np.int64).reshape(len(length), self.nseq)
+        out = np.zeros(max(len(length), 1), np.int64)
+        self._chk(self.L.mauve_match_sp_scores_repeat(self.h, C.c_uint64(pattern), int(mode), C.c_int64(len(length)), _p(length, C.c_int64),
+                                                      _p(start, C.c_int64), C.byref(sc), _p(out, C.c_int64)), "mauve_match_sp_scores_repeat")
         return out[:len(length)].copy()
 
     def align(self, params=None, fetch=True, names=None, want_xmfa=False, out=None, compact=False):

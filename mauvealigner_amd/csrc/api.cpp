@@ -216,7 +216,7 @@ void mauve_ctx_destroy(mauve_ctx *c)
     DevBuf *bufs[] = {&c->genomes, &c->keysA, &c->keysB, &c->valsA, &c->valsB, &c->hist, &c->totals, &c->posmask,
                       &c->hit_mask, &c->hit_pos, &c->hit_seg, &c->base_invalid, &c->contig_mask, &c->node_cmask, &c->run_sum, &c->join_ovf, &c->join_bound, &c->dpf_anch, &c->dpf_work, &c->dpf_tot, &c->ch_len, &c->ch_st, &c->ch_crop, &c->ch_ent, &c->ch_ord, &c->ch_rank, &c->ch_node, &c->ch_graph, &c->ch_cnt, &c->ch_anch, &c->ch_lw, &c->ch_anch2, &c->ext_work, &c->bp_work, &c->dp_sp, &c->hom_cols, &c->sorted_rec_keep, &c->ch_big, &c->gap_work, &c->as_wide, &c->res_narrow, &c->dp_pick, &c->dp_wflags, &c->ch_mw, &c->shard_dev, &c->as_work, &c->as_isl, &c->res_cols, &c->sorted_rec, &c->canon_k1, &c->canon_k2, &c->canon_v1, &c->canon_v2, &c->rec_genomes, &c->rec_seg, &c->rec_vinv, &c->rec_vcm, &c->placed_mask, &c->bb_cols, &c->bb_work, &c->bb_query, &c->cand, &c->mlen, &c->mstart, &c->counters, &c->dp_desc, &c->dp_list, &c->dp_codes, &c->dp_off,
                       &c->dp_prof_cnt, &c->dp_prof_mask, &c->dp_prof2_cnt, &c->dp_prof2_mask, &c->dp_tb, &c->dp_meta,
-                      &c->dp_score, &c->dp_cols, &c->dp_rows};
+                      &c->dp_score, &c->dp_cols, &c->dp_rows, &c->rp_wcnt, &c->rp_mult};
     for (DevBuf *b : bufs) b->release();
     c->pin_genomes.release(); c->pin_tail.release(); c->pin_ext.release(); c->pin_chain.release(); c->pin_mask.release(); c->pin_bb.release(); c->pin_asm.release(); c->pin_tab.release(); c->pin_cols.release(); c->pin_anch.release(); c->pin_dcols.release(); c->pin_meta.release(); c->pin_seed.release(); c->pin_dp_in.release(); c->shard_pin.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -295,6 +295,7 @@ int mauve_set_genomes(mauve_ctx *c, int nseq, const uint64_t *const *packed, con
     // would copy every result twice -- and a later fetch is refused instead of handing out half a result.
     if (c->res.dev_pending || c->res.cols_pending) { c->res.dev_pending = false; c->res.cols_pending = false; c->res.stale = true; }
     c->res.genomes_replaced = true;       // what is on the host can still be fetched; mauve_apply_homology / mauve_write_xmfa on it are refused
+    c->genome_gen++;                      // the cached repeat multiplicities belong to the genomes before
     size_t total_words = 0;
     std::vector<uint64_t> off(nseq);
     int64_t total_len = 0;
@@ -485,6 +486,37 @@ int mauve_sorted_mer_list(mauve_ctx *c, int seq, uint64_t pattern, uint64_t *mer
             mer_out[i] = (keys[i] << (64 - 2 * w)) | (vals[i] >> 31);
             pos_out[i] = vals[i] & 0x7fffffffu;
         }
+    return MAUVE_OK;
+}
+
+// the libMems global penalize_repeats (progressiveMauve.cpp:606-609), frozen form DESIGN.md S11d
+int mauve_set_repeat_penalty(mauve_ctx *c, int mode)
+{
+    if (!c) return MAUVE_ERR_ARG;
+    if (mode != MAUVE_REPEAT_PENALTY_OFF && mode != MAUVE_REPEAT_PENALTY_NEGATIVE && mode != MAUVE_REPEAT_PENALTY_ZERO) { c->err = "set_repeat_penalty: unknown mode"; return MAUVE_ERR_ARG; }
+    c->repeat_mode = mode;
+    return MAUVE_OK;
+}
+
+int mauve_seed_multiplicity(mauve_ctx *c, int seq, uint64_t pattern, uint8_t *mult)
+{
+    if (!c) return MAUVE_ERR_ARG;
+    SeedShape sh;
+    if (!make_seed_shape(pattern, &sh)) { c->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
+    if (c->nseq < 1) { c->err = "no genomes set"; return MAUVE_ERR_STATE; }
+    if (seq < 0 || seq >= c->nseq) { c->err = "sequence index out of range"; return MAUVE_ERR_ARG; }
+    const int64_t L = c->lens[(size_t)seq];
+    if (L && !mult) { c->err = "seed_multiplicity: null output"; return MAUVE_ERR_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcm = materialize_tables(c); if (rcm) return rcm; }          // the pass reuses the seed pass's buffers
+    int rc = repeat_multiplicity(c, pattern);
+    if (rc) return rc;
+    if (L) {
+        HIPCHK(c, c->pin_seed.ensure((size_t)L + 64));
+        HIPCHK(c, hipMemcpyAsync(c->pin_seed.p, c->rp_mult.as<uint8_t>() + c->rp_off[(size_t)seq], (size_t)L, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        memcpy(mult, c->pin_seed.p, (size_t)L);
+    }
     return MAUVE_OK;
 }
 

@@ -118,9 +118,13 @@ __global__ void __launch_bounds__(256) as_islands(const Island *__restrict__ isl
 // ---- extant sum-of-pairs score of ungapped matches ---------------------------------------------------------
 // One wave per match: a lane takes every 64th column, reads the base of every present component from the packed genomes
 // (a reverse component from its right end, complemented), adds the substitution scores of all pairs; wave reduction.
+// MODE != MAUVE_REPEAT_PENALTY_OFF: the lane also gathers the base multiplicity of every component's position beside
+// its base, and a positive pair score S becomes S*(2-r)/r (NEGATIVE) or S/r (ZERO), r = the larger multiplicity of the pair.
+// MODE OFF compiles to the plain score (the multiplicities are never read).
 struct SpGenomes { uint64_t word_off[MAUVE_MAX_SEQ]; int32_t s[4][4]; };
+template <int MODE>
 __global__ void __launch_bounds__(256) sp_score_matches(const uint64_t *__restrict__ packed, SpGenomes G, int n, const int64_t *__restrict__ rec,
-                                                        uint32_t nm, int64_t *__restrict__ out)
+                                                        uint32_t nm, int64_t *__restrict__ out, SpMult M)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nw = (gridDim.x * 256u) >> 6;
@@ -130,6 +134,7 @@ __global__ void __launch_bounds__(256) sp_score_matches(const uint64_t *__restri
         int64_t acc = 0;
         for (int64_t c = lane; c < len; c += 64) {
             uint32_t have = 0, bases = 0;                      // 2 bits per component
+            uint64_t mlo = 0, mhi = 0;                         // (MODE) a byte of multiplicity per component
             for (int g = 0; g < n; g++) {
                 const int64_t st = r[1 + g];
                 if (!st) continue;
@@ -137,11 +142,17 @@ __global__ void __launch_bounds__(256) sp_score_matches(const uint64_t *__restri
                 uint32_t b = (uint32_t)(packed[G.word_off[g] + (uint64_t)(p >> 5)] >> (2 * (p & 31))) & 3u;
                 if (st < 0) b = 3u - b;
                 have |= 1u << g; bases |= b << (2 * g);          // n <= 16 (checked on the host)
+                if (MODE) { const uint64_t mv = M.p[M.off[g] + (uint64_t)p]; if (g < 8) mlo |= mv << (8 * g); else mhi |= mv << (8 * (g - 8)); }
             }
             for (int x = 0; x < n; x++) {
                 if (!(have >> x & 1)) continue;
                 const uint32_t bx = (bases >> (2 * x)) & 3u;
-                for (int y = x + 1; y < n; y++) if (have >> y & 1) acc += G.s[bx][(bases >> (2 * y)) & 3u];
+                const uint32_t mx = MODE ? (uint32_t)((x < 8 ? mlo >> (8 * x) : mhi >> (8 * (x - 8))) & 255u) : 0u;
+                for (int y = x + 1; y < n; y++)
+                    if (have >> y & 1) {
+                        const uint32_t my = MODE ? (uint32_t)((y < 8 ? mlo >> (8 * y) : mhi >> (8 * (y - 8))) & 255u) : 0u;
+                        acc += sp_pair<MODE>(G.s[bx][(bases >> (2 * y)) & 3u], mx, my);
+                    }
             }
         }
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
@@ -188,7 +199,18 @@ int match_sp_scores(mauve_ctx *c, const MatchVec &m, const int *gmap, const mauv
     memcpy(c->pin_asm.p, m.d.data(), rb);
     HIPCHK(c, hipMemcpyAsync(d_rec, c->pin_asm.p, rb, hipMemcpyHostToDevice, c->stream));
     const uint32_t blocks = (uint32_t)std::min<size_t>((nm + 3) / 4, 256 * 8);
-    hipLaunchKernelGGL(sp_score_matches, dim3(blocks), dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), G, n, d_rec, (uint32_t)nm, d_out);
+    SpMult M; memset(&M, 0, sizeof M);
+    if (c->rp_now != MAUVE_REPEAT_PENALTY_OFF) {            // the multiplicities repeat_begin left for this call
+        if (c->rp_gen != c->genome_gen) { c->err = "sp scores: repeat multiplicities missing"; return MAUVE_ERR_STATE; }
+        M.p = c->rp_mult.as<uint8_t>();
+        for (int g = 0; g < n; g++) M.off[g] = c->rp_off[(size_t)(gmap ? gmap[g] : g)];
+    }
+    if (c->rp_now == MAUVE_REPEAT_PENALTY_NEGATIVE)
+        hipLaunchKernelGGL(sp_score_matches<MAUVE_REPEAT_PENALTY_NEGATIVE>, dim3(blocks), dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), G, n, d_rec, (uint32_t)nm, d_out, M);
+    else if (c->rp_now == MAUVE_REPEAT_PENALTY_ZERO)
+        hipLaunchKernelGGL(sp_score_matches<MAUVE_REPEAT_PENALTY_ZERO>, dim3(blocks), dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), G, n, d_rec, (uint32_t)nm, d_out, M);
+    else
+        hipLaunchKernelGGL(sp_score_matches<MAUVE_REPEAT_PENALTY_OFF>, dim3(blocks), dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), G, n, d_rec, (uint32_t)nm, d_out, M);
     HIPCHK(c, hipGetLastError());
     int64_t *h_out = reinterpret_cast<int64_t *>(c->pin_asm.as<char>() + rb);
     HIPCHK(c, hipMemcpyAsync(h_out, d_out, nm * 8, hipMemcpyDeviceToHost, c->stream));

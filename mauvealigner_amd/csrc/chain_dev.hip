@@ -553,10 +553,12 @@ int chain_order_device(mauve_ctx *c, int N, int64_t nl, int64_t min_gap, int64_t
 // the lengths).  The compact graph arrives on the host in c->pin_chain (ChainGraphHost): weight[K], orient[K], prev[K*N],
 // next[K*N].  seg0 != nullptr: a recursion batch (forward matches only, nodes confined to their gaps).
 // extant sum-of-pairs score of every cropped record of the chain (sp_score_matches' rule on the chain's int32 records): a wave per match,
-// a lane takes every 64th column; dead records (length <= 0) score 0
+// a lane takes every 64th column; dead records (length <= 0) score 0.  MODE != OFF: repeat-penalized (S11d), the base multiplicities
+// gathered beside the bases as sp_score_matches does; MODE OFF never reads them
 struct ChSpGenomes { uint64_t word_off[MAUVE_MAX_SEQ]; int32_t s[4][4]; };
+template <int MODE>
 __global__ void __launch_bounds__(256) ch_sp_scores(const uint64_t *__restrict__ packed, ChSpGenomes G, int N, const int32_t *__restrict__ len, const int32_t *__restrict__ st,
-                                                    uint32_t n, int64_t *__restrict__ out)
+                                                    uint32_t n, int64_t *__restrict__ out, SpMult M)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, nw = (gridDim.x * 256u) >> 6;
@@ -565,6 +567,7 @@ __global__ void __launch_bounds__(256) ch_sp_scores(const uint64_t *__restrict__
         int64_t acc = 0;
         for (int64_t c = lane; c < L; c += 64) {
             uint32_t have = 0, bases = 0;
+            uint64_t mlo = 0, mhi = 0;
             for (int g = 0; g < N; g++) {
                 const int64_t s0 = st[(size_t)i * N + g];
                 if (!s0) continue;
@@ -572,11 +575,17 @@ __global__ void __launch_bounds__(256) ch_sp_scores(const uint64_t *__restrict__
                 uint32_t b = (uint32_t)(packed[G.word_off[g] + (uint64_t)(p >> 5)] >> (2 * (p & 31))) & 3u;
                 if (s0 < 0) b = 3u - b;
                 have |= 1u << g; bases |= b << (2 * g);
+                if (MODE) { const uint64_t mv = M.p[M.off[g] + (uint64_t)p]; if (g < 8) mlo |= mv << (8 * g); else mhi |= mv << (8 * (g - 8)); }
             }
             for (int x = 0; x < N; x++) {
                 if (!(have >> x & 1)) continue;
                 const uint32_t bx = (bases >> (2 * x)) & 3u;
-                for (int y = x + 1; y < N; y++) if (have >> y & 1) acc += G.s[bx][(bases >> (2 * y)) & 3u];
+                const uint32_t mx = MODE ? (uint32_t)((x < 8 ? mlo >> (8 * x) : mhi >> (8 * (x - 8))) & 255u) : 0u;
+                for (int y = x + 1; y < N; y++)
+                    if (have >> y & 1) {
+                        const uint32_t my = MODE ? (uint32_t)((y < 8 ? mlo >> (8 * y) : mhi >> (8 * (y - 8))) & 255u) : 0u;
+                        acc += sp_pair<MODE>(G.s[bx][(bases >> (2 * y)) & 3u], mx, my);
+                    }
             }
         }
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
@@ -663,8 +672,19 @@ int chain_device_graph(mauve_ctx *c, int N, int64_t maxlen_in, const uint32_t *s
         ChSpGenomes SG; memset(&SG, 0, sizeof SG);
         for (int g = 0; g < N; g++) SG.word_off[g] = c->word_off[(size_t)g];
         memcpy(SG.s, sp_scoring->matrix, sizeof SG.s);
-        hipLaunchKernelGGL(ch_sp_scores, dim3((uint32_t)std::min<size_t>(((size_t)n + 3) / 4, 256 * 8)), dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), SG, N, len, st, n,
-                           c->ch_mw.as<int64_t>());
+        SpMult M; memset(&M, 0, sizeof M);
+        if (c->rp_now != MAUVE_REPEAT_PENALTY_OFF) {        // DESIGN.md S11d (the records' genomes are the context's 0 .. N-1)
+            if (c->rp_gen != c->genome_gen) { c->err = "chain_device: repeat multiplicities missing"; return MAUVE_ERR_STATE; }
+            M.p = c->rp_mult.as<uint8_t>();
+            for (int g = 0; g < N; g++) M.off[g] = c->rp_off[(size_t)g];
+        }
+        const dim3 grid((uint32_t)std::min<size_t>(((size_t)n + 3) / 4, 256 * 8));
+        if (c->rp_now == MAUVE_REPEAT_PENALTY_NEGATIVE)
+            hipLaunchKernelGGL(ch_sp_scores<MAUVE_REPEAT_PENALTY_NEGATIVE>, grid, dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), SG, N, len, st, n, c->ch_mw.as<int64_t>(), M);
+        else if (c->rp_now == MAUVE_REPEAT_PENALTY_ZERO)
+            hipLaunchKernelGGL(ch_sp_scores<MAUVE_REPEAT_PENALTY_ZERO>, grid, dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), SG, N, len, st, n, c->ch_mw.as<int64_t>(), M);
+        else
+            hipLaunchKernelGGL(ch_sp_scores<MAUVE_REPEAT_PENALTY_OFF>, grid, dim3(256), 0, c->stream, c->genomes.as<uint64_t>(), SG, N, len, st, n, c->ch_mw.as<int64_t>(), M);
         mw = c->ch_mw.as<int64_t>();
     }
     const LcbNodes ln{len, st, n, N, ordc, rank, cnt, node_of, weight, orient, gapid, mw};

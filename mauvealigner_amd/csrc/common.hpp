@@ -319,9 +319,35 @@ struct mauve_ctx {
     PinnedBuf shard_pin;                  // ... and its page-locked host side
     mauve_shard_stats shard_stat = {0, 0, 0, 0.0};
 
+    // repeat penalty: the caller's mode, the mode in force for the alignment call under way (read by the sum-of-pairs
+    // scoring launches), and the base multiplicities of the resident genomes for one seed pattern, cached by (genome generation, pattern)
+    int repeat_mode = MAUVE_REPEAT_PENALTY_OFF, rp_now = MAUVE_REPEAT_PENALTY_OFF;
+    uint64_t genome_gen = 0;             // bumped by every mauve_set_genomes
+    uint64_t rp_gen = 0, rp_pat = 0;     // what rp_mult holds (rp_gen 0: nothing)
+    DevBuf rp_wcnt, rp_mult;             // per window: its genome's count of the canonical mer (0 = invalid window); per base: the multiplicity
+    std::vector<uint64_t> rp_off;        // byte offset of every genome in rp_mult (16-byte aligned)
+
     AlignResult res;
     AlignState ast;
     mauve_stage_times stage{};
+};
+
+// base multiplicities of the resident genomes as a kernel argument: genome g's at p + off[g] (sp_score_matches, ch_sp_scores)
+struct SpMult { const uint8_t *p; uint64_t off[MAUVE_MAX_SEQ]; };
+// one pair of a sum-of-pairs column: substitution score s, base multiplicities mx, my of the two positions
+template <int MODE>
+__device__ __forceinline__ int64_t sp_pair(int32_t s, uint32_t mx, uint32_t my)
+{
+    if (MODE == MAUVE_REPEAT_PENALTY_OFF || s <= 0) return s;
+    const int64_t r = (int64_t)(mx > my ? mx : my);
+    return MODE == MAUVE_REPEAT_PENALTY_NEGATIVE ? (int64_t)s * (2 - r) / r : (int64_t)s / r;
+}
+
+// the repeat penalty of one alignment call: in force from repeat_begin to the end of the scope
+struct RepeatScope {
+    mauve_ctx *c;
+    explicit RepeatScope(mauve_ctx *ctx) : c(ctx) { c->rp_now = MAUVE_REPEAT_PENALTY_OFF; }
+    ~RepeatScope() { c->rp_now = MAUVE_REPEAT_PENALTY_OFF; }
 };
 
 // RAII-less helper: time one kernel launch on ctx->stream when profiling is on.
@@ -389,7 +415,13 @@ void host_left_orders(const MatchVec &m, ChainOrders &orders);       // per-geno
 void host_lcb_chain(const MatchVec &m, int64_t min_weight, bool collinear, std::vector<int64_t> &match_lcb, int64_t &n_lcb,
                     const ChainOrders *orders = nullptr, const int64_t *match_weight = nullptr);
 // extant sum-of-pairs scores of the matches of m (n components; gmap: their genomes, nullptr = 0..n-1), assemble_dev.hip
+// (c->rp_now != OFF: penalized by the multiplicities in c->rp_mult)
 int match_sp_scores(mauve_ctx *c, const MatchVec &m, const int *gmap, const mauve_scoring *sc, std::vector<int64_t> &out);
+// base multiplicities of the resident genomes for `pattern` into c->rp_mult (seed_pass.hip; cached)
+int repeat_multiplicity(mauve_ctx *c, uint64_t pattern);
+// the root seed pattern of a call (seed families: the first of the family) -> multiplicities, c->rp_now = the context's mode; only
+// under sum-of-pairs LCB scoring (pipeline.cpp)
+int repeat_begin(mauve_ctx *c, const mauve_params *p, int w, uint64_t pat);
 int64_t sp_default_min_weight(int w, int n, const mauve_scoring *sc);
 
 void lcb_greedy(int N, int32_t K, int64_t *weight, const uint32_t *orient_bits, int32_t *prevv, int32_t *nextv, int64_t min_weight,

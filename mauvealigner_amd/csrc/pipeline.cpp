@@ -209,14 +209,21 @@ static int extend_lcbs(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
 
 // The searches of the seed family of weight w (ranks 0..2, longest seed first; ties: the higher rank, as the call site's
 // sort leaves them, progressiveMauve.cpp:515-521) merged into one list (host_merge_matches).
-int seed_family_matches(mauve_ctx *c, const GenomeSet &gs, int w, int mode, uint64_t mask, MatchVec &out)
+// the ranks of the seed family of weight w in search order: longest seed first
+static void family_order(int w, int order[3])
 {
-    const int n = gs.nseq;
-    int order[3] = {0, 1, 2};
+    for (int k = 0; k < 3; k++) order[k] = k;
     std::sort(order, order + 3, [&](int a, int b) {
         const int la = mauve_seed_length(mauve_get_seed(w, a)), lb = mauve_seed_length(mauve_get_seed(w, b));
         return la != lb ? la > lb : a > b;
     });
+}
+
+int seed_family_matches(mauve_ctx *c, const GenomeSet &gs, int w, int mode, uint64_t mask, MatchVec &out)
+{
+    const int n = gs.nseq;
+    int order[3];
+    family_order(w, order);
     out = MatchVec(n);
     for (int k = 0; k < 3; k++) {
         const uint64_t pat = mauve_get_seed(w, order[k]);
@@ -244,6 +251,25 @@ static const bool g_trace_pipeline = getenv("MAUVE_TRACE") != nullptr;     // re
 // begin : seed pass, chaining, recursive anchoring, interval descriptors        (every rank, deterministic)
 // dp    : gapped alignment of a subset of the intervals                         (each rank its share)
 // finish: assembly of the interval table from the columns of ALL intervals      (every rank)
+// the repeat penalty of a call whose LCBs are score-weighted -- the multiplicities of the pattern of its root search
+// (seed families: the family's first), then the context's mode in force until the caller's RepeatScope ends
+int repeat_begin(mauve_ctx *c, const mauve_params *p, int w, uint64_t pat)
+{
+    c->rp_now = MAUVE_REPEAT_PENALTY_OFF;
+    if (c->repeat_mode == MAUVE_REPEAT_PENALTY_OFF || p->lcb_scoring != MAUVE_LCB_SCORE_SP) return MAUVE_OK;
+    if (p->seed_family) {
+        int order[3];
+        family_order(w, order);
+        pat = 0;
+        for (int k = 0; k < 3 && !pat; k++) pat = mauve_get_seed(w, order[k]);
+        if (!pat) { c->err = "repeat penalty: no seed of this weight"; return MAUVE_ERR_ARG; }
+    }
+    const int rc = repeat_multiplicity(c, pat);
+    if (rc) return rc;
+    c->rp_now = c->repeat_mode;
+    return MAUVE_OK;
+}
+
 static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = false, const MatchVec *given = nullptr, bool want_tail = false)
 {
     const int N = c->nseq;
@@ -269,6 +295,8 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     w = mauve_seed_weight(pat);
     const uint32_t full = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
     S.full = full;
+    RepeatScope rp_scope(c);                         // the anchor scores of this call's LCBs
+    { const int rr = repeat_begin(c, p, w, pat); if (rr) return rr; }
 
     // ---- seed pass: N-way multi-MUMs (the multiplicity filter is pushed into the join) ----
     // In its shadow (the host would otherwise wait for the kernels): bring the column buffer back to the
@@ -943,6 +971,24 @@ int mauve_match_sp_scores(mauve_ctx *c, int64_t n, const int64_t *length, const 
     if (rc) return rc;
     std::copy(out.begin(), out.end(), scores);
     return MAUVE_OK;
+}
+
+int mauve_match_sp_scores_repeat(mauve_ctx *c, uint64_t pattern, int mode, int64_t n, const int64_t *length, const int64_t *start,
+                                 const mauve_scoring *sc, int64_t *scores)
+{
+    if (!c || !sc || n < 0 || (n && (!length || !start || !scores))) return MAUVE_ERR_ARG;
+    if (mode != MAUVE_REPEAT_PENALTY_OFF && mode != MAUVE_REPEAT_PENALTY_NEGATIVE && mode != MAUVE_REPEAT_PENALTY_ZERO) { c->err = "match_sp_scores_repeat: unknown mode"; return MAUVE_ERR_ARG; }
+    SeedShape sh;
+    if (!make_seed_shape(pattern, &sh)) { c->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
+    if (mode == MAUVE_REPEAT_PENALTY_OFF) return mauve_match_sp_scores(c, n, length, start, sc, scores);
+    if (c->nseq < 2) { c->err = "match_sp_scores: at least two genomes required"; return MAUVE_ERR_STATE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rcm = materialize_tables(c); if (rcm) return rcm; }          // the multiplicity pass reuses the seed pass's buffers
+    int rc = repeat_multiplicity(c, pattern);
+    if (rc) return rc;
+    RepeatScope rp_scope(c);
+    c->rp_now = mode;
+    return mauve_match_sp_scores(c, n, length, start, sc, scores);
 }
 
 int mauve_align_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const int64_t *length, const int64_t *start, mauve_align_sizes *sizes)

@@ -588,6 +588,8 @@ static int progressive_core(mauve_ctx *c, const mauve_params *p, mauve_align_siz
     int w = p->seed_weight > 0 ? p->seed_weight : mauve_default_seed_weight(sum / N);
     uint64_t pat = p->seed_pattern ? p->seed_pattern : mauve_get_seed(w, p->seed_rank);
     if (!pat) { c->err = "progressive_align: no seed pattern for this weight/rank"; return MAUVE_ERR_ARG; }
+    RepeatScope rp_scope(c);                         // whole-genome multiplicities of the root pattern, once for every node
+    { const int rr = repeat_begin(c, p, mauve_seed_weight(pat), pat); if (rr) return rr; }
     Prog P; P.c = c; P.p = p; P.N = N;
     P.left.assign((size_t)(2 * N - 1), -1); P.right.assign((size_t)(2 * N - 1), -1);
     int rc = 0;

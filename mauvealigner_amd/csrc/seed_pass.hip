@@ -2339,3 +2339,142 @@ int seed_matches_to_host(mauve_ctx *ctx)
     ctx->matches_pending = false;
     return MAUVE_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// repeat multiplicity of every base: the extract and the radix sort of the seed pass over all windows of the
+// resident genomes, then
+//   rp_count    : every window learns the size of its (canonical mer, genome) run in the sorted list -- the sort is stable on the
+//                 global window index, so a genome's windows of one mer are contiguous inside the mer's run -- saturated at 255,
+//                 and stores it at its window index (a byte per window; 0 = invalid window: contig join or ambiguous base)
+//   rp_span_min : per genome, 4096 positions per workgroup: the window counts of the tile and its span-1 halo in LDS, each thread
+//                 the minimum over the covering windows of four consecutive positions (1 where none is valid), one 4-byte store
+// ------------------------------------------------------------------------------------------------
+template <typename KeyT>
+__global__ void __launch_bounds__(256) rp_count(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n, GenomeTab tab,
+                                                uint8_t *__restrict__ wcnt)
+{
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const KeyT k = keys[i];
+        const uint32_t w = vals[i] & 0x7fffffffu;
+        if (k == (KeyT)~0ULL) { wcnt[w] = 0; continue; }
+        const int g = genome_of(w, tab);
+        const uint32_t lo = tab.gpos_off[g], hi = tab.gpos_off[g + 1];
+        uint32_t c = 1;                                        // the walks stop at the saturation count: at most 254 steps each way
+        for (uint32_t j = i; j > 0 && c < 255u; j--) {
+            const uint32_t v = vals[j - 1] & 0x7fffffffu;
+            if (keys[j - 1] != k || v < lo || v >= hi) break;
+            c++;
+        }
+        for (uint32_t j = i + 1; j < n && c < 255u; j++) {
+            const uint32_t v = vals[j] & 0x7fffffffu;
+            if (keys[j] != k || v < lo || v >= hi) break;
+            c++;
+        }
+        wcnt[w] = (uint8_t)c;
+    }
+}
+
+constexpr int RP_TILE = 4096;
+struct RpOut { int64_t len[MAUVE_MAX_SEQ]; uint64_t off[MAUVE_MAX_SEQ]; };
+__global__ void __launch_bounds__(256) rp_span_min(const uint8_t *__restrict__ wcnt, GenomeTab tab, RpOut o, int span, uint8_t *__restrict__ mult)
+{
+    // c[t] = count of window p0 - (span - 1) + t, t < RP_TILE + span - 1 (0 outside the genome's windows)
+    __shared__ uint8_t c[RP_TILE + MAUVE_MAX_SEED_SPAN];
+    const int g = blockIdx.y;
+    const int64_t L = o.len[g];
+    const int64_t p0 = (int64_t)blockIdx.x * RP_TILE;
+    if (p0 >= L) return;                                       // (the grid is sized for the longest genome; uniform per workgroup)
+    const int64_t nw = tab.nwin[g], w0 = p0 - (span - 1);
+    const uint8_t *W = wcnt + tab.gpos_off[g];
+    for (int t = threadIdx.x; t < RP_TILE + span - 1; t += 256) {
+        const int64_t w = w0 + t;
+        c[t] = (w >= 0 && w < nw) ? W[w] : (uint8_t)0;
+    }
+    __syncthreads();
+    uint8_t *out = mult + o.off[g];
+#pragma unroll 1
+    for (int i = 0; i < 4; i++) {
+        const int j = i * 1024 + (int)threadIdx.x * 4;        // position p0 + j + k covers the windows at t = j + k .. j + k + span - 1
+        const int64_t p = p0 + j;
+        if (p >= L) break;
+        uint32_t m0 = 256, m1 = 256, m2 = 256, m3 = 256;       // 256: no valid window yet
+        for (int t = 0; t < span + 3; t++) {
+            uint32_t v = c[j + t]; v = v ? v : 256u;
+            if (t < span) m0 = min(m0, v);
+            if (t >= 1 && t < span + 1) m1 = min(m1, v);
+            if (t >= 2 && t < span + 2) m2 = min(m2, v);
+            if (t >= 3) m3 = min(m3, v);
+        }
+        const uint32_t b = (m0 & 255u ? m0 : 1u) | (m1 & 255u ? m1 : 1u) << 8 | (m2 & 255u ? m2 : 1u) << 16 | (m3 & 255u ? m3 : 1u) << 24;
+        if (p + 3 < L) *reinterpret_cast<uint32_t *>(out + p) = b;     // (o.off and p are multiples of 4)
+        else for (int k = 0; k < 4 && p + k < L; k++) out[p + k] = (uint8_t)(b >> (8 * k));
+    }
+}
+static_assert(RP_TILE == RS_TILE, "the multiplicity pass sorts with the histograms seed_extract_all leaves, tiled like the radix sort");
+
+template <typename KeyT>
+static int rp_windows(mauve_ctx *c, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, uint32_t n)
+{
+    HIPCHK(c, c->keysA.ensure((size_t)n * sizeof(KeyT)));
+    HIPCHK(c, c->keysB.ensure((size_t)n * sizeof(KeyT)));
+    HIPCHK(c, c->valsA.ensure((size_t)n * 4));
+    HIPCHK(c, c->valsB.ensure((size_t)n * 4));
+    const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
+    HIPCHK(c, c->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
+    KeyT *keys = c->keysA.as<KeyT>(); uint32_t *vals = c->valsA.as<uint32_t>();
+    const uint64_t *packed = gs.buf->as<uint64_t>();
+    const uint64_t *vmask = gs.vmask ? gs.vmask->as<uint64_t>() : nullptr;      // ambiguous bases
+    const uint64_t *cmask = gs.cmask ? gs.cmask->as<uint64_t>() : nullptr;      // contig joins
+    {
+        KernelTimer t(c, MAUVE_K_EXTRACT, n);
+        if (sh.span <= 32 && sh.weight <= 15)
+            hipLaunchKernelGGL((seed_extract_all<KeyT, false, true>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
+                               c->hist.as<uint32_t>(), nblk, vmask, 0, cmask);
+        else
+            hipLaunchKernelGGL((seed_extract_all<KeyT, false, false>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
+                               c->hist.as<uint32_t>(), nblk, vmask, 0, cmask);
+    }
+    HIPCHK(c, hipGetLastError());
+    // the mer bits only: an invalid window's all-ones key has ones there that no canonical mer has (min(F, R) is never all T),
+    // so the invalid windows end the list
+    int rc = sort_pairs<KeyT>(c, n, 2 * sh.weight, &keys, &vals, c->keysB.as<KeyT>(), c->valsB.as<uint32_t>(), true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rp_count<KeyT>, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->cus * 16)), dim3(256), 0, c->stream, keys, vals, n, tab,
+                       c->rp_wcnt.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    return MAUVE_OK;
+}
+
+int repeat_multiplicity(mauve_ctx *c, uint64_t pattern)
+{
+    SeedShape sh;
+    if (!make_seed_shape(pattern, &sh)) { c->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
+    if (c->nseq < 1) { c->err = "no genomes set"; return MAUVE_ERR_STATE; }
+    if (c->rp_gen == c->genome_gen && c->rp_pat == pattern) return MAUVE_OK;
+    const GenomeSet gs = main_genome_set(c);
+    GenomeTab tab; int64_t total = 0;
+    int rc = build_tab(c, gs, sh.span, &tab, &total);
+    if (rc) return rc;
+    c->rp_gen = 0;                                             // (nothing valid while it is rebuilt)
+    RpOut o; memset(&o, 0, sizeof o);
+    c->rp_off.assign((size_t)c->nseq, 0);
+    uint64_t bytes = 0; int64_t maxlen = 0;
+    for (int g = 0; g < c->nseq; g++) {
+        o.len[g] = c->lens[(size_t)g]; o.off[g] = bytes; c->rp_off[(size_t)g] = bytes;
+        bytes += ((uint64_t)c->lens[(size_t)g] + 15) & ~(uint64_t)15;
+        maxlen = std::max(maxlen, c->lens[(size_t)g]);
+    }
+    HIPCHK(c, c->rp_mult.ensure(bytes + 16));
+    HIPCHK(c, c->rp_wcnt.ensure((size_t)total + 16));
+    if (total > 0) {
+        rc = 2 * sh.weight <= 32 ? rp_windows<uint32_t>(c, gs, sh, tab, (uint32_t)total) : rp_windows<uint64_t>(c, gs, sh, tab, (uint32_t)total);
+        if (rc) return rc;
+    }
+    if (maxlen > 0) {
+        hipLaunchKernelGGL(rp_span_min, dim3((uint32_t)((maxlen + RP_TILE - 1) / RP_TILE), (uint32_t)c->nseq), dim3(256), 0, c->stream,
+                           c->rp_wcnt.as<uint8_t>(), tab, o, sh.span, c->rp_mult.as<uint8_t>());
+        HIPCHK(c, hipGetLastError());
+    }
+    c->rp_gen = c->genome_gen; c->rp_pat = pattern;
+    return MAUVE_OK;
+}
