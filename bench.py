@@ -7,13 +7,19 @@ FASTA parse and XMFA text formatting)".  A "step" is therefore: upload of the pa
 pass of the whole hot path (mauve_align / mauve_progressive_align) and the copy of every result array into the caller's
 buffers (mauve_align_fetch).  The caller's buffers are page-locked (mauve_host_alloc), as a production caller's would be.
 `value` is that figure; the same pass with the genomes already resident in HBM and the results left there is reported
-beside it as `device_resident` (never as `value`).
+beside it as `device_resident` (--full only; never as `value`).
 
 Workload at N = 1: BASELINE config C3 -- 5 x 5 Mbp genomes, ~3 % divergence, ~50 inversions, seed weight 15: the
-configuration the >= 50 Mbp/s target of `north_star` is quoted on.  The other BASELINE configs are measured in the same
-run and reported as objects of their own ("c2", "c4", "c5"), each with its stage times, roofline and CPU baseline:
-C2 (3 x 5 Mbp), C4 (8 x 2 Mbp, progressive path), C5 (2 x 100 Mbp, default seed weight 19, 64-bit keys).
---config picks another primary workload; --only-primary skips the others.
+configuration the >= 50 Mbp/s target of `north_star` is quoted on.  --config picks another primary workload.
+
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs if asked and prints
+the JSON line.  --full adds every side measurement, each in passes of its own after the timed steps: the wide fetch, the
+device-resident pass with its stage times, the per-kernel profile and roofline, the other lcb_extension setting, accuracy
+against the generator's truth, the backbone and homology calls, the CPU baselines (which double as the full-size parity
+check against the oracle) and the other BASELINE configs, reported as objects of their own ("c2", "c4", "c5"), each with
+its stage times, roofline and CPU baseline: C2 (3 x 5 Mbp), C4 (8 x 2 Mbp, progressive path), C5 (2 x 100 Mbp, default
+seed weight 19, 64-bit keys).  Within --full, --only-primary skips the side passes and the other configs and
+--no-cpu-baseline the CPU baselines.
 
 --gpus N, two forms (--shard):
   replicas (default): every rank aligns its own genome set of the workload's shape (different PRNG stream), no
@@ -22,7 +28,7 @@ C2 (3 x 5 Mbp), C4 (8 x 2 Mbp, progressive path), C5 (2 x 100 Mbp, default seed 
              passes of the guide tree, the recursion's gaps, the gapped-DP intervals -- are LPT-sharded over the ranks and
              their results exchanged with RCCL all_gathers (mauvealigner_amd/parallel.py): strong scaling.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full; null in a plain run):
   roofline     -- dominant HBM kernel (by HIP-event time on the library's stream): algorithmic bytes per launch
                    / average launch duration, against the 8 TB/s HBM peak; the seed-pass
                   aggregate (SURVEY.md 8d's B_seed per position) and the DP kernel's GCUPS beside it.
@@ -444,9 +450,12 @@ def main():
     ap.add_argument("--config", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--shard", default="replicas", choices=["replicas", "lcb"])
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the genomes (debug only; 1.0 = BASELINE size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement: wide fetch, device-resident pass, kernel profile and roofline, "
+                         "accuracy, backbone, CPU baselines with the oracle parity check, the other configs (default: only what `value` needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-secondary", "--only-primary", dest="no_secondary", action="store_true",
-                    help="skip the side measurements (the other configs, the pass with the other lcb_extension setting, the backbone call)")
+                    help="with --full: skip the side measurements (the other configs, the pass with the other lcb_extension setting, the backbone call)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write the result arrays of the last timed step to DIR/<name>.npy (float64; at most 64 MB, larger ones as a seeded sample of rows)")
     args = ap.parse_args()
@@ -480,7 +489,8 @@ def main():
         if dist is not None and not shard_lcb and world > 1:
             print("bench.py: %s with --gpus N needs --shard lcb" % args.config, file=sys.stderr)
             sys.exit(2)
-    genomes, origins, L = make_workload(args.config, args.scale, 0 if shard_lcb else rank, track=args.config in ("C2", "C3"))
+    # (the generator's truth feeds only --full's accuracy figure; the genomes are the same with or without it)
+    genomes, origins, L = make_workload(args.config, args.scale, 0 if shard_lcb else rank, track=args.full and args.config in ("C2", "C3"))
     total_bp = sum(len(g) for g in genomes)
     ctx = _lib.Context(local_rank)
     weight = seed_weight_of(cfg, genomes)
@@ -538,11 +548,11 @@ def main():
         total_all = float(total_bp)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_all / 1e6 / (elapsed / args.steps)
-    side = rank == 0 and world == 1                          # the side measurements: one GPU, rank 0
+    side = args.full and rank == 0 and world == 1            # the side measurements: --full, one GPU, rank 0
     gpu_result = {k: np.array(v, copy=True) for k, v in res.items() if isinstance(v, np.ndarray)} if side else None
 
     roofline, kern_ms, extras, stages = None, {}, {}, {}
-    if rank == 0 and not shard_lcb:
+    if args.full and rank == 0 and not shard_lcb:
         nw = max(3, args.steps // 2)
         e_w, _ = rn.time_host(nw, 1, compact=False)
         extras["fetch_wide"] = {"ms_per_step": round(e_w / nw * 1e3, 3), "Mbp_s": round(total_bp / 1e6 / (e_w / nw), 2),
@@ -637,7 +647,7 @@ def main():
             "metric": "aligned Mbp/s (seed+extend+DP)", "value": round(value, 2), "unit": "Mbp/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "strong" if shard_lcb else "weak", "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": (cfg["text"] % L) + ", recursive anchoring + gapped DP on",
                        "genomes_per_gpu": cfg["n"], "genome_length": L, "seed_weight": weight, "parallelism": par,
                        "extend_lcbs": int(params.extend_lcbs), "max_extension_iters": int(params.max_extension_iters),

@@ -114,7 +114,7 @@ def main():
         except Exception:
             cal = 2.0                                  # MI355X_MICROARCH.md: FETCH_SIZE reports half the bytes of a wide coalesced streaming read
     traffic = {}
-    cmd_text = ("Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --config " + cfg +
+    cmd_text = ("Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --config " + cfg +
                 "` (" + str(passes) + " passes of the hot path in the process: warmup, timed host-to-host, device-resident and HIP-event legs, all over BASELINE config " + cfg + ": " +
                 bench["config"]["workload"][:70] + " ..., P = " + str(int(P)) + " windows per pass).  PMC passes: `--pmc FETCH_SIZE`, `--pmc WRITE_SIZE` and `--pmc SQ_LDS_BANK_CONFLICT "
                 "SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY`, separate runs (tools/profile_gpu.sh).  The raw `--stats` table is " + tag + "_kernel_stats.csv; the table below is built "
@@ -159,7 +159,7 @@ def main():
     except Exception:
         commit = "?"
     traffic["_meta"] = {"round": tag, "commit": commit, "kernel_source_digest": kernel_source_digest(),
-                        "command": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE --kernel-trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --config " + cfg}
+                        "command": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --config " + cfg}
     tpath = os.path.join(DST, "roofline_traffic.json")
     if cfg == "C3":
         try:
