@@ -138,6 +138,14 @@ int orc_eliminate_overlaps(orc_matches *m);   /* in place, N-way input */
 int orc_compute_lcbs_w(const orc_matches *m, const int64_t *match_weight, int64_t min_weight, int collinear, orc_lcbs *out);
 void orc_match_sp_scores(int nseq, const uint8_t *const *codes, const orc_matches *m, const orc_scoring *sc, int64_t *out);
 int orc_compute_lcbs(const orc_matches *m, int64_t min_weight, int collinear, orc_lcbs *out);
+/* DESIGN.md S11d repeat penalty: modes, base multiplicities of one genome (every window valid), penalized match scores
+   (mult[g]: the multiplicities of genome g; mode OFF is orc_match_sp_scores) */
+#define ORC_REPEAT_OFF 0
+#define ORC_REPEAT_NEGATIVE 1
+#define ORC_REPEAT_ZERO 2
+int orc_seed_multiplicity(const uint8_t *codes, int64_t len, uint64_t pattern, uint8_t *mult);
+void orc_match_sp_scores_repeat(int nseq, const uint8_t *const *codes, const uint8_t *const *mult, const orc_matches *m,
+                                const orc_scoring *sc, int mode, int64_t *out);
 void orc_free_lcbs(orc_lcbs *l);
 
 /* ---- gapped DP -------------------------------------------------------------------------------- */
@@ -160,6 +168,9 @@ int64_t orc_profile_dp(int64_t m, const uint8_t *cnt, int k_rows, int64_t n, con
 /* ---- whole path -------------------------------------------------------------------------------- */
 int orc_align(int nseq, const uint8_t *const *codes, const int64_t *lens, const orc_params *p,
               orc_matches *mums_out, orc_lcbs *lcbs_out, orc_alignment *aln_out);
+/* orc_align with the repeat penalty (ORC_REPEAT_*) in force where S11 scoring is; orc_align is mode OFF */
+int orc_align_ex(int nseq, const uint8_t *const *codes, const int64_t *lens, const orc_params *p, int repeat_penalty,
+                 orc_matches *mums_out, orc_lcbs *lcbs_out, orc_alignment *aln_out);
 void orc_free_alignment(orc_alignment *a);
 /* guide tree + guide-tree recursive anchoring (ProgressiveAligner::align stand-in);
    dist: [nseq*nseq] ppm distances (may be NULL), tree_left/right: [2*nseq-1] */
@@ -177,6 +188,11 @@ int orc_progressive_align(int nseq, const uint8_t *const *codes, const int64_t *
 int orc_check_tree(int nseq, const int32_t *tree_left, const int32_t *tree_right);
 int orc_progressive_align_tree(int nseq, const uint8_t *const *codes, const int64_t *lens, const orc_params *p,
                                const int32_t *tree_left, const int32_t *tree_right, orc_alignment *aln);
+/* the two progressive entries with the repeat penalty; the plain ones are mode OFF */
+int orc_progressive_align_ex(int nseq, const uint8_t *const *codes, const int64_t *lens, const orc_params *p, int repeat_penalty,
+                             int32_t *tree_left, int32_t *tree_right, int64_t *dist, orc_alignment *aln);
+int orc_progressive_align_tree_ex(int nseq, const uint8_t *const *codes, const int64_t *lens, const orc_params *p, int repeat_penalty,
+                                  const int32_t *tree_left, const int32_t *tree_right, orc_alignment *aln);
 /* backbone segments and pairwise islands of an alignment (stands in for libMems detectBackbone with
    BigGapsDetector, progressiveMauve.cpp:242-243, and simpleFindIslands, mauveAligner.cpp:844) */
 typedef struct {

@@ -299,6 +299,29 @@ def match_sp_scores(seqs, length, start, scoring=None):
     return out[:len(keep[0])].copy()
 
 
+def seed_multiplicity(codes, pattern):
+    """base multiplicities of one genome for one pattern (every window valid) -> uint8[L]"""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    out = np.zeros(max(len(codes), 1), np.uint8)
+    if lib().orc_seed_multiplicity(_u8p(codes), C.c_int64(len(codes)), C.c_uint64(pattern), _u8p(out)):
+        raise RuntimeError("orc_seed_multiplicity failed")
+    return out[:len(codes)].copy()
+
+
+def match_sp_scores_repeat(seqs, mults, length, start, mode, scoring=None):
+    """repeat-penalized sum-of-pairs score of every (ungapped) match; mults[g]: multiplicities of genome g"""
+    sc = scoring or default_scoring()
+    seqs, arr, lens = _seq_args(seqs)
+    mults = [np.ascontiguousarray(m, dtype=np.uint8) for m in mults]
+    if [len(m) for m in mults] != [len(g) for g in seqs]:
+        raise ValueError("one multiplicity per base of every sequence")
+    marr = (C.POINTER(C.c_uint8) * len(mults))(*[_u8p(m) for m in mults])
+    m, keep = _np_to_matches(length, start)
+    out = np.zeros(max(len(keep[0]), 1), np.int64)
+    lib().orc_match_sp_scores_repeat(len(seqs), arr, marr, C.byref(m), C.byref(sc), int(mode), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    return out[:len(keep[0])].copy()
+
+
 def profile_dp(cnt, k_rows, seq, scoring=None, banded=False):
     sc = scoring or default_scoring()
     cnt = np.ascontiguousarray(cnt, dtype=np.uint8).reshape(-1, 4)
@@ -358,13 +381,14 @@ def breakpoint_counts(codes, pattern, min_len):
     return bp
 
 
-def align(codes, params=None, names=None, want_xmfa=False):
-    """Whole path.  -> dict(mums=(len,start), lcbs={...}, aln={...}, xmfa=str|None)"""
+def align(codes, params=None, names=None, want_xmfa=False, repeat_penalty=0):
+    """Whole path.  -> dict(mums=(len,start), lcbs={...}, aln={...}, xmfa=str|None)
+    repeat_penalty: 0 OFF, 1 NEGATIVE, 2 ZERO (in force with lcb_scoring=1)"""
     p = params or default_params()
     codes, arr, lens = _seq_args(codes)
     N = len(codes)
     mm, lc, al = Matches(), Lcbs(), Alignment()
-    rc = lib().orc_align(N, arr, lens, C.byref(p), C.byref(mm), C.byref(lc), C.byref(al))
+    rc = lib().orc_align_ex(N, arr, lens, C.byref(p), int(repeat_penalty), C.byref(mm), C.byref(lc), C.byref(al))
     if rc:
         raise RuntimeError("orc_align failed: %d" % rc)
     mums = _matches_to_np(mm)
@@ -426,9 +450,10 @@ def check_tree(nseq, left, right):
     return lib().orc_check_tree(nseq, left.ctypes.data_as(C.POINTER(C.c_int32)), right.ctypes.data_as(C.POINTER(C.c_int32))) == 0
 
 
-def progressive_align(codes, params=None, names=None, want_xmfa=False, tree=None):
+def progressive_align(codes, params=None, names=None, want_xmfa=False, tree=None, repeat_penalty=0):
     """Guide-tree recursive anchoring.  -> dict(aln={...}, tree=(left,right), dist, xmfa)
-    tree=(left, right): align along the caller's guide tree (--input-guide-tree) instead of the UPGMA one."""
+    tree=(left, right): align along the caller's guide tree (--input-guide-tree) instead of the UPGMA one.
+    repeat_penalty: 0 OFF, 1 NEGATIVE, 2 ZERO (in force with lcb_scoring=1)"""
     p = params or default_params()
     codes, arr, lens = _seq_args(codes)
     N = len(codes)
@@ -437,7 +462,7 @@ def progressive_align(codes, params=None, names=None, want_xmfa=False, tree=None
     if tree is None:
         left = np.zeros(2 * N - 1, np.int32)
         right = np.zeros(2 * N - 1, np.int32)
-        rc = lib().orc_progressive_align(N, arr, lens, C.byref(p), left.ctypes.data_as(C.POINTER(C.c_int32)),
+        rc = lib().orc_progressive_align_ex(N, arr, lens, C.byref(p), int(repeat_penalty), left.ctypes.data_as(C.POINTER(C.c_int32)),
                                          right.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_int64)),
                                          C.byref(al))
     else:
@@ -445,7 +470,7 @@ def progressive_align(codes, params=None, names=None, want_xmfa=False, tree=None
         right = np.ascontiguousarray(tree[1], np.int32)
         if len(left) != 2 * N - 1 or len(right) != 2 * N - 1:
             raise ValueError("guide tree must have 2*nseq-1 nodes")
-        rc = lib().orc_progressive_align_tree(N, arr, lens, C.byref(p), left.ctypes.data_as(C.POINTER(C.c_int32)),
+        rc = lib().orc_progressive_align_tree_ex(N, arr, lens, C.byref(p), int(repeat_penalty), left.ctypes.data_as(C.POINTER(C.c_int32)),
                                               right.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(al))
     if rc:
         raise RuntimeError("orc_progressive_align failed: %d" % rc)

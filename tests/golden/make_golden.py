@@ -88,9 +88,34 @@ def round2(name):
           "progressive blocks", pr["aln"]["n_iv"])
 
 
+def repeat(name):
+    """A progressive alignment with the repeat penalty (NEGATIVE) and the default progressive parameters (sum-of-pairs
+    scoring, weight and breakpoint scaling, refinement) of four genomes carrying a planted repeat family."""
+    from tests import repeat_ref as R
+    gs = R.repeat_genomes(4, 6000, 37, copies=10, elem=(150, 300), div=0.03)
+    names = ["g%d" % g for g in range(len(gs))]
+    p = O.default_progressive_params()
+    r = O.progressive_align(gs, p, names=names, want_xmfa=True, repeat_penalty=R.NEGATIVE)
+    off = O.progressive_align(gs, p)["aln"]
+    a = r["aln"]
+    assert not all(np.array_equal(off[k], a[k]) for k in ("left", "right", "cols")), "the penalty changes nothing here"
+    pat = O.get_seed(O.default_seed_weight(sum(len(g) for g in gs) // len(gs)), 0)
+    d = {"nseq": len(gs), "pattern": np.uint64(pat), "repeat_penalty": R.NEGATIVE, "tree_left": r["tree"][0], "tree_right": r["tree"][1],
+         "left": a["left"], "right": a["right"], "reverse": a["reverse"], "col_off": a["col_off"], "cols": a["cols"], "dp_score": a["dp_score"]}
+    for g, x in enumerate(gs):
+        d["genome%d" % g] = x
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
+    with open(os.path.join(OUT, name + ".xmfa"), "w") as f:
+        f.write(r["xmfa"])
+    print(name, "blocks", a["n_iv"], "(OFF: %d)" % off["n_iv"], "cols", len(a["cols"]))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "round2":          # only the later fixture (the others stay byte for byte)
         round2("g3x6k_round2")
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "repeat":          # only the repeat-penalty fixture
+        repeat("g4x6k_repeat")
         return
     rng = np.random.default_rng(20261003)
     anc = rng.integers(0, 4, 2000, dtype=np.uint8)
@@ -107,6 +132,7 @@ def main():
     # four leaves of a two-level tree with clade-specific inserts and inversions (config C4 in miniature)
     progressive("g4x3k_tree", synth.tree_genomes(4, 3000, 0.02, 77, inv_per_branch=1, insert_per_branch=1, insert_len=(60, 300)), 9)
     round2("g3x6k_round2")
+    repeat("g4x6k_repeat")
 
 
 if __name__ == "__main__":

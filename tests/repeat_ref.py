@@ -1,9 +1,11 @@
 """CPU reference of the repeat penalty: numpy over the oracle's per-window mers (oracle.pyoracle.mers) and its LCB
-chaining on given weights (orc_compute_lcbs_w).  Read-only use of the oracle; nothing here needs a GPU."""
+chaining on given weights (orc_compute_lcbs_w), and the genome sets with planted repeats that the CPU and GPU tests share.  Read-only
+use of the oracle; nothing here needs a GPU."""
 import ctypes as C
 
 import numpy as np
 
+from mauvealigner_amd import synth
 from oracle import pyoracle as O
 
 OFF, NEGATIVE, ZERO = 0, 1, 2
@@ -105,3 +107,53 @@ def compute_lcbs_w(length, start, weights, min_weight, collinear=False):
     d = O._lcbs_to_dict(out, len(keep[0]))
     O.lib().orc_free_lcbs(C.byref(out))
     return d
+
+
+def repeat_genomes(n, L, seed, copies=12, elem=(300, 1500), div=0.02):
+    """n genomes of about L bases from one ancestor that carries `copies` planted copies (half of them reverse-complemented,
+    each point-mutated by 3 %) of one repeat element, then mutated per genome at `div`"""
+    rng = np.random.default_rng(seed)
+    anc = rng.integers(0, 4, L).astype(np.uint8)
+    e = rng.integers(0, 4, int(rng.integers(*elem))).astype(np.uint8)
+    for k, p in enumerate(np.sort(rng.choice(L - len(e), copies, replace=False)).tolist()):
+        c = e.copy()
+        hit = rng.random(len(c)) < 0.03
+        c[hit] = (c[hit] + rng.integers(1, 4, int(hit.sum()))) & 3
+        anc[p:p + len(c)] = synth.revcomp(c) if k % 2 else c
+    return [synth.mutate(anc, div, np.random.default_rng(seed * 100 + g)) for g in range(n)]
+
+
+def _blocks_and_repeats(seed, tag=0):
+    """two genomes: unique blocks U0..U7 in the same order, a copy of one 300-base element E between every two; the caller's match
+    list pairs U_k with U_k and the copies of E out of order.  tag > 0: copy j is E between two unique tags of `tag` bases, and
+    genome 1 holds it in slot perm[j], so the genomes' own seed search finds the copies paired out of order (the tags seed them)
+    while the tags break the diagonal of the blocks"""
+    rng = np.random.default_rng(seed)
+    U = [rng.integers(0, 4, 800).astype(np.uint8) for _ in range(8)]
+    E = rng.integers(0, 4, 300).astype(np.uint8)
+    perm = [3, 0, 5, 1, 6, 2, 4]
+    if tag:
+        cp = [np.concatenate([rng.integers(0, 4, tag), E, rng.integers(0, 4, tag)]).astype(np.uint8) for _ in range(7)]
+    else:
+        cp = [E] * 7
+    le = len(cp[0])
+    g0, pos_u, pos_e = [], [], []
+    at = 0
+    for k in range(8):
+        pos_u.append(at); g0.append(U[k]); at += 800
+        if k < 7:
+            pos_e.append(at); g0.append(cp[k]); at += le
+    g0 = np.concatenate(g0)
+    g1 = g0.copy()
+    for p in pos_u:
+        hit = np.flatnonzero(rng.random(800) < 0.01) + p
+        g1[hit] = (g1[hit] + 1) & 3
+    for j in range(7):
+        g1[pos_e[perm[j]]:pos_e[perm[j]] + le] = cp[j]
+    ln, st = [], []
+    for p in pos_u:
+        ln.append(800); st.append([p + 1, p + 1])
+    for j, p in enumerate(pos_e):
+        ln.append(le); st.append([p + 1, pos_e[perm[j]] + 1])
+    order = np.argsort([s[0] for s in st], kind="stable")
+    return [g0, g1], np.array(ln, np.int64)[order], np.array(st, np.int64)[order]

@@ -1,18 +1,25 @@
 """One process of tests/test_gpu_repeat_penalty.py::test_device_chain_equals_host_chain: a progressive alignment with the repeat
-penalty on of a C4-shaped set with planted repeats; the parent runs it once as is and once with MAUVE_HOST_CHAIN=1.
+penalty on of a C4-shaped set with planted repeats; the parent runs it on each chain route (as is,
+MAUVE_CANON_DEVICE_MIN=1, MAUVE_HOST_CHAIN=1) and compares every run with the oracle.
 usage: python -m tests.repeat_worker <out.npz>"""
 import sys
 
 import numpy as np
 
 
+def worker_genomes(scale=0.02):
+    """C4 at `scale`, every genome with the same planted repeat family appended (tests.repeat_ref.repeat_genomes)"""
+    from mauvealigner_amd import synth
+    from tests.repeat_ref import repeat_genomes
+    gs = synth.make_config("C4", scale=scale)
+    rep = repeat_genomes(len(gs), 20000, 9, copies=16)
+    return [np.concatenate([g, r]) for g, r in zip(gs, rep)]
+
+
 def main():
     out = sys.argv[1]
-    from mauvealigner_amd import _lib, synth
-    from tests.test_gpu_repeat_penalty import repeat_genomes
-    gs = synth.make_config("C4", scale=0.02)
-    rep = repeat_genomes(len(gs), 20000, 9, copies=16)
-    gs = [np.concatenate([g, r]) for g, r in zip(gs, rep)]      # every genome carries the same planted repeat family
+    from mauvealigner_amd import _lib
+    gs = worker_genomes()
     ctx = _lib.Context(0)
     res = {}
     try:
@@ -25,6 +32,7 @@ def main():
             r = ctx.progressive_align(p)
             for k in ("cols", "col_off", "dp_score", "left", "right", "reverse"):
                 res["m%d_%s" % (mode, k)] = r[k]
+            res["m%d_n_gap_dp" % mode] = np.array(r["n_gap_dp"])
         ctx.set_repeat_penalty(0)
     finally:
         ctx.close()

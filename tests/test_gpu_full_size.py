@@ -162,3 +162,50 @@ def test_banded_long_intervals(ctx):
     diag = int(mat[big[0][:k], big[1][:k]].sum()) + (sc.gap_open + (abs(m - n) - 1) * sc.gap_extend if m != n else 0)
     assert int(score[0]) >= diag
     print("banded 60k: %.3f s, 150k: %.3f s" % (t1 - t0, t3 - t2))
+
+
+def test_c4_full_size_repeat_penalty_equals_oracle(ctx):
+    """C4 at full size with a planted repeat family appended to every genome (tests/repeat_worker.py's construction), progressive
+    at the call site's defaults with the repeat penalty NEGATIVE: bit-exact against the oracle, and not the OFF result"""
+    from mauvealigner_amd import _lib
+    from tests.repeat_worker import worker_genomes
+    gs = worker_genomes(scale=1.0)
+    ctx.set_genomes(gs)
+    p = _lib.default_progressive_params()
+    try:
+        ctx.set_repeat_penalty(_lib.REPEAT_PENALTY_NEGATIVE)
+        r = ctx.progressive_align(p)
+    finally:
+        ctx.set_repeat_penalty(_lib.REPEAT_PENALTY_OFF)
+    off = ctx.progressive_align(p)
+    e = O.progressive_align(gs, O.default_progressive_params(), repeat_penalty=1)["aln"]
+    for k in ("left", "right", "reverse", "col_off", "cols", "dp_score"):
+        assert np.array_equal(r[k], e[k]), k
+    assert r["n_gap_dp"] == e["n_gap_dp"]
+    assert not all(np.array_equal(r[k], off[k]) for k in ("left", "right", "cols"))
+    check_partition(gs, r)
+
+
+def test_c5_shaped_pair_repeat_penalty_equals_oracle(ctx):
+    """a C5-shaped pair (2 x 3 Mbp, w = 19: 64-bit keys) with a planted repeat family through align with SP scoring and NEGATIVE:
+    bit-exact against the oracle, anchors and LCB weights included, and not the OFF result"""
+    from mauvealigner_amd import _lib
+    from tests.repeat_ref import repeat_genomes
+    gs = repeat_genomes(2, 3_000_000, 19, copies=60, elem=(1000, 3000), div=0.03)
+    pat = _lib.get_seed(19, 0)
+    ctx.set_genomes(gs)
+    assert max(int(ctx.seed_multiplicity(g, pat).max()) for g in range(2)) > 1
+    kw = dict(lcb_scoring=1, seed_weight=19)
+    try:
+        ctx.set_repeat_penalty(_lib.REPEAT_PENALTY_NEGATIVE)
+        r = ctx.align(_lib.default_params(**kw))
+    finally:
+        ctx.set_repeat_penalty(_lib.REPEAT_PENALTY_OFF)
+    off = ctx.align(_lib.default_params(**kw))
+    e = O.align(gs, O.default_params(**kw), repeat_penalty=1)
+    for k in KEYS + ("reverse", "anchor_lcb"):
+        assert np.array_equal(r[k], e["aln"][k]), k
+    assert np.array_equal(r["lcb_weight"], e["lcbs"]["weight"])
+    assert r["n_gap_dp"] == e["aln"]["n_gap_dp"]
+    assert not np.array_equal(r["lcb_weight"], off["lcb_weight"])
+    check_partition(gs, r)
