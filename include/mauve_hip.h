@@ -30,6 +30,13 @@ extern "C" {
 #define MAUVE_ERR_STATE (-5)      /* call order violated (e.g. no genomes set) */
 
 #define MAUVE_MAX_SEQ 32
+/* genome set limits (MAUVE_ERR_LIMIT, checked by mauve_set_genomes*): every genome holds fewer than 2^31 bases (match and anchor starts
+   stay int32 on the device), and the genomes together fewer than 2^32 - 2^20 (every window count, rounded up to whole tiles, stays
+   32-bit).  A seed pass over 2^31 windows or more carries 64-bit window indices.  On a set of 2^31 bases or more in
+   total only the seed-pass entry points run (mauve_seed_mums, mauve_extend_hits, mauve_sorted_mer_list, mauve_seed_match_enumerate,
+   mauve_seed_multiplicity); the alignment entry points return MAUVE_ERR_LIMIT (not yet verified at that size). */
+#define MAUVE_MAX_GENOME_LEN (1LL << 31)
+#define MAUVE_MAX_TOTAL_LEN ((1LL << 32) - (1LL << 20))
 #define MAUVE_MAX_SEED_SPAN 49
 #define MAUVE_CODING_SEED 3                /* mauveAligner.cpp:266-279 */
 #define MAUVE_SOLID_SEED 0x7fffffff        /* repeatoire.cpp:1847 (SOLID_SEED == INT_MAX) */
@@ -267,7 +274,7 @@ int mauve_align_fetch(mauve_ctx *ctx,
                       int64_t *col_off, uint32_t *cols, int64_t *dp_score);     /* [n_iv+1],[n_cols],[n_iv] */
 /* The same result in the narrowest types that hold it (no reference counterpart: libMems hands out objects; this is what a caller that
    wants the arrays moves).  cols: col_bytes bytes per column (1: up to 8 genomes, 2: up to 16, 4: any; MAUVE_ERR_ARG when a column does not
-   fit); match and anchor tables as int32 (a context holds fewer than 2^31 bases, so every start and length fits); the small per-LCB and
+   fit); match and anchor tables as int32 (every genome holds fewer than 2^31 bases, MAUVE_MAX_GENOME_LEN, so every start and length fits); the small per-LCB and
    per-interval tables as in mauve_align_fetch.  From page-locked buffers (mauve_host_alloc) the bulk arrays are narrowed on the device and
    copied once; any pointer may be NULL.  mauve_align_fetch is unchanged. */
 int mauve_align_fetch_compact(mauve_ctx *ctx, int col_bytes,

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libmauve_hip.so")
 
 MODE_MEM, MODE_UNIQUE, MODE_PAIRWISE = 0, 1, 2
 CODING_SEED, SOLID_SEED = 3, 0x7FFFFFFF
+MAX_GENOME_LEN, MAX_TOTAL_LEN = 1 << 31, (1 << 32) - (1 << 20)             # mauve_set_genomes* limits (MAUVE_MAX_GENOME_LEN, MAUVE_MAX_TOTAL_LEN)
 REPEAT_PENALTY_OFF, REPEAT_PENALTY_NEGATIVE, REPEAT_PENALTY_ZERO = 0, 1, 2    # DESIGN.md S11d (progressiveMauve --repeat-penalty)
 K_EXTRACT, K_SORT_HIST, K_SORT_SCAN, K_SORT_SCATTER, K_JOIN, K_EXTEND, K_DP, K_RUNS = range(8)
 KERNEL_NAMES = ["seed_extract", "rs_hist", "rs_rowscan", "rs_scatter", "mum_join", "mum_extend", "dp_step", "mum_runs", "canon_sort", "misc_sort"]
@@ -343,12 +344,32 @@ class Context:
         self.nseq = n
         self.lens = [len(c) for c in codes_list]
 
-    def set_genomes_packed(self, packed, lens):
+    def set_genomes_packed(self, packed, lens, contig_starts=None, invalid_bits=None):
         """genomes already in the boundary's 2-bit packing (pack_codes): the upload alone (arrays from pinned_empty go up
-        in one DMA each, without a staging copy)"""
+        in one DMA each, without a staging copy).  contig_starts: as in set_genomes; invalid_bits: per genome the ambiguity
+        bitmap already packed (uint64, bit i of word i // 64 = base i is ambiguous, at least len // 64 + 1 words: the layout
+        of mauve_ambiguity_bitmap) or None -- no per-base array, so genomes of a gigabase cost their 2-bit and 1-bit images only"""
         n = len(packed)
         arr = (C.POINTER(C.c_uint64) * n)(*[_p(w, C.c_uint64) for w in packed])
-        self._chk(self.L.mauve_set_genomes(self.h, n, arr, (C.c_int64 * n)(*[int(x) for x in lens])), "mauve_set_genomes")
+        ln = (C.c_int64 * n)(*[int(x) for x in lens])
+        if contig_starts is None and invalid_bits is None:
+            self._chk(self.L.mauve_set_genomes(self.h, n, arr, ln), "mauve_set_genomes")
+        else:
+            if (contig_starts is not None and len(contig_starts) != n) or (invalid_bits is not None and len(invalid_bits) != n):
+                raise ValueError("set_genomes_packed: contig_starts / invalid_bits need one entry per genome (%d)" % n)
+            cs = contig_starts or [[0]] * n
+            ncont = (C.c_int64 * n)(*[len(x) for x in cs])
+            flat = np.array([int(v) for x in cs for v in x] + [0], dtype=np.int64)
+            bits = []
+            for g in range(n):
+                w = None if invalid_bits is None else invalid_bits[g]
+                if w is not None:
+                    w = np.ascontiguousarray(w, dtype=np.uint64)
+                    if len(w) < int(lens[g]) // 64 + 1:
+                        raise ValueError("invalid_bits[%d]: %d words, the genome needs %d" % (g, len(w), int(lens[g]) // 64 + 1))
+                bits.append(w)
+            inv = (C.POINTER(C.c_uint64) * n)(*[_p(w, C.c_uint64) if w is not None else C.POINTER(C.c_uint64)() for w in bits])
+            self._chk(self.L.mauve_set_genomes_contigs(self.h, n, arr, ln, ncont, _p(flat, C.c_int64), inv), "mauve_set_genomes_contigs")
         self.nseq = n
         self.lens = [int(x) for x in lens]
 

@@ -156,6 +156,16 @@ void shard_lpt(const std::vector<int64_t> &cost, int world, std::vector<int> &ow
     }
 }
 
+int refuse_past_2g(mauve_ctx *c, const char *what)
+{
+    int64_t tot = 0;
+    for (int64_t l : c->lens) tot += l;
+    if (tot < (1LL << 31)) return MAUVE_OK;
+    c->err = std::string(what) + ": the genomes hold 2^31 bases or more together; at that size only the seed-pass entry points are verified "
+             "(seed_mums, extend_hits, sorted_mer_list, seed_match_enumerate, seed_multiplicity), the alignment path is not (DESIGN.md S9)";
+    return MAUVE_ERR_LIMIT;
+}
+
 extern "C" {
 
 // The second stream carries the one-wave launch of the DP (dp_step2: thousands of small workgroups) while the workgroup launches -- the tail of
@@ -289,6 +299,15 @@ int mauve_set_genomes(mauve_ctx *c, int nseq, const uint64_t *const *packed, con
 {
     if (!c) return MAUVE_ERR_ARG;
     if (nseq < 1 || nseq > MAUVE_MAX_SEQ || !packed || !lens) { c->err = "set_genomes: 1..32 sequences required"; return MAUVE_ERR_ARG; }
+    // the limits before anything changes: a refused set leaves the context as it was
+    {
+        int64_t tot = 0;
+        for (int g = 0; g < nseq; g++) {
+            if (lens[g] >= MAUVE_MAX_GENOME_LEN) { c->err = "set_genomes: genome " + std::to_string(g) + " holds 2^31 bases or more (per-genome limit)"; return MAUVE_ERR_LIMIT; }
+            if (lens[g] > 0) tot += lens[g];
+        }
+        if (tot >= MAUVE_MAX_TOTAL_LEN) { c->err = "set_genomes: the genomes together hold 2^32 - 2^20 bases or more (total limit)"; return MAUVE_ERR_LIMIT; }
+    }
     HIPCHK(c, hipSetDevice(c->device));
     // A result still in the context was made from the genomes that are being replaced: it ends here (mauve_hip.h: results are held
     // until the next call).  What of it is still on the device is not brought over -- in a loop of set_genomes / align / fetch that
@@ -298,14 +317,11 @@ int mauve_set_genomes(mauve_ctx *c, int nseq, const uint64_t *const *packed, con
     c->genome_gen++;                      // the cached repeat multiplicities belong to the genomes before
     size_t total_words = 0;
     std::vector<uint64_t> off(nseq);
-    int64_t total_len = 0;
     for (int g = 0; g < nseq; g++) {
         if (lens[g] < 0 || (lens[g] > 0 && !packed[g])) { c->err = "set_genomes: bad length or null pointer"; return MAUVE_ERR_ARG; }
         off[g] = total_words;
         total_words += mauve_packed_words(lens[g]);
-        total_len += lens[g];
     }
-    if (total_len >= (1LL << 31)) { c->err = "set_genomes: total length must stay below 2^31 bases"; return MAUVE_ERR_LIMIT; }
     HIPCHK(c, c->genomes.ensure((total_words + 4) * sizeof(uint64_t)));
     // Genomes in page-locked caller memory (mauve_host_alloc) go up straight from there: one DMA per genome, plus the few
     // words of its tail (the last data word with the bits past the last base cleared, the zero padding) from a small staging
@@ -444,6 +460,8 @@ int mauve_extend_hits(mauve_ctx *c, uint64_t pattern, int64_t n_hits, const uint
     std::vector<uint32_t> off((size_t)N + 1, 0);                  // first global window index of every genome
     std::vector<int64_t> nwin((size_t)N, 0);
     for (int g = 0; g < N; g++) { nwin[(size_t)g] = std::max<int64_t>(0, c->lens[(size_t)g] - span + 1); off[(size_t)g + 1] = off[(size_t)g] + (uint32_t)nwin[(size_t)g]; }
+    // a wide seed pass takes windows local to their genome: its hit table holds them that way
+    if (seedpass_wide((int64_t)off[(size_t)N])) std::fill(off.begin(), off.end(), 0u);
     std::vector<uint32_t> rec((size_t)n_hits * (N + 1), 0);
     for (int64_t h = 0; h < n_hits; h++) {
         const uint32_t m = mask[h];

@@ -1019,6 +1019,7 @@ int mauve_apply_homology_alignment(mauve_ctx *c, int nseq, int64_t n_iv, const i
                                    const uint32_t *cols, const mauve_hmm_params *h, int64_t *col_off_out, uint32_t *cols_out, int64_t *n_moved)
 {
     if (!c || !h || nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !col_off_out || (n_iv && (!left || !right || !reverse || !col_off || !cols || !cols_out))) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "apply_homology_alignment"); if (rg) return rg; }
     if (n_moved) *n_moved = 0;
     col_off_out[0] = 0;
     if (n_iv == 0) return MAUVE_OK;

@@ -382,6 +382,10 @@ int shard_allgather(mauve_ctx *c, const void *send, size_t bytes, std::vector<st
 void shard_lpt(const std::vector<int64_t> &cost, int world, std::vector<int> &owner);
 bool make_seed_shape(uint64_t pattern, SeedShape *out);
 GenomeSet main_genome_set(mauve_ctx *ctx);
+bool seedpass_wide(int64_t total_windows);
+// genome sets of 2^31 bases or more: the seed-pass entry points take them; the alignment path behind them refuses them
+// (MAUVE_ERR_LIMIT, `what` named) until it is verified at that size
+int refuse_past_2g(mauve_ctx *c, const char *what);      // 64-bit window indices for a pass of this many windows
 int seedpass_run(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, int mode, uint64_t mask, int extend,
                  const uint32_t *seg_dev, uint32_t nseg, int64_t *n_matches);
 int seedpass_enumerate(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t pattern, EnumRequest &q);

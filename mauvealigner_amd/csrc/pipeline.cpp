@@ -871,6 +871,7 @@ extern "C" {
 int mauve_align(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
 {
     if (!c || !p || !sizes) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "align"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     static const bool host_front = getenv("MAUVE_HOST_DP_FRONT") != nullptr;      // A/B switch
@@ -904,6 +905,7 @@ int mauve_align(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
 int mauve_align_lcbs(mauve_ctx *c, const mauve_params *p, int64_t n, const int64_t *length, const int64_t *start, const int64_t *lcb, mauve_align_sizes *sizes)
 {
     if (!c || !p || !sizes) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "align_lcbs"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "align_lcbs: at least two genomes required"; return MAUVE_ERR_STATE; }
     if (n < 0 || (n && (!length || !start || !lcb))) { c->err = "align_lcbs: bad anchor list"; return MAUVE_ERR_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -961,6 +963,7 @@ static int given_matches(mauve_ctx *c, int64_t n, const int64_t *length, const i
 int mauve_match_sp_scores(mauve_ctx *c, int64_t n, const int64_t *length, const int64_t *start, const mauve_scoring *sc, int64_t *scores)
 {
     if (!c || !sc || n < 0 || (n && (!length || !start || !scores))) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "match_sp_scores"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "match_sp_scores: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->nseq;
@@ -977,6 +980,7 @@ int mauve_match_sp_scores_repeat(mauve_ctx *c, uint64_t pattern, int mode, int64
                                  const mauve_scoring *sc, int64_t *scores)
 {
     if (!c || !sc || n < 0 || (n && (!length || !start || !scores))) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "match_sp_scores_repeat"); if (rg) return rg; }
     if (mode != MAUVE_REPEAT_PENALTY_OFF && mode != MAUVE_REPEAT_PENALTY_NEGATIVE && mode != MAUVE_REPEAT_PENALTY_ZERO) { c->err = "match_sp_scores_repeat: unknown mode"; return MAUVE_ERR_ARG; }
     SeedShape sh;
     if (!make_seed_shape(pattern, &sh)) { c->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
@@ -994,6 +998,7 @@ int mauve_match_sp_scores_repeat(mauve_ctx *c, uint64_t pattern, int mode, int64
 int mauve_align_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const int64_t *length, const int64_t *start, mauve_align_sizes *sizes)
 {
     if (!c || !p || !sizes) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "align_matches"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     MatchVec mv;
@@ -1015,6 +1020,7 @@ int mauve_align_begin_matches(mauve_ctx *c, const mauve_params *p, int64_t n, co
                               int64_t *n_codes)
 {
     if (!c || !p || !n_dp) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "align_begin_matches"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     MatchVec mv;
@@ -1045,6 +1051,7 @@ int mauve_align_dp_anchors(mauve_ctx *c, int64_t *left, int64_t *right)
 int mauve_align_begin(mauve_ctx *c, const mauve_params *p, int64_t *n_dp, int64_t *n_codes)
 {
     if (!c || !p || !n_dp) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "align_begin"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     int rc = align_begin(c, p);

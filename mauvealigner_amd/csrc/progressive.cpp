@@ -471,6 +471,8 @@ static int guide_tree_core(mauve_ctx *c, uint64_t pattern, int64_t *dist, int32_
 // guide tree only (distance matrix in ppm, UPGMA merge order); dist may be NULL
 int mauve_guide_tree(mauve_ctx *c, uint64_t pattern, int64_t *dist, int32_t *left, int32_t *right)
 {
+    if (!c) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "guide_tree"); if (rg) return rg; }
     return guide_tree_core(c, pattern, dist, left, right, -1, nullptr);
 }
 
@@ -478,6 +480,7 @@ int mauve_guide_tree(mauve_ctx *c, uint64_t pattern, int64_t *dist, int32_t *lef
 int mauve_breakpoint_counts(mauve_ctx *c, uint64_t pattern, int64_t min_len, int64_t *bp)
 {
     if (!c || !bp) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "breakpoint_counts"); if (rg) return rg; }
     if (min_len < 0) { c->err = "breakpoint_counts: min_len must not be negative"; return MAUVE_ERR_ARG; }
     if (c->nseq < 2) { c->err = "breakpoint_counts: at least two genomes required"; return MAUVE_ERR_STATE; }
     std::vector<int32_t> l((size_t)(2 * c->nseq - 1)), r((size_t)(2 * c->nseq - 1));
@@ -548,6 +551,8 @@ static int progressive_core(mauve_ctx *c, const mauve_params *p, mauve_align_siz
 int mauve_progressive_align(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes, int32_t *tree_left,
                             int32_t *tree_right, int64_t *dist)
 {
+    if (!c) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "progressive_align"); if (rg) return rg; }
     return progressive_core(c, p, sizes, nullptr, nullptr, tree_left, tree_right, dist);
 }
 
@@ -557,6 +562,7 @@ int mauve_progressive_align_tree(mauve_ctx *c, const mauve_params *p, mauve_alig
                                  const int32_t *tree_right)
 {
     if (!c || !tree_left || !tree_right) return MAUVE_ERR_ARG;
+    { const int rg = refuse_past_2g(c, "progressive_align_tree"); if (rg) return rg; }
     const int N = c->nseq, M = 2 * N - 1;
     if (N < 2) { c->err = "progressive_align: at least two genomes required"; return MAUVE_ERR_STATE; }
     std::vector<char> used((size_t)M, 0);

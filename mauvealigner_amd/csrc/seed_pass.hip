@@ -128,6 +128,24 @@ __device__ __forceinline__ int genome_of(uint32_t gpos, const GenomeTab &t)
     return g;
 }
 
+// A sort value: global window index | strand flag.  The narrow form (uint32_t) keeps the flag in bit 31, so a pass over it holds fewer
+// than 2^31 windows; the wide form (uint64_t, a pass of 2^31 windows or more) keeps it in bit 63 -- the index itself is below
+// 2^32 either way, so every decoded index, and genome_of, stays 32-bit.
+__device__ __forceinline__ uint32_t win_idx(uint32_t v) { return v & 0x7fffffffu; }
+__device__ __forceinline__ uint32_t win_idx(uint64_t v) { return (uint32_t)v; }
+__device__ __forceinline__ uint32_t win_strand(uint32_t v) { return v >> 31; }
+__device__ __forceinline__ uint32_t win_strand(uint64_t v) { return (uint32_t)(v >> 63); }
+template <typename ValT> __device__ __forceinline__ ValT win_make(uint32_t gp, uint32_t s)
+{
+    if constexpr (sizeof(ValT) == 4) return gp | (s << 31);
+    else return (uint64_t)gp | ((uint64_t)s << 63);
+}
+// The hit table's word for a component in genome g (tpos, see mum_join): narrow, the value itself (global index | strand << 31); wide, the
+// window index LOCAL to genome g | strand << 31 -- the slot names the genome and a genome holds fewer than 2^31 bases, so the table keeps
+// four bytes per entry.  Only differences of two indices of the same genome (mum_runs) or the local index (mum_extend) are read back.
+__device__ __forceinline__ uint32_t hit_word(uint32_t v, uint32_t) { return v; }
+__device__ __forceinline__ uint32_t hit_word(uint64_t v, uint32_t goff) { return (win_idx(v) - goff) | (win_strand(v) << 31); }
+
 // ------------------------------------------------------------------------------------------------
 // seed_extract: one thread per window.  Reads 0.25 B/position (L1-shared), writes key + val.
 // val = global window index | strand << 31.
@@ -143,10 +161,10 @@ __device__ __forceinline__ uint32_t seg_of(const uint32_t *__restrict__ segs, ui
     return lo;
 }
 
-template <typename KeyT, bool SEG>
+template <typename KeyT, bool SEG, typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) seed_extract(const uint64_t *__restrict__ packed, GenomeTab tab,
                                                     SeedShape sh, int g, KeyT *__restrict__ keys,
-                                                    uint32_t *__restrict__ vals, uint32_t out_base,
+                                                    ValT *__restrict__ vals, uint32_t out_base,
                                                     const uint32_t *__restrict__ seg, uint32_t nseg)
 {
     uint32_t n = tab.nwin[g];
@@ -163,7 +181,7 @@ __global__ void __launch_bounds__(256) seed_extract(const uint64_t *__restrict__
             key = (p + sh.span <= sg[k + 1]) ? (((uint64_t)k << (2 * sh.weight)) | key) : ~0ULL;
         }
         keys[out_base + p] = (KeyT)key;
-        vals[out_base + p] = (tab.gpos_off[g] + p) | (s << 31);
+        vals[out_base + p] = win_make<ValT>(tab.gpos_off[g] + p, s);
     }
 }
 
@@ -183,9 +201,9 @@ __device__ __forceinline__ uint32_t kprime_of32(uint64_t lo, const SeedShape &sh
     return k;
 }
 
-template <typename KeyT, bool SEG, bool NARROW>
+template <typename KeyT, bool SEG, bool NARROW, typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh,
-                                                        KeyT *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t P,
+                                                        KeyT *__restrict__ keys, ValT *__restrict__ vals, uint32_t P,
                                                         const uint32_t *__restrict__ seg, uint32_t nseg,
                                                         uint32_t *__restrict__ hist, uint32_t nblk,
                                                         const uint64_t *__restrict__ vmask, int hist_shift,
@@ -267,12 +285,17 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 reinterpret_cast<ulonglong2 *>(keys + gp0)[0] = make_ulonglong2(key[0], key[1]);
                 reinterpret_cast<ulonglong2 *>(keys + gp0)[1] = make_ulonglong2(key[2], key[3]);
             }
-            *reinterpret_cast<uint4 *>(vals + gp0) = make_uint4(gp0 | (sf[0] << 31), (gp0 + 1) | (sf[1] << 31), (gp0 + 2) | (sf[2] << 31), (gp0 + 3) | (sf[3] << 31));
+            if constexpr (sizeof(ValT) == 4)
+                *reinterpret_cast<uint4 *>(vals + gp0) = make_uint4(gp0 | (sf[0] << 31), (gp0 + 1) | (sf[1] << 31), (gp0 + 2) | (sf[2] << 31), (gp0 + 3) | (sf[3] << 31));
+            else {
+                reinterpret_cast<ulonglong2 *>(vals + gp0)[0] = make_ulonglong2(win_make<ValT>(gp0, sf[0]), win_make<ValT>(gp0 + 1, sf[1]));
+                reinterpret_cast<ulonglong2 *>(vals + gp0)[1] = make_ulonglong2(win_make<ValT>(gp0 + 2, sf[2]), win_make<ValT>(gp0 + 3, sf[3]));
+            }
 #pragma unroll
             for (int j = 0; j < 4; j++) atomicAdd(&h[(uint32_t)((KeyT)key[j] >> hist_shift) & 255u], 1u);
         } else {
             for (int j = 0; j < 4 && gp0 + j < P; j++) {
-                keys[gp0 + j] = (KeyT)key[j]; vals[gp0 + j] = (gp0 + j) | (sf[j] << 31);
+                keys[gp0 + j] = (KeyT)key[j]; vals[gp0 + j] = win_make<ValT>(gp0 + j, sf[j]);
                 atomicAdd(&h[(uint32_t)((KeyT)key[j] >> hist_shift) & 255u], 1u);
             }
         }
@@ -326,9 +349,9 @@ __global__ void __launch_bounds__(256) tile_scan(uint32_t *__restrict__ tile_cnt
     if (threadIdx.x == 0) *total_out = total;
 }
 
-template <typename KeyT, bool NARROW>
+template <typename KeyT, bool NARROW, typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) seed_extract_compact(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh,
-                                                            KeyT *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t P,
+                                                            KeyT *__restrict__ keys, ValT *__restrict__ vals, uint32_t P,
                                                             const uint64_t *__restrict__ vmask, const uint32_t *__restrict__ tile_off,
                                                             const uint64_t *__restrict__ cmask)
 {
@@ -353,7 +376,7 @@ __global__ void __launch_bounds__(256) seed_extract_compact(const uint64_t *__re
             const uint64_t f = digit_reverse(kp, sh.weight), r = (~kp) & sh.keymask;
             s = r < f; key = s ? r : f;
         }
-        keys[o] = (KeyT)key; vals[o] = gp | (s << 31);
+        keys[o] = (KeyT)key; vals[o] = win_make<ValT>(gp, s);
         o++;
     }
 }
@@ -442,16 +465,18 @@ __global__ void __launch_bounds__(256) rs_rowscan(uint32_t *__restrict__ hist, u
 // RAW: `hist` holds the raw per-tile digit counts (no rs_rowscan ran): every workgroup sums its digit's row for itself --
 // the sorts of the chain / DP front / canonical order have at most a few dozen tiles, where the row scan is one more
 // launch of pure latency.
-template <typename KeyT, bool RAW = false>
+// LDS per workgroup (RS_TILE = 4096): keys + values + 7 KiB of counters -- 39 KiB for 4 + 4 bytes, 55 KiB for 8 + 4 or 4 + 8, 71 KiB for 8 + 8
+// (the wide pass with 64-bit keys): 4, 2, 2 workgroups per compute unit of 160 KiB.
+template <typename KeyT, bool RAW = false, typename ValT = uint32_t>
 __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict__ keys_in,
-                                                         const uint32_t *__restrict__ vals_in,
+                                                         const ValT *__restrict__ vals_in,
                                                          KeyT *__restrict__ keys_out,
-                                                         uint32_t *__restrict__ vals_out, uint32_t n, int shift,
+                                                         ValT *__restrict__ vals_out, uint32_t n, int shift,
                                                          const uint32_t *__restrict__ hist,
                                                          const uint32_t *__restrict__ totals, uint32_t nblk)
 {
     __shared__ KeyT s_keys[RS_TILE];
-    __shared__ uint32_t s_vals[RS_TILE];
+    __shared__ ValT s_vals[RS_TILE];
     __shared__ uint32_t wcount[RS_WAVES][256];
     __shared__ uint32_t gbase[256];       // global output index of this tile's first key of digit d
     __shared__ uint32_t tstart[256];      // tile-local start of digit d
@@ -476,9 +501,9 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict_
     }
     __syncthreads();
     if (tile_n == RS_TILE)
-        rs_scatter_tile<KeyT, RS_ITEMS, true>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
+        rs_scatter_tile<KeyT, RS_ITEMS, true, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
     else
-        rs_scatter_tile<KeyT, RS_ITEMS, false>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
+        rs_scatter_tile<KeyT, RS_ITEMS, false, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -486,20 +511,18 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict_
 // the hit by the finder's rule and scatters the hit into the dense HIT TABLE, indexed by the global
 // window index of the hit's anchor (lowest genome of its component set):
 //   tmask[p]    = component set (0 = no hit anchored at p)
-//   tpos[p*N+g] = component g's window: global index | strand << 31   (one record of N words per anchor:
+//   tpos[p*N+g] = component g's window: global index | strand << 31, local to genome g in a wide pass (hit_word)   (one record of N words per anchor:
 //                 a hit is written, and later read, as one contiguous record instead of N scattered words)
 //   MODE_MEM    : MemHash -- a genome with more than one copy kills the seed
 //   MODE_UNIQUE : UniqueMatchFinder.cpp:44-58 -- genomes with more than one copy are dropped, >= 2 stay
 // A position carries at most one mer, so at most one hit is anchored at it: no atomics, no compaction.
 // ------------------------------------------------------------------------------------------------
-template <typename KeyT, bool SEG>
-__global__ void __launch_bounds__(256) mum_join(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                                uint32_t n, GenomeTab tab, int mode, uint32_t want_mask,
-                                                uint32_t consider, uint32_t *__restrict__ tmask,
-                                                uint32_t *__restrict__ tpos, uint32_t P, int has_invalid)
+// entry i of a sorted list of n entries (the whole list, or one slice join_hash handed back)
+template <typename KeyT, bool SEG, typename ValT>
+__device__ __forceinline__ void mum_join_at(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n, uint32_t i,
+                                            const GenomeTab &tab, int mode, uint32_t want_mask, uint32_t consider,
+                                            uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos, int has_invalid)
 {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
     const KeyT k = keys[i];
     if ((SEG || has_invalid) && k == (KeyT)~0ULL) return;
     if (i > 0 && keys[i - 1] == k) return;
@@ -508,7 +531,7 @@ __global__ void __launch_bounds__(256) mum_join(const KeyT *__restrict__ keys, c
     // entries of the other genomes are invisible to it
     uint32_t once = 0, multi = 0, j = i;
     while (j < n && keys[j] == k) {
-        uint32_t bit = (1u << genome_of(vals[j] & 0x7fffffffu, tab)) & consider;
+        uint32_t bit = (1u << genome_of(win_idx(vals[j]), tab)) & consider;
         multi |= once & bit; once |= bit; j++;
         if (mode == MAUVE_MODE_MEM && multi) return;   // MemHash: a repeat kills the seed, no need to finish the run
     }
@@ -519,12 +542,38 @@ __global__ void __launch_bounds__(256) mum_join(const KeyT *__restrict__ keys, c
     // entries of a run are in ascending global position (stable sort), so the anchor comes first
     uint32_t ap = 0xFFFFFFFFu;
     for (uint32_t t = i; t < j; t++) {
-        const uint32_t v = vals[t], gp = v & 0x7fffffffu;
+        const ValT v = vals[t]; const uint32_t gp = win_idx(v);
         const int g = genome_of(gp, tab);
         if (!(m >> g & 1)) continue;
         if (ap == 0xFFFFFFFFu) { ap = gp; tmask[ap] = m; }
-        tpos[(size_t)ap * tab.nseq + g] = v;
+        tpos[(size_t)ap * tab.nseq + g] = hit_word(v, tab.gpos_off[g]);
     }
+}
+template <typename KeyT, bool SEG, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) mum_join(const KeyT *__restrict__ keys, const ValT *__restrict__ vals,
+                                                uint32_t n, GenomeTab tab, int mode, uint32_t want_mask,
+                                                uint32_t consider, uint32_t *__restrict__ tmask,
+                                                uint32_t *__restrict__ tpos, uint32_t P, int has_invalid)
+{
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    mum_join_at<KeyT, SEG, ValT>(keys, vals, n, i, tab, mode, want_mask, consider, tmask, tpos, has_invalid);
+}
+// The slices join_hash handed back, all in one launch: thread t of the concatenated slices takes entry t - pre[q] of slice q (pre: running
+// slice lengths, nsl + 1 of them; lo: slice starts in the list).  A launch per slice ran the slices one after the other, and the head of a
+// run of millions of copies of one mer (a satellite repeat: UNIQUE and the pairwise finder walk the whole run) walks for seconds -- side by
+// side their walks overlap.
+template <typename KeyT, bool SEG, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) mum_join_slices(const KeyT *__restrict__ keys, const ValT *__restrict__ vals,
+                                                       const uint32_t *__restrict__ lo, const uint32_t *__restrict__ pre, uint32_t nsl,
+                                                       GenomeTab tab, int mode, uint32_t want_mask, uint32_t consider,
+                                                       uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos, int has_invalid)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= pre[nsl]) return;
+    uint32_t a = 0, b = nsl;                           // pre[a] <= t < pre[b]
+    while (b - a > 1) { const uint32_t m = (a + b) >> 1; if (pre[m] <= t) a = m; else b = m; }
+    mum_join_at<KeyT, SEG, ValT>(keys + lo[a], vals + lo[a], pre[a + 1] - pre[a], t - pre[a], tab, mode, want_mask, consider, tmask, tpos, has_invalid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -589,8 +638,10 @@ __global__ void __launch_bounds__(256) join_bounds(const KeyT *__restrict__ keys
     if ((threadIdx.x & 63) == 0) bound[c] = res;
 }
 
-template <typename KeyT, bool WIDE>
-__global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n,
+// (ValT = uint64_t: the values ride in registers only -- the slot that takes the anchor gets its window INDEX, which fits the key word --
+// so the LDS table is the narrow pass's)
+template <typename KeyT, bool WIDE, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n,
                                                  const uint32_t *__restrict__ bound, GenomeTab tab, int mode, uint32_t want_mask,
                                                  uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos,
                                                  uint32_t *__restrict__ ovf_cnt, uint32_t *__restrict__ ovf, uint32_t P)
@@ -603,11 +654,11 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
     const uint32_t cs = blockIdx.x * (uint32_t)HJ_T;
     // the rows sit at fixed places (cs + r*256 + tid), so their loads do not wait for the range: the first nine go out
     // at once; the range only decides which entries take part
-    KeyT k[HJ_ROWS]; uint32_t v[HJ_ROWS];
+    KeyT k[HJ_ROWS]; ValT v[HJ_ROWS];
 #pragma unroll
     for (int r = 0; r <= HJ_T / 256; r++) {
         const uint32_t idx = cs + (uint32_t)r * 256u + (uint32_t)tid;
-        k[r] = idx < n ? keys[idx] : EMPTY; v[r] = idx < n ? vals[idx] : 0u;
+        k[r] = idx < n ? keys[idx] : EMPTY; v[r] = idx < n ? vals[idx] : (ValT)0;
     }
     for (int i = tid; i < HJ_SLOTS; i += 256) { skey[i] = EMPTY; som[i] = 0; if (WIDE) som2[i] = 0; }
     __syncthreads();
@@ -624,7 +675,7 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
     for (int r = 0; r < HJ_ROWS; r++) {
         const uint32_t idx = cs + (uint32_t)r * 256u + (uint32_t)tid;
         if (r > HJ_T / 256) {                                 // rows the range rarely reaches
-            k[r] = EMPTY; v[r] = 0u;
+            k[r] = EMPTY; v[r] = (ValT)0;
             if (cs + (uint32_t)r * 256u < hi && idx < hi) { k[r] = keys[idx]; v[r] = vals[idx]; }
         }
         if (idx < lo || idx >= hi) k[r] = EMPTY;
@@ -642,7 +693,7 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
             if (old == EMPTY || old == k[r]) break;
             s = (s + 1) & (HJ_SLOTS - 1);
         }
-        const uint32_t bit = 1u << genome_of(v[r] & 0x7fffffffu, tab);
+        const uint32_t bit = 1u << genome_of(win_idx(v[r]), tab);
         const uint32_t old = atomicOr(&som[s], bit);
         if (old & bit) { if (WIDE) atomicOr(&som2[s], bit); else atomicOr(&som[s], bit << 16); }
         slot[r] = s; gbit[r] = bit;
@@ -660,15 +711,16 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
         if (mode == MAUVE_MODE_MEM && multi) continue;
         if (__popc(m) < 2 || (want_mask && m != want_mask) || !(m & gbit[r])) continue;
         mm[r] = m;
-        if ((m & (0u - m)) == gbit[r]) skey[slot[r]] = (KeyT)v[r];          // grouping is over: the slot's mer makes room for the anchor
+        if ((m & (0u - m)) == gbit[r]) skey[slot[r]] = sizeof(ValT) == 4 ? (KeyT)v[r] : (KeyT)win_idx(v[r]);   // grouping is over: the slot's mer makes room for the anchor
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < HJ_ROWS; r++) {
         if (!mm[r]) continue;
-        const uint32_t ap = (uint32_t)skey[slot[r]] & 0x7fffffffu;
+        const uint32_t ap = sizeof(ValT) == 4 ? (uint32_t)skey[slot[r]] & 0x7fffffffu : (uint32_t)skey[slot[r]];
         if (ap >= P) { atomicAdd(&ovf_cnt[1], 1u); continue; }   // cannot happen; a wild store could take the device down
-        tpos[(size_t)ap * tab.nseq + (__ffs(gbit[r]) - 1)] = v[r];
+        const int g = __ffs(gbit[r]) - 1;
+        tpos[(size_t)ap * tab.nseq + g] = hit_word(v[r], tab.gpos_off[g]);
         if ((mm[r] & (0u - mm[r])) == gbit[r]) tmask[ap] = mm[r];
     }
 }
@@ -684,6 +736,7 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
 constexpr int TJ_SLOTS = 16384;                  // 128 KB of LDS: key word + genome sets per slot
 constexpr int TJ_MAX = 9216;                     // load factor <= 0.5625
 constexpr int TJ_ROWS = TJ_MAX / 1024;
+template <bool LOCAL = false>
 __global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh, uint32_t P,
                                                   const uint64_t *__restrict__ vmask, const uint64_t *__restrict__ cmask, int mode, uint32_t want_mask,
                                                   uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos, uint32_t *__restrict__ err_cnt,
@@ -722,7 +775,7 @@ __global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ p
             if (p + (uint32_t)sh.span > sg[sk + 1]) continue;
             k |= sk << (2 * sh.weight);
         }
-        key[r] = k; v[r] = gp | (sflag << 31); gbit[r] = 1u << g;
+        key[r] = k; v[r] = (LOCAL ? p : gp) | (sflag << 31); gbit[r] = 1u << g;
     }
     __syncthreads();
 #pragma unroll
@@ -749,27 +802,30 @@ __global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ p
         if (mode == MAUVE_MODE_MEM && multi) continue;
         if (__popc(m) < 2 || (want_mask && m != want_mask) || !(m & gbit[r])) continue;
         mm[r] = m;
-        if ((m & (0u - m)) == gbit[r]) skey[slot[r]] = v[r];          // grouping is over: the slot's mer makes room for the anchor
+        if ((m & (0u - m)) == gbit[r])                                 // grouping is over: the slot's mer makes room for the anchor
+            skey[slot[r]] = LOCAL ? (v[r] & 0x7fffffffu) + tab.gpos_off[__ffs(gbit[r]) - 1] : v[r];
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < TJ_ROWS; r++) {
         if (!mm[r]) continue;
-        const uint32_t ap = skey[slot[r]] & 0x7fffffffu;
+        const uint32_t ap = LOCAL ? skey[slot[r]] : skey[slot[r]] & 0x7fffffffu;
         if (ap >= P) { atomicAdd(err_cnt, 1u); continue; }     // cannot happen (the anchor is one of the group's own windows)
         tpos[(size_t)ap * tab.nseq + (__ffs(gbit[r]) - 1)] = v[r];
         if ((mm[r] & (0u - mm[r])) == gbit[r]) tmask[ap] = mm[r];
     }
 }
 
+// (LOCAL: a wide pass -- the records carry windows local to their genome, as the hit table does; the anchor's global index is rebuilt)
+template <bool LOCAL = false>
 __global__ void __launch_bounds__(256) hits_scatter(const uint32_t *__restrict__ rec, uint32_t nh, int N, uint32_t P,
-                                                    uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos)
+                                                    uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos, GenomeTab tab)
 {
     const uint32_t h = blockIdx.x * 256u + threadIdx.x;
     if (h >= nh) return;
     const uint32_t *r = rec + (size_t)h * (N + 1);
     const uint32_t m = r[0];
-    const uint32_t ap = r[1 + (__ffs(m) - 1)] & 0x7fffffffu;
+    const uint32_t ap = (r[1 + (__ffs(m) - 1)] & 0x7fffffffu) + (LOCAL ? tab.gpos_off[__ffs(m) - 1] : 0u);
     if (ap >= P) return;                                      // validated on the host; never a wild store
     tmask[ap] = m;
     for (int g = 0; g < N; g++) if (m >> g & 1) tpos[(size_t)ap * N + g] = r[1 + g];
@@ -783,8 +839,8 @@ __global__ void __launch_bounds__(256) hits_scatter(const uint32_t *__restrict__
 // genomes: entries of the others are invisible to it).  The order of the list does not matter: hits go to the
 // dense table by anchor position.
 // ------------------------------------------------------------------------------------------------
-template <typename KeyT>
-__global__ void __launch_bounds__(256) run_summary(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n,
+template <typename KeyT, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) run_summary(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n,
                                                    GenomeTab tab, int has_invalid, uint32_t *__restrict__ rstart,
                                                    uint32_t *__restrict__ rlen, uint32_t *__restrict__ runiq,
                                                    uint32_t *__restrict__ counter, uint32_t cap)
@@ -806,7 +862,7 @@ __global__ void __launch_bounds__(256) run_summary(const KeyT *__restrict__ keys
             if (valid && (i == 0 || keys[i - 1] != k) && i + 1 < n && keys[i + 1] == k) {
                 uint32_t once = 0, multi = 0, j = i;
                 while (j < n && keys[j] == k) {
-                    const uint32_t bit = 1u << genome_of(vals[j] & 0x7fffffffu, tab);
+                    const uint32_t bit = 1u << genome_of(win_idx(vals[j]), tab);
                     multi |= once & bit; once |= bit; j++;
                 }
                 uniq[it] = once & ~multi; len[it] = j - i;
@@ -824,7 +880,8 @@ __global__ void __launch_bounds__(256) run_summary(const KeyT *__restrict__ keys
         if (uniq[it]) { if (r < cap) { rstart[r] = base + it * 256 + threadIdx.x; rlen[r] = len[it]; runiq[r] = uniq[it]; } r++; }   // (the counter keeps counting: the host sees a list that outgrew its buffer)
 }
 
-__global__ void __launch_bounds__(256) join_pair(const uint32_t *__restrict__ vals, GenomeTab tab, const uint32_t *__restrict__ rstart,
+template <typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) join_pair(const ValT *__restrict__ vals, GenomeTab tab, const uint32_t *__restrict__ rstart,
                                                  const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ runiq,
                                                  uint32_t nruns, int gi, int gj, uint32_t *__restrict__ tmask,
                                                  uint32_t *__restrict__ tpos)
@@ -834,17 +891,17 @@ __global__ void __launch_bounds__(256) join_pair(const uint32_t *__restrict__ va
     const uint32_t u = runiq[r];
     if (!((u >> gi) & (u >> gj) & 1u)) return;
     const uint32_t s = rstart[r], L = rlen[r];
-    uint32_t vi = 0, vj = 0;
+    ValT vi = 0, vj = 0;
     for (uint32_t t = s; t < s + L; t++) {
-        const uint32_t v = vals[t];
-        const int g = genome_of(v & 0x7fffffffu, tab);
+        const ValT v = vals[t];
+        const int g = genome_of(win_idx(v), tab);
         if (g == gi) vi = v;
         if (g == gj) vj = v;
     }
-    const uint32_t ap = vi & 0x7fffffffu;               // gi < gj: the anchor is genome gi's window
+    const uint32_t ap = win_idx(vi);                    // gi < gj: the anchor is genome gi's window
     tmask[ap] = (1u << gi) | (1u << gj);
-    tpos[(size_t)ap * tab.nseq + gi] = vi;
-    tpos[(size_t)ap * tab.nseq + gj] = vj;
+    tpos[(size_t)ap * tab.nseq + gi] = hit_word(vi, tab.gpos_off[gi]);
+    tpos[(size_t)ap * tab.nseq + gj] = hit_word(vj, tab.gpos_off[gj]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -857,8 +914,8 @@ __global__ void __launch_bounds__(256) join_pair(const uint32_t *__restrict__ va
 //   vscan_*    : start offsets; cmp_* (EnumRuns): the emitting runs in list order -> mult / start_off
 //   enum_write : the heads walk again and write the starts
 // ------------------------------------------------------------------------------------------------
-template <typename KeyT>
-__global__ void __launch_bounds__(256) enum_runs(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n, int64_t min_multi,
+template <typename KeyT, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) enum_runs(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n, int64_t min_multi,
                                                  int64_t max_multi, int direct_only, uint32_t *__restrict__ emit)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -866,9 +923,9 @@ __global__ void __launch_bounds__(256) enum_runs(const KeyT *__restrict__ keys, 
     const KeyT k = keys[i];
     uint32_t e = 0;
     if (i == 0 || keys[i - 1] != k) {
-        const uint32_t ref = vals[i] >> 31;
+        const uint32_t ref = win_strand(vals[i]);
         uint32_t j = i, kept = 0; bool found_rev = false;
-        while (j < n && keys[j] == k) { if ((vals[j] >> 31) != ref) found_rev = true; else kept++; j++; }
+        while (j < n && keys[j] == k) { if (win_strand(vals[j]) != ref) found_rev = true; else kept++; j++; }
         const int64_t m = (int64_t)(j - i);
         if (m >= 2 && m >= min_multi && m <= max_multi) e = (direct_only && found_rev) ? (kept > 1 ? kept : 0u) : (uint32_t)m;
     }
@@ -883,21 +940,21 @@ struct EnumRuns {
     __device__ void emit(uint32_t i, uint32_t r, int) const { mult[r] = cnt[i]; start_off[r] = soff[i]; }
     __device__ void total(uint32_t runs, int) const { tot[0] = runs; start_off[runs] = soff[n]; }
 };
-template <typename KeyT>
-__global__ void __launch_bounds__(256) enum_write(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n, int direct_only,
+template <typename KeyT, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) enum_write(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n, int direct_only,
                                                   const uint32_t *__restrict__ emit, const int64_t *__restrict__ soff, uint32_t gpos0,
                                                   int64_t *__restrict__ starts)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || emit[i] == 0) return;
     const KeyT k = keys[i];
-    const uint32_t ref = vals[i] >> 31;
+    const uint32_t ref = win_strand(vals[i]);
     uint32_t j = i; bool found_rev = false;
-    while (j < n && keys[j] == k) { if ((vals[j] >> 31) != ref) found_rev = true; j++; }
+    while (j < n && keys[j] == k) { if (win_strand(vals[j]) != ref) found_rev = true; j++; }
     int64_t o = soff[i];
     for (uint32_t t = i; t < j; t++) {
-        const bool rv = (vals[t] >> 31) != ref;
-        const int64_t p1 = (int64_t)((vals[t] & 0x7fffffffu) - gpos0) + 1;
+        const bool rv = win_strand(vals[t]) != ref;
+        const int64_t p1 = (int64_t)(win_idx(vals[t]) - gpos0) + 1;
         if (direct_only && found_rev) { if (!rv) starts[o++] = p1; }
         else starts[o++] = rv ? -p1 : p1;
     }
@@ -1189,7 +1246,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
     if (lo + blockIdx.x * RUNS_TILE >= hi) return;                     // (workgroup-uniform: the grid covers the longest slice)
     mum_runs_body<false>(tab, span, tmask, tpos, hi, all, cand, counters, nullptr, 0u, lo, cand_cap);
 }
-__global__ void __launch_bounds__(256) join_pair_group(const uint32_t *__restrict__ vals, GenomeTab tab, const uint32_t *__restrict__ rstart,
+template <typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) join_pair_group(const ValT *__restrict__ vals, GenomeTab tab, const uint32_t *__restrict__ rstart,
                                                        const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ runiq,
                                                        uint32_t nruns, PairGroup grp, uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos)
 {
@@ -1202,27 +1260,27 @@ __global__ void __launch_bounds__(256) join_pair_group(const uint32_t *__restric
     const uint32_t s = rstart[r], L = rlen[r];
     // the run's entries once (nearly every run has at most one entry per genome: <= 8 of them stay in registers)
     constexpr int RC = 8;
-    uint32_t ev[RC]; int eg[RC];
+    ValT ev[RC]; int eg[RC];
 #pragma unroll
     for (int t = 0; t < RC; t++) {
         ev[t] = 0; eg[t] = -1;
-        if ((uint32_t)t < L) { ev[t] = vals[s + t]; eg[t] = genome_of(ev[t] & 0x7fffffffu, tab); }
+        if ((uint32_t)t < L) { ev[t] = vals[s + t]; eg[t] = genome_of(win_idx(ev[t]), tab); }
     }
     for (; hit; hit &= hit - 1) {
         const int y = __ffs(hit) - 1, gi = grp.ga[y], gj = grp.gb[y];
-        uint32_t vi = 0, vj = 0;
+        ValT vi = 0, vj = 0;
 #pragma unroll
         for (int t = 0; t < RC; t++) { if (eg[t] == gi) vi = ev[t]; if (eg[t] == gj) vj = ev[t]; }
         for (uint32_t t = s + RC; t < s + L; t++) {     // (longer runs: the rest from memory)
-            const uint32_t v = vals[t];
-            const int g = genome_of(v & 0x7fffffffu, tab);
+            const ValT v = vals[t];
+            const int g = genome_of(win_idx(v), tab);
             if (g == gi) vi = v;
             if (g == gj) vj = v;
         }
-        const uint32_t ap = vi & 0x7fffffffu;           // gi < gj: the anchor is genome gi's window
+        const uint32_t ap = win_idx(vi);                // gi < gj: the anchor is genome gi's window
         tmask[ap] = (1u << gi) | (1u << gj);
-        tpos[(size_t)ap * tab.nseq + gi] = vi;
-        tpos[(size_t)ap * tab.nseq + gj] = vj;
+        tpos[(size_t)ap * tab.nseq + gi] = hit_word(vi, tab.gpos_off[gi]);
+        tpos[(size_t)ap * tab.nseq + gj] = hit_word(vj, tab.gpos_off[gj]);
     }
 }
 
@@ -1233,7 +1291,7 @@ __global__ void __launch_bounds__(256) join_pair_group(const uint32_t *__restric
 // measurement build only (-DMAUVE_EXT_STATS): [0] rounds, [2] sum of wave times, [3] longest wave time (10 ns ticks), [4] waves, [5] most rounds of one wave, [1] / [6] / [7] time in set-up / left walk / right walk
 __device__ unsigned long long g_ext_stats[8];
 #endif
-template <bool SEG>
+template <bool SEG, bool LOCAL = false>
 __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh,
                                                   const uint32_t *__restrict__ tmask, const uint32_t *__restrict__ tpos,
                                                   uint32_t P, const uint32_t *__restrict__ cand, uint32_t ncand,
@@ -1278,7 +1336,7 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
             C.G = packed + tab.word_off[g];
             C.VM = vmask ? vmask + tab.mask_off[g] : nullptr;
             C.CM = cmask ? cmask + tab.mask_off[g] : nullptr;
-            C.pos = (int64_t)((vg & 0x7fffffffu) - tab.gpos_off[g]);
+            C.pos = (int64_t)((vg & 0x7fffffffu) - (LOCAL ? 0u : tab.gpos_off[g]));      // (LOCAL: a wide pass's table word, hit_word)
             C.rev = (vg >> 31) ^ sa; C.g = (uint32_t)g; C.pad = 0;
             C.lo = 0; C.hi = (int64_t)tab.nwin[g] - 1;
             C.maxw = (uint32_t)(((uint64_t)tab.nwin[g] + (uint32_t)sh.span - 1 + 31) / 32 + 2);       // mauve_packed_words - 1
@@ -1539,7 +1597,8 @@ static int build_tab(mauve_ctx *ctx, const GenomeSet &gs, int span, GenomeTab *t
         tab->gpos_off[g] = (uint32_t)tot; tab->nwin[g] = (uint32_t)nw; tab->word_off[g] = gs.word_off[g];
         tab->mask_off[g] = (gs.vmask || gs.cmask) ? gs.mask_off[g] : 0;
         tot += nw;
-        if (tot >= (1LL << 31)) { ctx->err = "total genome length exceeds 2^31 windows"; return MAUVE_ERR_LIMIT; }
+        if (gs.lens[g] >= MAUVE_MAX_GENOME_LEN) { ctx->err = "seed pass: a genome holds 2^31 bases or more (per-genome limit)"; return MAUVE_ERR_LIMIT; }
+        if (tot >= MAUVE_MAX_TOTAL_LEN) { ctx->err = "seed pass: the genomes together hold 2^32 - 2^20 windows or more (total limit)"; return MAUVE_ERR_LIMIT; }
     }
     tab->gpos_off[gs.nseq] = (uint32_t)tot;
     for (int g = gs.nseq + 1; g <= MAUVE_MAX_SEQ; g++) tab->gpos_off[g] = 0xffffffffu;      // see genome_of
@@ -1547,9 +1606,9 @@ static int build_tab(mauve_ctx *ctx, const GenomeSet &gs, int span, GenomeTab *t
     return MAUVE_OK;
 }
 
-template <typename KeyT>
-static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, uint32_t **vals_io, KeyT *keys_alt,
-                      uint32_t *vals_alt, bool have_hist0, int timer_id = -1, int shift_lo = 0)
+template <typename KeyT, typename ValT = uint32_t>
+static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **vals_io, KeyT *keys_alt,
+                      ValT *vals_alt, bool have_hist0, int timer_id = -1, int shift_lo = 0)
 {
     // LSD passes over bits [shift_lo, key_bits); have_hist0: the tile histograms of the first pass are already in ctx->hist
     // timer_id >= 0: all launches are booked under that id (the small canonical-order sort must not dilute the
@@ -1567,7 +1626,7 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
     uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
     HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
     HIPCHK(ctx, ctx->totals.ensure(256 * sizeof(uint32_t)));
-    KeyT *kin = *keys_io, *kout = keys_alt; uint32_t *vin = *vals_io, *vout = vals_alt;
+    KeyT *kin = *keys_io, *kout = keys_alt; ValT *vin = *vals_io, *vout = vals_alt;
     for (int shift = shift_lo; shift < key_bits; shift += 8) {
         if (!(shift == shift_lo && have_hist0)) { KernelTimer t(ctx, k_hist, n);
           hipLaunchKernelGGL(rs_hist<KeyT>, dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, n, shift,
@@ -1575,7 +1634,7 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
         static const bool no_raw = getenv("MAUVE_SORT_ROWSCAN") != nullptr;        // A/B switch
         if (nblk <= 64 && !no_raw) {      // small sort: no row scan launch, the scatter reads the raw tile histograms
             KernelTimer t(ctx, k_scat, n);
-            hipLaunchKernelGGL((rs_scatter<KeyT, true>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
+            hipLaunchKernelGGL((rs_scatter<KeyT, true, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
                                shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk);
             std::swap(kin, kout); std::swap(vin, vout);
             continue;
@@ -1584,7 +1643,7 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
           hipLaunchKernelGGL(rs_rowscan, dim3(256), dim3(256), 0, ctx->stream, ctx->hist.as<uint32_t>(), nblk,
                              ctx->totals.as<uint32_t>()); }
         { KernelTimer t(ctx, k_scat, n);
-          hipLaunchKernelGGL(rs_scatter<KeyT>, dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
+          hipLaunchKernelGGL((rs_scatter<KeyT, false, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
                              shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk); }
         std::swap(kin, kout); std::swap(vin, vout);
     }
@@ -1595,19 +1654,24 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
 
 // One seed pass over a genome set.  SEG: the set is segmented (recursive anchoring); seg = device array
 // [nseq][nseg+1] of segment starts.  Results land in ctx->match_len / match_start (canonical order).
-template <typename KeyT, bool SEG>
+// ValT: the sort value, uint32_t (narrow) or uint64_t (wide: a pass of 2^31 windows or more, or MAUVE_WIDE_INDEX=1).  A wide
+// pass's hit table and host-side hit records hold windows local to their genome (hit_word); out_vals are then local too.
+template <typename KeyT, bool SEG, typename ValT = uint32_t>
 static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, int64_t total,
                          int mode, uint64_t mask, int extend, int only_seq, const uint32_t *seg, uint32_t nseg,
                          int64_t *n_matches, std::vector<uint64_t> *out_keys, std::vector<uint32_t> *out_vals)
 {
+    constexpr bool WIDEV = sizeof(ValT) == 8;
     const uint32_t n = (uint32_t)total;
     double trace_t0 = now_ms();
+    if (g_trace) fprintf(stderr, "[trace] seed pass: %u windows, %d-bit keys, %s window index (%d-bit values)\n", n, (int)sizeof(KeyT) * 8,
+                         WIDEV ? "wide" : "narrow", (int)sizeof(ValT) * 8);
     HIPCHK(ctx, ctx->keysA.ensure((size_t)n * sizeof(KeyT)));
     HIPCHK(ctx, ctx->keysB.ensure((size_t)n * sizeof(KeyT)));
-    HIPCHK(ctx, ctx->valsA.ensure((size_t)n * 4));
-    HIPCHK(ctx, ctx->valsB.ensure((size_t)n * 4));
+    HIPCHK(ctx, ctx->valsA.ensure((size_t)n * sizeof(ValT)));
+    HIPCHK(ctx, ctx->valsB.ensure((size_t)n * sizeof(ValT)));
     HIPCHK(ctx, ctx->counters.ensure(64));
-    KeyT *keys = ctx->keysA.as<KeyT>(); uint32_t *vals = ctx->valsA.as<uint32_t>();
+    KeyT *keys = ctx->keysA.as<KeyT>(); ValT *vals = ctx->valsA.as<ValT>();
     const uint64_t *packed = gs.buf->as<uint64_t>();
     const uint64_t *vmask = gs.vmask ? gs.vmask->as<uint64_t>() : nullptr;
     const uint64_t *cmask = gs.cmask ? gs.cmask->as<uint64_t>() : nullptr;
@@ -1651,10 +1715,10 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
             hipLaunchKernelGGL(valid_count, dim3(nblk), dim3(256), 0, ctx->stream, tab, sh.span, n, vmask, tile_cnt, cmask);
             hipLaunchKernelGGL(tile_scan, dim3(1), dim3(256), 0, ctx->stream, tile_cnt, nblk, ctx->counters.as<uint32_t>());
             if (sh.span <= 32 && sh.weight <= 15)
-                hipLaunchKernelGGL((seed_extract_compact<KeyT, true>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys, vals, n,
+                hipLaunchKernelGGL((seed_extract_compact<KeyT, true, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys, vals, n,
                                    vmask, tile_cnt, cmask);
             else
-                hipLaunchKernelGGL((seed_extract_compact<KeyT, false>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys, vals, n,
+                hipLaunchKernelGGL((seed_extract_compact<KeyT, false, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys, vals, n,
                                    vmask, tile_cnt, cmask);
         }
         HIPCHK(ctx, hipGetLastError());
@@ -1669,10 +1733,10 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
         KernelTimer t(ctx, MAUVE_K_EXTRACT, n);
         const int hshift = low_bits(n);
         if (sh.span <= 32 && sh.weight <= 15)
-            hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, true>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
+            hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, true, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
                                vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask);
         else
-            hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, false>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
+            hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, false, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
                                vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask);
         sorted_n = n; have_hist0 = true;
     } else {
@@ -1681,7 +1745,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
         if (nw) {
             uint32_t blocks = std::min<uint32_t>((nw + 255) / 256, 256 * 16);
             KernelTimer t(ctx, MAUVE_K_EXTRACT, nw);
-            hipLaunchKernelGGL((seed_extract<KeyT, SEG>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, g, keys,
+            hipLaunchKernelGGL((seed_extract<KeyT, SEG, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, g, keys,
                                vals, 0u, seg, nseg);
             sorted_n = nw;
         }
@@ -1693,7 +1757,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
     const int has_invalid = masked && !compacted;
     const uint32_t ns = sorted_n;                   // entries of the sorted list (all windows, or the valid ones)
     const int L = low_bits(ns);                     // the passes order bits [L, key_bits); 0 = full sort
-    int rc = (hh || tiny) ? MAUVE_OK : sort_pairs<KeyT>(ctx, sorted_n, key_bits, &keys, &vals, ctx->keysB.as<KeyT>(), ctx->valsB.as<uint32_t>(), have_hist0, -1, L);
+    int rc = (hh || tiny) ? MAUVE_OK : sort_pairs<KeyT, ValT>(ctx, sorted_n, key_bits, &keys, &vals, ctx->keysB.as<KeyT>(), ctx->valsB.as<ValT>(), have_hist0, -1, L);
     if (rc) return rc;
     TRACE(ctx, "sort");
 
@@ -1706,7 +1770,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
         int64_t *soff = reinterpret_cast<int64_t *>(ctx->run_sum.as<char>() + (((size_t)sorted_n * 4 + 63) & ~(size_t)63));
         int64_t *d_mult = soff + sorted_n + 2, *d_off = d_mult + sorted_n + 2, *bsum = d_off + sorted_n + 2, *tot = bsum + nb + 2;
         uint32_t *bcnt = reinterpret_cast<uint32_t *>(tot + 4);
-        hipLaunchKernelGGL((enum_runs<KeyT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.min_multi, q.max_multi, q.direct_only, emit);
+        hipLaunchKernelGGL((enum_runs<KeyT, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.min_multi, q.max_multi, q.direct_only, emit);
         hipLaunchKernelGGL((vscan_partial<int64_t, EmitVal>), dim3(nb), dim3(256), 0, ctx->stream, EmitVal{emit}, sorted_n, bsum);
         hipLaunchKernelGGL((vscan_write<int64_t, EmitVal>), dim3(nb), dim3(256), 0, ctx->stream, EmitVal{emit}, sorted_n, bsum, soff, tot + 1);
         const EnumRuns er{emit, soff, sorted_n, d_mult, d_off, tot};
@@ -1719,7 +1783,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
         q.n = ht[0]; q.ns = ht[1];
         if (q.starts) {
             HIPCHK(ctx, ctx->sorted_rec.ensure(((size_t)q.ns + 1) * 8));
-            hipLaunchKernelGGL((enum_write<KeyT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.direct_only, emit, soff,
+            hipLaunchKernelGGL((enum_write<KeyT, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.direct_only, emit, soff,
                                tab.gpos_off[only_seq], ctx->sorted_rec.as<int64_t>());
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, hipMemcpyAsync(q.mult, d_mult, (size_t)q.n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1732,11 +1796,16 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
     if (out_keys) {   // sorted-mer-list export: hand the sorted pairs to the host
         std::vector<KeyT> hk(sorted_n);
         out_vals->resize(sorted_n);
+        std::vector<ValT> hv(WIDEV ? sorted_n : 0);
         HIPCHK(ctx, hipMemcpyAsync(hk.data(), keys, (size_t)sorted_n * sizeof(KeyT), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out_vals->data(), vals, (size_t)sorted_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(WIDEV ? (void *)hv.data() : (void *)out_vals->data(), vals, (size_t)sorted_n * sizeof(ValT), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         out_keys->resize(sorted_n);
         for (uint32_t i = 0; i < sorted_n; i++) (*out_keys)[i] = (uint64_t)hk[i];
+        if (WIDEV) {                                // wide: local to the genome already (index | strand << 31), as the narrow caller makes them
+            const uint32_t g0 = tab.gpos_off[only_seq];
+            for (uint32_t i = 0; i < sorted_n; i++) (*out_vals)[i] = ((uint32_t)hv[i] - g0) | ((uint32_t)((uint64_t)hv[i] >> 63) << 31);
+        }
         return MAUVE_OK;
     }
 
@@ -1779,7 +1848,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
         rstart = ctx->run_sum.as<uint32_t>(); rlen = rstart + cap; runiq = rlen + cap;
         HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
         { KernelTimer t(ctx, MAUVE_K_JOIN, ns);
-          hipLaunchKernelGGL((run_summary<KeyT>), dim3((ns + 1023) / 1024), dim3(256), 0, ctx->stream, keys, vals, ns, tab,
+          hipLaunchKernelGGL((run_summary<KeyT, ValT>), dim3((ns + 1023) / 1024), dim3(256), 0, ctx->stream, keys, vals, ns, tab,
                              has_invalid, rstart, rlen, runiq, ctx->counters.as<uint32_t>() + 2, run_cap); }
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, ctx->pin_seed.ensure(64));
@@ -1817,7 +1886,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
             for (int y = 0; y < grp.n; y++) HIPCHK(ctx, hipMemsetAsync(ctx->posmask.as<uint32_t>() + grp.lo[y], 0, (size_t)(grp.hi[y] - grp.lo[y]) * 4, ctx->stream));
             HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
             { KernelTimer t(ctx, MAUVE_K_JOIN, nruns);
-              hipLaunchKernelGGL(join_pair_group, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, vals, tab, rstart, rlen, runiq, nruns, grp, tmask, tpos); }
+              hipLaunchKernelGGL(join_pair_group<ValT>, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, vals, tab, rstart, rlen, runiq, nruns, grp, tmask, tpos); }
             HIPCHK(ctx, hipGetLastError());
             TRACE(ctx, "join");
             { KernelTimer t(ctx, MAUVE_K_RUNS, slices);
@@ -1838,7 +1907,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
             {
                 const uint32_t blocks = std::min<uint32_t>((nc + 3) / 4, 256 * 8);
                 KernelTimer t(ctx, MAUVE_K_EXTEND, nc);
-                hipLaunchKernelGGL((mum_extend<SEG>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P, ctx->cand.as<uint32_t>(), nc, extend,
+                hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P, ctx->cand.as<uint32_t>(), nc, extend,
                                    ctx->mlen.as<int32_t>() + cand_total, ctx->mstart.as<int32_t>() + (size_t)cand_total * N, seg, nseg, vmask, cmask);
                 HIPCHK(ctx, hipGetLastError());
             }
@@ -1861,18 +1930,18 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
         if (hh) {
             HIPCHK(ctx, ctx->run_sum.ensure((size_t)hh->n * (N + 1) * 4 + 64));
             HIPCHK(ctx, hipMemcpyAsync(ctx->run_sum.p, hh->rec, (size_t)hh->n * (N + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-            if (hh->n) hipLaunchKernelGGL(hits_scatter, dim3((hh->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->run_sum.as<uint32_t>(), hh->n, N, P, tmask, tpos);
+            if (hh->n) hipLaunchKernelGGL(hits_scatter<WIDEV>, dim3((hh->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->run_sum.as<uint32_t>(), hh->n, N, P, tmask, tpos, tab);
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the host records must outlive the copy
         } else if (use_summary) {
             KernelTimer t(ctx, MAUVE_K_JOIN, nruns);
             if (nruns)
-                hipLaunchKernelGGL(join_pair, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, vals, tab, rstart, rlen, runiq, nruns,
+                hipLaunchKernelGGL(join_pair<ValT>, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, vals, tab, rstart, rlen, runiq, nruns,
                                    __builtin_ctz(fp.consider), 31 - __builtin_clz(fp.consider), tmask, tpos);
         } else if (tiny) {
-            static const bool tj_attr = []() { return hipFuncSetAttribute(reinterpret_cast<const void *>(tiny_join), hipFuncAttributeMaxDynamicSharedMemorySize, TJ_SLOTS * 8) == hipSuccess; }();
+            static const bool tj_attr = []() { return hipFuncSetAttribute(reinterpret_cast<const void *>(tiny_join<WIDEV>), hipFuncAttributeMaxDynamicSharedMemorySize, TJ_SLOTS * 8) == hipSuccess; }();
             if (!tj_attr) { ctx->err = "tiny_join: cannot reserve its LDS"; return MAUVE_ERR_HIP; }
             KernelTimer t(ctx, MAUVE_K_JOIN, P);
-            hipLaunchKernelGGL(tiny_join, dim3(1), dim3(1024), TJ_SLOTS * 8, ctx->stream, packed, tab, sh, P, vmask, cmask, fp.rule, fp.want, tmask, tpos,
+            hipLaunchKernelGGL(tiny_join<WIDEV>, dim3(1), dim3(1024), TJ_SLOTS * 8, ctx->stream, packed, tab, sh, P, vmask, cmask, fp.rule, fp.want, tmask, tpos,
                                ctx->counters.as<uint32_t>() + 9, SEG ? seg : (const uint32_t *)nullptr, nseg, ctx->counters.as<uint32_t>(), s_lo, s_hi);
         } else if (hash_path) {
             const uint32_t nchunk = (ns + HJ_T - 1) / HJ_T;
@@ -1881,14 +1950,14 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
             HIPCHK(ctx, ctx->join_bound.ensure(((size_t)nchunk + 2) * 4));
             hipLaunchKernelGGL((join_bounds<KeyT>), dim3((nchunk + 1 + 3) / 4), dim3(256), 0, ctx->stream, keys, ns, L, nchunk,
                                ctx->join_bound.as<uint32_t>());
-#define JH_LAUNCH(W) hipLaunchKernelGGL((join_hash<KeyT, W>), dim3(nchunk), dim3(256), 0, ctx->stream, keys, vals, ns, \
+#define JH_LAUNCH(W) hipLaunchKernelGGL((join_hash<KeyT, W, ValT>), dim3(nchunk), dim3(256), 0, ctx->stream, keys, vals, ns, \
                                            ctx->join_bound.as<uint32_t>(), tab, fp.rule, fp.want, tmask, tpos, ctx->counters.as<uint32_t>() + 8, ctx->join_ovf.as<uint32_t>(), P)
             if (N > 16) JH_LAUNCH(true);
             else JH_LAUNCH(false);
 #undef JH_LAUNCH
         } else
         { KernelTimer t(ctx, MAUVE_K_JOIN, ns);
-          hipLaunchKernelGGL((mum_join<KeyT, SEG>), dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, keys, vals, ns, tab, fp.rule,
+          hipLaunchKernelGGL((mum_join<KeyT, SEG, ValT>), dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, keys, vals, ns, tab, fp.rule,
                              fp.want, fp.consider, tmask, tpos, P, has_invalid); }
         HIPCHK(ctx, hipGetLastError());
         TRACE(ctx, "join");
@@ -1915,7 +1984,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
             int32_t *o_len = host_out ? reinterpret_cast<int32_t *>(pin + 64) : ctx->mlen.as<int32_t>();
             int32_t *o_st = host_out ? reinterpret_cast<int32_t *>(pin + 64 + lbytes) : ctx->mstart.as<int32_t>();
             { KernelTimer t(ctx, MAUVE_K_EXTEND, cand_cap);
-              hipLaunchKernelGGL((mum_extend<SEG>), dim3(std::min<uint32_t>((cand_cap + 3) / 4, 512)), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P,
+              hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(std::min<uint32_t>((cand_cap + 3) / 4, 512)), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P,
                                  ctx->cand.as<uint32_t>(), cand_cap, extend, o_len, o_st, seg, nseg, vmask, cmask,
                                  ctx->counters.as<uint32_t>() + 1, reinterpret_cast<uint32_t *>(pin)); }
             HIPCHK(ctx, hipGetLastError());
@@ -1950,15 +2019,34 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
                 HIPCHK(ctx, hipMemcpy(rng.data(), ctx->join_ovf.as<uint32_t>() + 2, rng.size() * 4, hipMemcpyDeviceToHost));
             }
             KeyT *alt_k = keys == ctx->keysA.as<KeyT>() ? ctx->keysB.as<KeyT>() : ctx->keysA.as<KeyT>();
-            uint32_t *alt_v = vals == ctx->valsA.as<uint32_t>() ? ctx->valsB.as<uint32_t>() : ctx->valsA.as<uint32_t>();
-            for (size_t q = 0; q + 1 < rng.size(); q += 2) {
-                const uint32_t s0 = rng[q], cnt = rng[q + 1] - rng[q];
-                KeyT *kp = keys + s0; uint32_t *vp = vals + s0;
-                int rc3 = sort_pairs<KeyT>(ctx, cnt, key_bits, &kp, &vp, alt_k + s0, alt_v + s0, false, MAUVE_K_JOIN);
+            ValT *alt_v = vals == ctx->valsA.as<ValT>() ? ctx->valsB.as<ValT>() : ctx->valsA.as<ValT>();
+            // each slice sorted in full where it lies (the sorted pairs end up in this buffer or the other one), then ONE join over all slices
+            const size_t nsl = rng.size() / 2;
+            std::vector<uint32_t> sl_lo(nsl), sl_pre(nsl + 1, 0);
+            const KeyT *jk = keys; const ValT *jv = vals;
+            uint64_t tot_sl = 0;
+            for (size_t q = 0; q < nsl; q++) {
+                const uint32_t s0 = rng[2 * q], cnt = rng[2 * q + 1] - rng[2 * q];
+                KeyT *kp = keys + s0; ValT *vp = vals + s0;
+                int rc3 = sort_pairs<KeyT, ValT>(ctx, cnt, key_bits, &kp, &vp, alt_k + s0, alt_v + s0, false, MAUVE_K_JOIN);
                 if (rc3) return rc3;
-                KernelTimer t(ctx, MAUVE_K_JOIN, cnt);
-                hipLaunchKernelGGL((mum_join<KeyT, SEG>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, kp, vp, cnt, tab, fp.rule,
-                                   fp.want, fp.consider, tmask, tpos, P, has_invalid);
+                if (kp != keys + s0) {           // an odd number of passes: the slice now lies in the other buffer -- copy it back
+                    HIPCHK(ctx, hipMemcpyAsync(keys + s0, kp, (size_t)cnt * sizeof(KeyT), hipMemcpyDeviceToDevice, ctx->stream));
+                    HIPCHK(ctx, hipMemcpyAsync(vals + s0, vp, (size_t)cnt * sizeof(ValT), hipMemcpyDeviceToDevice, ctx->stream));
+                }
+                sl_lo[q] = s0; tot_sl += cnt; sl_pre[q + 1] = (uint32_t)tot_sl;
+            }
+            if (tot_sl) {
+                HIPCHK(ctx, ctx->join_bound.ensure((2 * nsl + 1) * 4));
+                HIPCHK(ctx, ctx->pin_seed.ensure(64 + (2 * nsl + 1) * 4));
+                uint32_t *hp = reinterpret_cast<uint32_t *>(ctx->pin_seed.as<char>() + 64);
+                memcpy(hp, sl_lo.data(), nsl * 4); memcpy(hp + nsl, sl_pre.data(), (nsl + 1) * 4);
+                HIPCHK(ctx, hipMemcpyAsync(ctx->join_bound.p, hp, (2 * nsl + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+                KernelTimer t(ctx, MAUVE_K_JOIN, (uint32_t)tot_sl);
+                hipLaunchKernelGGL((mum_join_slices<KeyT, SEG, ValT>), dim3((uint32_t)((tot_sl + 255) / 256)), dim3(256), 0, ctx->stream, jk, jv,
+                                   ctx->join_bound.as<uint32_t>(), ctx->join_bound.as<uint32_t>() + nsl, (uint32_t)nsl, tab, fp.rule, fp.want,
+                                   fp.consider, tmask, tpos, has_invalid);
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));     // the page-locked slice table is reused by the counter copy below
             }
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
@@ -1985,7 +2073,7 @@ static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &s
             static const int per_cu = getenv("MAUVE_EXT_BLOCKS_PER_CU") ? atoi(getenv("MAUVE_EXT_BLOCKS_PER_CU")) : 12;
             uint32_t blocks = std::min<uint32_t>((nc + 3) / 4, (uint32_t)(ctx->cus * per_cu));
             KernelTimer t(ctx, MAUVE_K_EXTEND, nc);
-            hipLaunchKernelGGL((mum_extend<SEG>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P,
+            hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P,
                                ctx->cand.as<uint32_t>(), nc, extend, ctx->mlen.as<int32_t>() + cand_total,
                                ctx->mstart.as<int32_t>() + (size_t)cand_total * N, seg, nseg, vmask, cmask);
             HIPCHK(ctx, hipGetLastError());
@@ -2248,6 +2336,18 @@ int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io,
     return sort_pairs<uint32_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
 }
 
+// Index width of a seed pass: wide values when the pass has 2^31 windows or more; MAUVE_WIDE_INDEX=1 forces them for every
+// pass (test switch: small inputs take the wide kernels against the oracle).  Every other pass runs the narrow instantiations.
+bool seedpass_wide(int64_t total_windows)
+{
+    static const bool force = [] { const char *e = getenv("MAUVE_WIDE_INDEX"); return e && e[0] == '1' && e[1] == 0; }();
+    return force || total_windows >= (1LL << 31);
+}
+
+// the seedpass_impl instantiation of a pass: key width by the seed weight (and SEG), value width by seedpass_wide
+#define SEEDPASS_DISPATCH(KEY, SEGV, ...) \
+    (seedpass_wide(total) ? seedpass_impl<KEY, SEGV, uint64_t>(__VA_ARGS__) : seedpass_impl<KEY, SEGV, uint32_t>(__VA_ARGS__))
+
 int seedpass_run(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, int mode, uint64_t mask, int extend,
                  const uint32_t *seg_dev, uint32_t nseg, int64_t *n_matches)
 {
@@ -2261,12 +2361,13 @@ int seedpass_run(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, int mode
     ctx->dev_rec_n = -1;
     if (n_matches) *n_matches = 0;
     if (total == 0) return MAUVE_OK;
-    if (seg_dev) return seedpass_impl<uint64_t, true>(ctx, gs, sh, tab, total, mode, mask, extend, -1, seg_dev, nseg, n_matches, nullptr, nullptr);
-    if (2 * sh.weight <= 32) return seedpass_impl<uint32_t, false>(ctx, gs, sh, tab, total, mode, mask, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
-    return seedpass_impl<uint64_t, false>(ctx, gs, sh, tab, total, mode, mask, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
+    if (seg_dev) return SEEDPASS_DISPATCH(uint64_t, true, ctx, gs, sh, tab, total, mode, mask, extend, -1, seg_dev, nseg, n_matches, nullptr, nullptr);
+    if (2 * sh.weight <= 32) return SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, mode, mask, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
+    return SEEDPASS_DISPATCH(uint64_t, false, ctx, gs, sh, tab, total, mode, mask, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
 }
 
-// extension + canonical order of hits a host-side finder supplies (records of 1 + nseq words: component set, values)
+// extension + canonical order of hits a host-side finder supplies (records of 1 + nseq words: component set, values -- global window
+// index | strand << 31, or local to the genome when seedpass_wide says so for the genome set: api.cpp builds them by the same rule)
 int seedpass_from_hits(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, const HostHits &hits, int extend, int64_t *n_matches)
 {
     SeedShape sh;
@@ -2280,7 +2381,7 @@ int seedpass_from_hits(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, co
     if (n_matches) *n_matches = 0;
     if (total == 0 || hits.n == 0) return MAUVE_OK;
     ctx->host_hits = &hits;
-    rc = seedpass_impl<uint32_t, false>(ctx, gs, sh, tab, total, MAUVE_MODE_MEM, 0, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
+    rc = SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, MAUVE_MODE_MEM, 0, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
     ctx->host_hits = nullptr;
     return rc;
 }
@@ -2297,8 +2398,8 @@ int seedpass_enumerate(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t pa
     q.n = 0; q.ns = 0;
     if (tab.nwin[seq] == 0) { if (q.start_off) q.start_off[0] = 0; return MAUVE_OK; }
     ctx->enum_req = &q;
-    if (2 * sh.weight <= 32) rc = seedpass_impl<uint32_t, false>(ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, nullptr, nullptr);
-    else rc = seedpass_impl<uint64_t, false>(ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, nullptr, nullptr);
+    if (2 * sh.weight <= 32) rc = SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, nullptr, nullptr);
+    else rc = SEEDPASS_DISPATCH(uint64_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, nullptr, nullptr);
     ctx->enum_req = nullptr;
     return rc;
 }
@@ -2315,11 +2416,12 @@ int seedpass_sorted_list(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t 
     *weight = sh.weight;
     keys->clear(); vals->clear();
     if (tab.nwin[seq] == 0) return MAUVE_OK;
-    if (2 * sh.weight <= 32) rc = seedpass_impl<uint32_t, false>(ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, keys, vals);
-    else rc = seedpass_impl<uint64_t, false>(ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, keys, vals);
+    if (2 * sh.weight <= 32) rc = SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, keys, vals);
+    else rc = SEEDPASS_DISPATCH(uint64_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, keys, vals);
     if (rc) return rc;
-    // vals carry global window indices; make them local to the genome
-    for (auto &v : *vals) v = ((v & 0x7fffffffu) - tab.gpos_off[seq]) | (v & 0x80000000u);
+    // vals carry global window indices; make them local to the genome (a wide pass hands them out local already)
+    if (!seedpass_wide(total))
+        for (auto &v : *vals) v = ((v & 0x7fffffffu) - tab.gpos_off[seq]) | (v & 0x80000000u);
     return MAUVE_OK;
 }
 
@@ -2349,24 +2451,24 @@ int seed_matches_to_host(mauve_ctx *ctx)
 //   rp_span_min : per genome, 4096 positions per workgroup: the window counts of the tile and its span-1 halo in LDS, each thread
 //                 the minimum over the covering windows of four consecutive positions (1 where none is valid), one 4-byte store
 // ------------------------------------------------------------------------------------------------
-template <typename KeyT>
-__global__ void __launch_bounds__(256) rp_count(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t n, GenomeTab tab,
+template <typename KeyT, typename ValT = uint32_t>
+__global__ void __launch_bounds__(256) rp_count(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n, GenomeTab tab,
                                                 uint8_t *__restrict__ wcnt)
 {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const KeyT k = keys[i];
-        const uint32_t w = vals[i] & 0x7fffffffu;
+        const uint32_t w = win_idx(vals[i]);
         if (k == (KeyT)~0ULL) { wcnt[w] = 0; continue; }
         const int g = genome_of(w, tab);
         const uint32_t lo = tab.gpos_off[g], hi = tab.gpos_off[g + 1];
         uint32_t c = 1;                                        // the walks stop at the saturation count: at most 254 steps each way
         for (uint32_t j = i; j > 0 && c < 255u; j--) {
-            const uint32_t v = vals[j - 1] & 0x7fffffffu;
+            const uint32_t v = win_idx(vals[j - 1]);
             if (keys[j - 1] != k || v < lo || v >= hi) break;
             c++;
         }
         for (uint32_t j = i + 1; j < n && c < 255u; j++) {
-            const uint32_t v = vals[j] & 0x7fffffffu;
+            const uint32_t v = win_idx(vals[j]);
             if (keys[j] != k || v < lo || v >= hi) break;
             c++;
         }
@@ -2412,34 +2514,35 @@ __global__ void __launch_bounds__(256) rp_span_min(const uint8_t *__restrict__ w
 }
 static_assert(RP_TILE == RS_TILE, "the multiplicity pass sorts with the histograms seed_extract_all leaves, tiled like the radix sort");
 
-template <typename KeyT>
+template <typename KeyT, typename ValT>
 static int rp_windows(mauve_ctx *c, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, uint32_t n)
 {
+    if (g_trace) fprintf(stderr, "[trace] multiplicity pass: %u windows, %s window index (%d-bit values)\n", n, sizeof(ValT) == 8 ? "wide" : "narrow", (int)sizeof(ValT) * 8);
     HIPCHK(c, c->keysA.ensure((size_t)n * sizeof(KeyT)));
     HIPCHK(c, c->keysB.ensure((size_t)n * sizeof(KeyT)));
-    HIPCHK(c, c->valsA.ensure((size_t)n * 4));
-    HIPCHK(c, c->valsB.ensure((size_t)n * 4));
+    HIPCHK(c, c->valsA.ensure((size_t)n * sizeof(ValT)));
+    HIPCHK(c, c->valsB.ensure((size_t)n * sizeof(ValT)));
     const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
     HIPCHK(c, c->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
-    KeyT *keys = c->keysA.as<KeyT>(); uint32_t *vals = c->valsA.as<uint32_t>();
+    KeyT *keys = c->keysA.as<KeyT>(); ValT *vals = c->valsA.as<ValT>();
     const uint64_t *packed = gs.buf->as<uint64_t>();
     const uint64_t *vmask = gs.vmask ? gs.vmask->as<uint64_t>() : nullptr;      // ambiguous bases
     const uint64_t *cmask = gs.cmask ? gs.cmask->as<uint64_t>() : nullptr;      // contig joins
     {
         KernelTimer t(c, MAUVE_K_EXTRACT, n);
         if (sh.span <= 32 && sh.weight <= 15)
-            hipLaunchKernelGGL((seed_extract_all<KeyT, false, true>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
+            hipLaunchKernelGGL((seed_extract_all<KeyT, false, true, ValT>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
                                c->hist.as<uint32_t>(), nblk, vmask, 0, cmask);
         else
-            hipLaunchKernelGGL((seed_extract_all<KeyT, false, false>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
+            hipLaunchKernelGGL((seed_extract_all<KeyT, false, false, ValT>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
                                c->hist.as<uint32_t>(), nblk, vmask, 0, cmask);
     }
     HIPCHK(c, hipGetLastError());
     // the mer bits only: an invalid window's all-ones key has ones there that no canonical mer has (min(F, R) is never all T),
     // so the invalid windows end the list
-    int rc = sort_pairs<KeyT>(c, n, 2 * sh.weight, &keys, &vals, c->keysB.as<KeyT>(), c->valsB.as<uint32_t>(), true);
+    int rc = sort_pairs<KeyT, ValT>(c, n, 2 * sh.weight, &keys, &vals, c->keysB.as<KeyT>(), c->valsB.as<ValT>(), true);
     if (rc) return rc;
-    hipLaunchKernelGGL(rp_count<KeyT>, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->cus * 16)), dim3(256), 0, c->stream, keys, vals, n, tab,
+    hipLaunchKernelGGL((rp_count<KeyT, ValT>), dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->cus * 16)), dim3(256), 0, c->stream, keys, vals, n, tab,
                        c->rp_wcnt.as<uint8_t>());
     HIPCHK(c, hipGetLastError());
     return MAUVE_OK;
@@ -2467,7 +2570,9 @@ int repeat_multiplicity(mauve_ctx *c, uint64_t pattern)
     HIPCHK(c, c->rp_mult.ensure(bytes + 16));
     HIPCHK(c, c->rp_wcnt.ensure((size_t)total + 16));
     if (total > 0) {
-        rc = 2 * sh.weight <= 32 ? rp_windows<uint32_t>(c, gs, sh, tab, (uint32_t)total) : rp_windows<uint64_t>(c, gs, sh, tab, (uint32_t)total);
+        const bool wide = seedpass_wide(total);
+        if (2 * sh.weight <= 32) rc = wide ? rp_windows<uint32_t, uint64_t>(c, gs, sh, tab, (uint32_t)total) : rp_windows<uint32_t, uint32_t>(c, gs, sh, tab, (uint32_t)total);
+        else rc = wide ? rp_windows<uint64_t, uint64_t>(c, gs, sh, tab, (uint32_t)total) : rp_windows<uint64_t, uint32_t>(c, gs, sh, tab, (uint32_t)total);
         if (rc) return rc;
     }
     if (maxlen > 0) {

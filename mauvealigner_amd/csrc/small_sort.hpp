@@ -47,23 +47,23 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total,
 // ever predicated off (all tiles but the last) -- the loads, ballots and stores compile without exec-mask branches.
 // hnext (small engine only): tile-major histogram of the next pass (digit at shift + 8, tiles of 1 << tile_log2 keys),
 // which every written key is added to; hbits: bits of a counter index there (8 + bits of the tile number).
-template <typename KeyT, int ITEMS, bool FULL>
-__device__ __forceinline__ void rs_scatter_tile(const KeyT *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
-                                                KeyT *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
-                                                uint32_t tile_base, uint32_t tile_n, int shift, KeyT *s_keys, uint32_t *s_vals,
+template <typename KeyT, int ITEMS, bool FULL, typename ValT = uint32_t>
+__device__ __forceinline__ void rs_scatter_tile(const KeyT *__restrict__ keys_in, const ValT *__restrict__ vals_in,
+                                                KeyT *__restrict__ keys_out, ValT *__restrict__ vals_out,
+                                                uint32_t tile_base, uint32_t tile_n, int shift, KeyT *s_keys, ValT *s_vals,
                                                 uint32_t (*wcount)[256], const uint32_t *gbase, uint32_t *tstart, uint32_t *scan,
                                                 uint32_t *__restrict__ hnext = nullptr, int tile_log2 = 0, int hbits = 0)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // load (wave-striped: wave w owns [w*64*ITEMS, (w+1)*64*ITEMS), item i of lane l is index i*64+l)
-    KeyT k[ITEMS]; uint32_t v[ITEMS]; uint32_t rank[ITEMS];
+    KeyT k[ITEMS]; ValT v[ITEMS]; uint32_t rank[ITEMS];
     const uint32_t wbase = wave * (64 * ITEMS);
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const uint32_t li = wbase + i * 64 + lane;
         const bool ok = FULL || li < tile_n;
         k[i] = ok ? keys_in[tile_base + li] : (KeyT)0;
-        v[i] = ok ? vals_in[tile_base + li] : 0u;
+        v[i] = ok ? vals_in[tile_base + li] : (ValT)0;
     }
     // wave-level multisplit ranking, stable in (i, lane) order.  peers = lanes of row i with the same digit, built
     // as two 32-bit halves from eight ballots (one 3-input bit op per half and bit).  The wave owns
@@ -170,15 +170,15 @@ __global__ void __launch_bounds__(RS_THREADS) rs_small_hist(const KeyT *__restri
 
 // one digit pass: hist = this pass's tile histograms (tile-major, nblk tiles); hnext: next pass's slot (added to), hzero: the
 // slot after it (this tile's row := 0); either may be null
-template <typename KeyT, int ITEMS>
-__global__ void __launch_bounds__(RS_THREADS) rs_small_scatter(const KeyT *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
-                                                               KeyT *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+template <typename KeyT, int ITEMS, typename ValT = uint32_t>
+__global__ void __launch_bounds__(RS_THREADS) rs_small_scatter(const KeyT *__restrict__ keys_in, const ValT *__restrict__ vals_in,
+                                                               KeyT *__restrict__ keys_out, ValT *__restrict__ vals_out,
                                                                uint32_t n, int shift, const uint32_t *__restrict__ hist, uint32_t nblk,
                                                                uint32_t *__restrict__ hnext, uint32_t *__restrict__ hzero, int hbits)
 {
     constexpr int TILE = RS_THREADS * ITEMS;
     __shared__ KeyT s_keys[TILE];
-    __shared__ uint32_t s_vals[TILE];
+    __shared__ ValT s_vals[TILE];
     __shared__ uint32_t wcount[RS_WAVES][256];
     __shared__ uint32_t gbase[256];       // global output index of this tile's first key of digit d
     __shared__ uint32_t tstart[256];      // tile-local start of digit d
@@ -208,15 +208,15 @@ __global__ void __launch_bounds__(RS_THREADS) rs_small_scatter(const KeyT *__res
     constexpr int LOG2 = ITEMS == 1 ? 8 : ITEMS == 2 ? 9 : ITEMS == 4 ? 10 : ITEMS == 8 ? 11 : 12;
     static_assert(TILE == 1 << LOG2, "ITEMS must be 1, 2, 4, 8 or 16");
     if (tile_n == (uint32_t)TILE)
-        rs_scatter_tile<KeyT, ITEMS, true>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase,
+        rs_scatter_tile<KeyT, ITEMS, true, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase,
                                            tstart, scan, hnext, LOG2, hbits);
     else
-        rs_scatter_tile<KeyT, ITEMS, false>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase,
+        rs_scatter_tile<KeyT, ITEMS, false, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase,
                                             tstart, scan, hnext, LOG2, hbits);
 }
 
-template <typename KeyT, int ITEMS, typename Book>
-inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT *kin, uint32_t *vin, KeyT *kout, uint32_t *vout,
+template <typename KeyT, int ITEMS, typename ValT, typename Book>
+inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT *kin, ValT *vin, KeyT *kout, ValT *vout,
                    uint32_t *ws, Book &book)
 {
     const uint32_t nblk = ss_tiles(n, ITEMS);
@@ -231,11 +231,11 @@ inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT 
         if (p == 0)
             book(false, [&] { hipLaunchKernelGGL((rs_small_hist<KeyT, ITEMS>), dim3(nblk), dim3(RS_THREADS), 0, st, kin, n, shift, h, hnext); });
         book(true, [&] {
-            hipLaunchKernelGGL((rs_small_scatter<KeyT, ITEMS>), dim3(nblk), dim3(RS_THREADS), 0, st, kin, vin, kout, vout, n, shift, h, nblk,
+            hipLaunchKernelGGL((rs_small_scatter<KeyT, ITEMS, ValT>), dim3(nblk), dim3(RS_THREADS), 0, st, kin, vin, kout, vout, n, shift, h, nblk,
                                hnext, hzero, hbits);
         });
         KeyT *tk = kin; kin = kout; kout = tk;
-        uint32_t *tv = vin; vin = vout; vout = tv;
+        ValT *tv = vin; vin = vout; vout = tv;
     }
 }
 
@@ -243,16 +243,16 @@ inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT 
 // point at the buffers holding the result (the alternates after an odd number of passes).  ws: ss_ws_words(n) words of
 // device memory, contents irrelevant.  book(scatter, launch): calls launch() once (a place to time it); scatter = false
 // for the histogram launch.
-template <typename KeyT, typename Book>
-inline void small_sort(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT **keys_io, uint32_t **vals_io, KeyT *keys_alt,
-                       uint32_t *vals_alt, uint32_t *ws, Book &&book)
+template <typename KeyT, typename ValT, typename Book>
+inline void small_sort(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT **keys_io, ValT **vals_io, KeyT *keys_alt,
+                       ValT *vals_alt, uint32_t *ws, Book &&book)
 {
-    KeyT *kin = *keys_io; uint32_t *vin = *vals_io;
+    KeyT *kin = *keys_io; ValT *vin = *vals_io;
     switch (ss_items(n)) {
-    case 1: ss_run<KeyT, 1>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    case 2: ss_run<KeyT, 2>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    case 4: ss_run<KeyT, 4>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    default: ss_run<KeyT, 8>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
+    case 1: ss_run<KeyT, 1, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
+    case 2: ss_run<KeyT, 2, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
+    case 4: ss_run<KeyT, 4, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
+    default: ss_run<KeyT, 8, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
     }
     const int passes = key_bits > shift_lo ? (key_bits - shift_lo + 7) / 8 : 0;
     if (passes & 1) { *keys_io = keys_alt; *vals_io = vals_alt; }
