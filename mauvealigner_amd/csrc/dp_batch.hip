@@ -6,15 +6,21 @@
 // every step is a 3-state affine-gap (Gotoh) DP of the current profile against the next sequence,
 // sum-of-pairs scores from per-column base counts, predecessor preference M > X > Y on ties.
 //
-// Mapping: the basic unit is one wave64 per interval (small intervals share a wave, dp_groups; the longest get a
-// 16-wave workgroup, dp_step_big -- same recurrence, different schedules).  The profile columns are the DP rows; the 64 lanes hold 64
-// consecutive rows and sweep the sequence as a systolic anti-diagonal wavefront: lane l works on
-// column j = t - l at step t, takes (i-1, j) from lane l-1 by a wave shuffle, (i-1, j-1) from what it
-// took one step earlier and (i, j-1) from its own registers.  Profiles longer than 64 columns run in
-// stripes; the last row of a stripe is parked in a per-interval HBM row buffer.  Traceback bytes are
-// written anti-diagonal-major (one coalesced 64-byte store per step), walked back by the wave, and
-// the new profile is rebuilt in forward order with ballot prefix counts.  Integer VALU + shuffle
-// bound, not HBM and not MFMA.
+// Mapping: the basic unit is one wave64 per interval; the profile columns are the DP rows.  Four schedules of the same
+// recurrence, each bit-identical to the others, in the order they appear below:
+//   stripe pipeline (dp_interval_mw, launched as dp_step_big): one row per lane, 64-row stripes swept as a systolic
+//     anti-diagonal wavefront (lane l works on column j = t - l at step t and takes (i-1, j) from lane l-1 by a DPP
+//     shift), the stripes pipelined over the 16 waves of a workgroup.  The only schedule with banded steps
+//     (DESIGN.md S7b), and the one that takes whatever the scans do not admit;
+//   register-blocked sweep (dp2_groups / dp2_interval, launched as dp_step2): four rows per lane; small intervals
+//     share a wave (4, 8 or 16 lanes each, everything of a step in LDS), larger ones get the wave to themselves;
+//   scan-formulated sweep (dp3_interval, inside dp_step2): a whole column or row per step, the dependent gap state
+//     by a wave-wide prefix maximum;
+//   wide sweep (dp_interval_wide, launched as dp_step_wide): the scan formulation over the waves of a workgroup, and
+//     over a cluster of workgroups for the largest intervals.
+// Profiles longer than a stripe / band park their boundary row in a per-interval HBM row buffer.  Traceback bytes
+// are walked back by the wave and the new profile is rebuilt in forward order with ballot prefix counts.  Integer
+// VALU + shuffle bound, not HBM and not MFMA.
 #include "common.hpp"
 #include "dev_scan.hpp"
 #include <algorithm>
@@ -23,9 +29,6 @@
 #include <cstdlib>
 
 #define DP_NEG_INF (-(1 << 29))
-constexpr int DP_LDS_TB = 8192;             // per wave: 128 systolic steps x 64 lanes.  With 12288 the LDS held dp_step to 3
-                                            // workgroups per CU; 8192 (and <= 128 VGPRs) gives 4 -- C3's DP stage 3.9 -> 2.4 ms
-constexpr int DP_LDS_OPS = 512;            // 4 groups x 128 reversed ops (dp_groups); >= 128 for the one-wave path
 
 struct DpMeta {
     int32_t m;        // current profile length
@@ -88,42 +91,11 @@ __device__ __forceinline__ int64_t dp_step_cells(int32_t m, int32_t n, bool band
     return acc;
 }
 
-// Kernel class of an interval from an ESTIMATE of its profile lengths: aligning a profile with one more sequence rarely
-// makes it much longer than the longest sequence so far, while the safe bound is the SUM of the lengths -- which puts
-// nearly every 5-way interval of ~20-base gaps into the one-wave class.  est(m) = min(bound, longest + longest / 8 + 2);
-// the kernels check the real lengths and fall back (dp_groups).  3: four per wave (rows <= 16), 2: two per wave
-// (rows <= 32), 1: a wave of its own.
-struct DpClassEst {
-    int64_t mbound = 0, longest = 0, rows = 0, steps = 0, nmax = 0; bool first = true;
-    int mode = 0;                     // 0: the estimate; 1: the safe bound (MAUVE_DP_CLASS=bound); 2: half the longest (=wild: tests the fallback)
-    __host__ __device__ void add(int64_t n)
-    {
-        if (n == 0) return;
-        if (first) { first = false; mbound = longest = n; return; }
-        int64_t e = mode == 1 ? mbound : (mode == 2 ? longest / 2 + 1 : longest + longest / 8 + 2);
-        if (e > mbound) e = mbound;
-        if (e > rows) rows = e;
-        if (e + n > steps) steps = e + n;
-        if (n > nmax) nmax = n;
-        mbound += n; if (n > longest) longest = n;
-    }
-    // systolic kernels (MAUVE_DP_OLD): 4: four per wave (rows <= 16), 3: two per wave (rows <= 32), 1: a wave of its own
-    __host__ __device__ int klass(int tmax) const { return steps <= tmax ? (rows <= 16 ? 4 : (rows <= 32 ? 3 : 1)) : 1; }
-    // register-blocked kernels: G lanes x 4 rows per interval, n + G steps in the LDS slice.  4: G = 4 (sixteen per wave),
-    // 3: G = 8, 2: G = 16, 1: a wave of its own
-    __host__ __device__ int klass2(int rows_per_lane, int tcap) const
-    {
-        if (rows <= 4 * rows_per_lane && nmax + 4 <= tcap) return 4;
-        if (rows <= 8 * rows_per_lane && nmax + 8 <= tcap) return 3;
-        if (rows <= 16 * rows_per_lane && nmax + 16 <= tcap) return 2;
-        return 1;
-    }
-};
-
-// lane l receives lane l-1's value; wave_shr1z: lane 0 receives 0 (its caller puts the real input there), wave_shr1: lane 0
-// keeps its own (gfx9 DPP wave_shr:1)
+// lane l receives lane l-1's value, lane 0 receives 0 (its caller puts the real input there) (gfx9 DPP wave_shr:1)
 __device__ __forceinline__ int32_t wave_shr1z(int32_t v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, true); }
-__device__ __forceinline__ int32_t wave_shr1(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+
+// lane l receives lane src_lane's value (ds_bpermute)
+__device__ __forceinline__ int32_t lane_read(int32_t v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
 
 // v with lane 0 replaced by the wave-uniform value x (v_writelane_b32; this compiler has no builtin for it)
 __device__ __forceinline__ int32_t lane0_set(int32_t v, int32_t x)
@@ -263,8 +235,8 @@ __device__ __forceinline__ void dp_stripe_round(DpStripe &S, int32_t c, int lane
 // The 64-row stripes of a long profile go round-robin to the waves and run as a software pipeline: stripe s
 // follows stripe s-1 three 64-step rounds behind, which is when the columns of the parked boundary row it is about to
 // consume (and the chunk it prefetches) are final.  Progress is published per wave in LDS between two barriers per
-// round; a wave whose dependency is not met sits the round out.  Same recurrences, same traceback bytes, same
-// results as the one-wave path -- only the schedule differs.
+// round; a wave whose dependency is not met sits the round out.  Same recurrences and tie rules, same results as
+// the one-wave kernels further down -- only the schedule differs.
 constexpr int DP_MW_LAG = 3;
 constexpr int DP_MW_WIN = 256;             // steps of traceback the walk keeps in LDS (16 KB)
 constexpr int DP_MW_WAVES = 16;            // 1024 threads: four waves per SIMD of one CU
@@ -362,7 +334,7 @@ __device__ void dp_interval_mw(int nseq, int64_t iv, const uint8_t *__restrict__
 
         // ---- traceback: every wave walks the same path (uniform control flow), wave 0 records it ----
         uint8_t *opr = ops + base;
-        // through a window in LDS that the whole workgroup refills (see the one-wave walker in dp_step)
+        // through a window in LDS that the whole workgroup refills (as the one-wave walker of dp2_interval does)
         int32_t ti = m, tj = n, len = 0, ws = -1, wj0 = 0, wlo = 0;
         while (ti > 0 || tj > 0) {
             uint32_t op, nstate;
@@ -416,159 +388,8 @@ __device__ void dp_interval_mw(int nseq, int64_t iv, const uint8_t *__restrict__
     if (threadIdx.x == 0) meta[iv] = mt;
 }
 
-
-// ---- small intervals: several per wave -------------------------------------------------------------------------
-// Most inter-anchor intervals of a closely related genome set are a handful of bases: a profile of m <= 16 rows
-// keeps 48 of a wave's 64 lanes idle in dp_step.  Here a wave is cut into 64/G groups of G lanes (G = 16 or 32) and
-// every group runs its own interval through the same systolic recurrence: the DPP wave shift still moves
-// (i-1, .) down the whole wave and each group's first lane overrides what it received with its own boundary row
-// (always the analytic first row: one stripe); the group leader's next base comes from the group's preloaded
-// chunk by ds_bpermute; traceback bytes and reversed ops live in the wave's LDS slice, cut per group; the
-// traceback walks are run by the group leaders side by side.  The step loop runs to the longest group of the wave
-// (the list is sorted by size, so neighbours are alike).  Same recurrences and tie rules as dp_stripe_round.
-constexpr int DP_GRP_TMAX = DP_LDS_TB / 64;        // 128 systolic steps, and m + n <= 128 ops, per group
-
-__device__ __forceinline__ int32_t lane_read(int32_t v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
-
-template <int G>
-__device__ void dp_groups(int nseq, const int64_t *__restrict__ list, int64_t first, int64_t count, int64_t wave_index, int64_t nwaves,
-                          const uint8_t *__restrict__ codes, const int64_t *__restrict__ seq_off, DpMeta *__restrict__ meta,
-                          uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA, uint32_t *__restrict__ cntB,
-                          uint32_t *__restrict__ maskB, uint8_t *s_tb_wave, uint8_t *s_ops_wave, const DpScoring &sc)
-{
-    constexpr int GROUPS = 64 / G;
-    constexpr uint64_t GMASK = G == 32 ? 0xffffffffULL : 0xffffULL;
-    const int lane = threadIdx.x & 63, ql = lane & (G - 1), q = lane / G, gbase = lane & ~(G - 1);
-    const bool leader = ql == 0;
-    const uint32_t below = (1u << ql) - 1u;                       // ql <= 31
-    uint8_t *tbq = s_tb_wave + q * (DP_GRP_TMAX * G);
-    uint8_t *opq = s_ops_wave + q * DP_GRP_TMAX;
-    for (int64_t li0 = wave_index * GROUPS; li0 < count; li0 += nwaves * GROUPS) {
-        const bool have = li0 + q < count;
-        const int64_t iv = have ? list[first + li0 + q] : 0;
-        DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
-        const int64_t base = have ? seq_off[iv * nseq] : 0;
-        // The class of an interval comes from an ESTIMATE of its profile lengths (dp_class_of): a group whose profile
-        // outgrows its G rows, or whose step outgrows the LDS slice, gives the interval up (mt.m = -1) and the wave
-        // runs it through the one-wave path afterwards (dp_step).
-        bool dead = false;
-        for (int g = 0; g < nseq; g++) {
-            int64_t so = 0; int32_t n = 0;
-            if (have && !dead) { so = seq_off[iv * nseq + g]; n = (int32_t)(seq_off[iv * nseq + g + 1] - so); }
-            if (n > 0 && mt.krows > 0 && (mt.m > G || mt.m + n > DP_GRP_TMAX)) { dead = true; n = 0; }
-            const uint8_t *seq = codes + so;
-            uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-            uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
-            const bool init = n > 0 && mt.krows == 0, step = n > 0 && mt.krows > 0;
-            if (init) for (int32_t c = ql; c < n; c += G) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
-            if (__ballot(step)) {
-                const int32_t m = step ? mt.m : 0, nn = step ? n : 0;
-                const int32_t i = ql + 1;
-                const bool active = i <= m;
-                const uint32_t cn = active ? Pc[i - 1] : 0u;
-                const int32_t c0 = cn & 255, c1 = (cn >> 8) & 255, c2 = (cn >> 16) & 255, c3 = cn >> 24;
-                const int32_t r = c0 + c1 + c2 + c3;
-                const int32_t sub0 = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-                const int32_t sub1 = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-                const int32_t sub2 = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-                const int32_t sub3 = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-                const int32_t gxo = sc.go * r, gxe = sc.ge * r, gyo = sc.go * mt.krows, gye = sc.ge * mt.krows;
-                const int32_t steps = step ? nn + m : 0;                   // t = 0 .. n + m - 1
-                int32_t tmax = 0;
-#pragma unroll
-                for (int k = 0; k < GROUPS; k++) tmax = max(tmax, __builtin_amdgcn_readlane(steps, k * G));
-                int32_t Mc = DP_NEG_INF, Xc = DP_NEG_INF, Yc = DP_NEG_INF, Md = DP_NEG_INF, Xd = DP_NEG_INF, Yd = DP_NEG_INF;
-                uint32_t bcur = 0;
-                // chunk k of the group's sequence: lane ql holds base k*G - 1 + ql (column t = k*G + ql reads base t-1)
-                auto chunk = [&](int32_t k) -> uint32_t { return nn > 0 ? (uint32_t)seq[min(max(k * G - 1 + ql, 0), nn - 1)] : 0u; };
-                uint32_t sq_cur = chunk(0), sq_nxt = chunk(1);
-                for (int32_t t = 0; t < tmax; t++) {
-                    if (t > 0 && (t & (G - 1)) == 0) { sq_cur = sq_nxt; sq_nxt = chunk(t / G + 1); }
-                    const int32_t j = t - ql;
-                    int32_t Mu = wave_shr1z(Mc), Xu = wave_shr1z(Xc), Yu = wave_shr1z(Yc);      // the leaders override what they receive
-                    uint32_t bnext = (uint32_t)wave_shr1z((int32_t)bcur);
-                    const uint32_t b0 = (uint32_t)lane_read((int32_t)sq_cur, gbase + (t & (G - 1)));
-                    const int32_t M0 = t == 0 ? 0 : DP_NEG_INF, Y0 = t == 0 ? DP_NEG_INF : gyo + (t - 1) * gye;
-                    Mu = leader ? M0 : Mu; Xu = leader ? DP_NEG_INF : Xu; Yu = leader ? Y0 : Yu; bnext = leader ? b0 : bnext;
-                    bcur = bnext;
-                    const bool on = active && (uint32_t)j <= (uint32_t)nn, j1 = j >= 1;
-                    int32_t best; uint32_t pm, px, py;
-                    max3(Md, Xd, Yd, best, pm);
-                    const int32_t sa = (bnext & 1) ? sub1 : sub0, sb = (bnext & 1) ? sub3 : sub2;
-                    int32_t Mn = max(best + ((bnext & 2) ? sb : sa), DP_NEG_INF);
-                    max3(Mu + gxo, Xu + gxe, Yu + gxo, best, px);
-                    const int32_t Xn = max(best, DP_NEG_INF);
-                    max3(Mc + gyo, Xc + gyo, Yc + gye, best, py);
-                    int32_t Yn = max(best, DP_NEG_INF);
-                    Mn = j1 ? Mn : DP_NEG_INF; Yn = j1 ? Yn : DP_NEG_INF; pm = j1 ? pm : 0u; py = j1 ? py : 0u;
-                    // straight-line: the slot (t, lane) is this lane's alone and is read only for real cells; the state moves
-                    // only where the lane has a cell, so the lane of row m ends up holding (m, n)
-                    tbq[t * G + ql] = (uint8_t)(pm | (px << 2) | (py << 4));
-                    Mc = on ? Mn : Mc; Xc = on ? Xn : Xc; Yc = on ? Yn : Yc;
-                    Md = Mu; Xd = Xu; Yd = Yu;
-                }
-                __threadfence_block();                       // traceback bytes: written by the lanes, read by the leader
-                const int owner = gbase + max(m, 1) - 1;
-                const int32_t fM = lane_read(Mc, owner), fX = lane_read(Xc, owner), fY = lane_read(Yc, owner);
-                int32_t best = fM; int state = 0;
-                if (fX > best) { best = fX; state = 1; }
-                if (fY > best) { best = fY; state = 2; }
-                // ---- traceback: the group leaders walk side by side ----
-                int32_t len = 0;
-                if (leader && step) {
-                    int32_t ti = m, tj = nn;
-                    while (ti > 0 || tj > 0) {
-                        uint32_t op, nstate;
-                        if (ti == 0) { op = 2; nstate = (tj == 1) ? 0 : 2; }
-                        else {
-                            const int32_t l = ti - 1;
-                            const uint8_t bt = tbq[(tj + l) * G + l];
-                            if (state == 0) { op = 3; nstate = bt & 3; }
-                            else if (state == 1) { op = 1; nstate = (bt >> 2) & 3; }
-                            else { op = 2; nstate = (bt >> 4) & 3; }
-                        }
-                        opq[len] = (uint8_t)op;
-                        len++;
-                        if (op & 1) ti--;
-                        if (op & 2) tj--;
-                        state = (int)nstate;
-                    }
-                }
-                __threadfence_block();
-                len = lane_read(len, gbase);
-                int32_t maxlen = 0;
-#pragma unroll
-                for (int k = 0; k < GROUPS; k++) maxlen = max(maxlen, __builtin_amdgcn_readlane(len, k * G));
-                // ---- new profile in forward order, per group ----
-                int32_t carry_p = 0, carry_s = 0;
-                for (int32_t c0i = 0; c0i < maxlen; c0i += G) {
-                    const int32_t c = c0i + ql;
-                    const bool ok = step && c < len;
-                    const uint32_t op = ok ? opq[len - 1 - c] : 0u;
-                    const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
-                    const uint32_t gp = (uint32_t)((bp >> gbase) & GMASK), gs = (uint32_t)((bs >> gbase) & GMASK);
-                    if (ok) {
-                        const int32_t pi = carry_p + (int32_t)__popc(gp & below), sj = carry_s + (int32_t)__popc(gs & below);
-                        uint32_t cv = 0, mv = 0;
-                        if (op & 1) { cv = Pc[pi]; mv = Pm[pi]; }
-                        if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
-                        Qc[c] = cv; Qm[c] = mv;
-                    }
-                    carry_p += (int32_t)__popc(gp); carry_s += (int32_t)__popc(gs);
-                }
-                if (step) { mt.cells += (int64_t)m * nn; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1; }
-            }
-            if (init) { mt.m = n; mt.krows = 1; }
-            __threadfence_block();       // profiles written by some lanes are read by others in the next step
-        }
-        if (dead) mt.m = -1;
-        if (have && leader) meta[iv] = mt;
-    }
-}
-
-
 // ================================================================================================================
-// Register-blocked sweep.  The systolic kernels above give every lane ONE profile row: a step costs ~75 instructions
+// Register-blocked sweep.  The stripe pipeline above gives every lane ONE profile row: a step costs ~75 instructions
 // whatever the lane does with it, a profile of m rows against n bases takes m + n steps, and most inter-anchor
 // intervals are a handful of bases (most lanes of the wave idle in the skew).  Here a lane owns R consecutive rows: it
 // takes (i0-1, j) and (i0-1, j-1) from the lane above once per step (three DPP shifts, not three per row) and runs
@@ -937,146 +758,6 @@ __device__ void dp2_interval(int nseq, int64_t iv, const uint8_t *__restrict__ c
 
 struct DpClasses { int64_t first_med, n_med, first_c, n_c, first_s32, n_s32, first_s16, n_s16; uint32_t blocks_med, blocks_c, blocks_s32; int32_t scan; };   // list = [big | one wave | G = 16 | s32 (G = 8) | s16 (G = 4)]
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) dp_step(int nseq, const int64_t *__restrict__ list, DpClasses cl, const uint8_t *__restrict__ codes,
-                                               const int64_t *__restrict__ seq_off, DpMeta *__restrict__ meta,
-                                               uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA,
-                                               uint32_t *__restrict__ cntB, uint32_t *__restrict__ maskB,
-                                               uint8_t *__restrict__ tb, const int64_t *__restrict__ tb_off,
-                                               int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
-                                               uint8_t *__restrict__ ops, DpScoring sc)
-{
-    // Small steps (one stripe, m + n <= 128) keep their traceback bytes and reversed ops in LDS: the traceback
-    // walk is a chain of dependent 1-byte loads, ~100 cycles each from LDS against >1000 from L2/HBM.
-    __shared__ __attribute__((aligned(16))) uint8_t s_tb[4][DP_LDS_TB];
-    __shared__ uint8_t s_ops[4][DP_LDS_OPS];
-    // The list is [dp_step_big's entries | one-wave | two per wave (m <= 32) | four per wave (m <= 16)], each class
-    // largest first; the block ranges follow the same order so the long ones start first.
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int per = 1; bool only_failed = false;
-    int64_t pos0, pstep, pend;
-    if (blockIdx.x >= cl.blocks_med) {
-        const bool s32 = blockIdx.x < cl.blocks_med + cl.blocks_s32;
-        const uint32_t b0 = s32 ? cl.blocks_med : cl.blocks_med + cl.blocks_s32;
-        const uint32_t nb = s32 ? cl.blocks_s32 : gridDim.x - cl.blocks_med - cl.blocks_s32;
-        const int64_t widx = (int64_t)(blockIdx.x - b0) * 4 + wv, nw = (int64_t)nb * 4;
-        if (s32) dp_groups<32>(nseq, list, cl.first_s32, cl.n_s32, widx, nw, codes, seq_off, meta, cntA, maskA, cntB, maskB, s_tb[wv], s_ops[wv], sc);
-        else dp_groups<16>(nseq, list, cl.first_s16, cl.n_s16, widx, nw, codes, seq_off, meta, cntA, maskA, cntB, maskB, s_tb[wv], s_ops[wv], sc);
-        // second look at this wave's own list positions: what a group gave up is aligned below, one interval per wave
-        per = s32 ? 2 : 4; only_failed = true;
-        pos0 = (s32 ? cl.first_s32 : cl.first_s16) + widx * per; pstep = nw * per; pend = (s32 ? cl.first_s32 + cl.n_s32 : cl.first_s16 + cl.n_s16);
-        __threadfence_block();
-    } else {
-        pos0 = cl.first_med + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6); pstep = ((int64_t)cl.blocks_med * blockDim.x) >> 6;
-        pend = cl.first_med + cl.n_med;
-    }
-    const uint64_t lt = lane ? (~0ULL >> (64 - lane)) : 0ULL;
-
-    for (int64_t lb = pos0; lb < pend; lb += pstep)
-    for (int q = 0; q < per && lb + q < pend; q++) {
-      const int64_t iv = list[lb + q];
-      if (only_failed && meta[iv].m != -1) continue;
-      // all progressive steps of one interval run back to back in this wave (they only depend on each other)
-      DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
-      const int64_t base = seq_off[iv * nseq];
-      for (int g = 0; g < nseq; g++) {
-        const int64_t so = seq_off[iv * nseq + g];
-        const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
-        if (n == 0) continue;
-        const uint8_t *seq = codes + so;
-        uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-        uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
-        if (mt.krows == 0) {           // first non-empty sequence becomes the profile
-            for (int32_t c = lane; c < n; c += 64) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
-            mt.m = n; mt.krows = 1;
-            __threadfence_block();      // the next step's lanes read what other lanes just wrote
-            continue;
-        }
-        const int32_t m = mt.m;
-        const int32_t T = n + 64;                          // traceback stride per stripe (steps)
-        const bool in_lds = m <= 64 && (size_t)(m + n) * 64 <= DP_LDS_TB && m + n <= DP_LDS_OPS;
-        uint8_t *tbp = in_lds ? s_tb[wv] : tb + tb_off[iv];
-        int32_t *rowbuf = rows + rows_off[iv];             // 2 x 3 x (n+1)
-        const int32_t nstripes = (m + 63) / 64;
-        int32_t fM = DP_NEG_INF, fX = DP_NEG_INF, fY = DP_NEG_INF;   // values at (m, n)
-
-        for (int32_t s = 0; s < nstripes; s++) {
-            DpStripe S;
-            dp_stripe_begin<false>(S, s, lane, m, n, nstripes, Pc, seq, sc, mt.krows, rowbuf, tbp, T);
-            const int32_t nrounds = (S.steps + 63) / 64;
-            for (int32_t c = 0; c < nrounds; c++) dp_stripe_round<false>(S, c, lane);
-            __threadfence_block();   // the parked row / traceback bytes are read back by this wave
-            if (s == nstripes - 1) { fM = S.Mc; fX = S.Xc; fY = S.Yc; }      // the lane of row m holds (m, n)
-        }
-        // result lives in the lane that owns row m
-        const int owner = (m - 1) & 63;
-        fM = __shfl(fM, owner); fX = __shfl(fX, owner); fY = __shfl(fY, owner);
-        int32_t best = fM; int state = 0;
-        if (fX > best) { best = fX; state = 1; }
-        if (fY > best) { best = fY; state = 2; }
-
-        // ---- traceback (wave-uniform walk; bytes were written by this wave) ----
-        uint8_t *opr = in_lds ? s_ops[wv] : ops + base;   // reversed ops, capacity m + n
-        // A step whose traceback went to global memory is walked through a window in the wave's LDS slice: the walk is a
-        // chain of dependent one-byte loads (m + n of them), so each would pay a full L2 round trip; inside a stripe the
-        // step index t = tj + l only falls (by 1 or 2 per op), so the DP_LDS_TB / 64 steps below the current one are
-        // fetched at once with 16-byte loads and serve at least half as many ops.
-        int32_t ti = m, tj = n, len = 0, ws = -1, wlo = 0;
-        uint8_t *win = s_tb[wv];
-        while (ti > 0 || tj > 0) {
-            uint32_t op, nstate;
-            if (ti == 0) { op = 2; nstate = (tj == 1) ? 0 : 2; }
-            else {
-                const int32_t s = (ti - 1) >> 6, l = (ti - 1) & 63;
-                const int32_t t = tj + l;
-                uint8_t bt;
-                if (in_lds) bt = win[(size_t)t * 64 + l];
-                else {
-                    if (s != ws || t < wlo) {
-                        ws = s; wlo = max(0, t - (DP_LDS_TB / 64 - 1));
-                        const uint8_t *src = tbp + ((size_t)s * T + wlo) * 64;
-                        const int32_t nbytes = (t - wlo + 1) * 64;
-                        for (int32_t o = lane * 16; o < nbytes; o += 1024)
-                            *reinterpret_cast<uint4 *>(win + o) = *reinterpret_cast<const uint4 *>(src + o);
-                        __threadfence_block();             // the window is read by every lane
-                    }
-                    bt = win[(size_t)(t - wlo) * 64 + l];
-                }
-                if (state == 0) { op = 3; nstate = bt & 3; }
-                else if (state == 1) { op = 1; nstate = (bt >> 2) & 3; }
-                else { op = 2; nstate = (bt >> 4) & 3; }
-            }
-            if (lane == 0) opr[len] = (uint8_t)op;
-            len++;
-            if (op & 1) ti--;
-            if (op & 2) tj--;
-            state = (int)nstate;
-        }
-        __threadfence_block();
-        // ---- new profile in forward order: ballot prefix counts give each column its sources ----
-        int32_t carry_p = 0, carry_s = 0;
-        for (int32_t c0i = 0; c0i < len; c0i += 64) {
-            const int32_t c = c0i + lane;
-            const bool ok = c < len;
-            const uint32_t op = ok ? opr[len - 1 - c] : 0u;
-            const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
-            if (ok) {
-                const int32_t pi = carry_p + (int32_t)__popcll(bp & lt), sj = carry_s + (int32_t)__popcll(bs & lt);
-                uint32_t cv = 0, mv = 0;
-                if (op & 1) { cv = Pc[pi]; mv = Pm[pi]; }
-                if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
-                Qc[c] = cv; Qm[c] = mv;
-            }
-            carry_p += (int32_t)__popcll(bp); carry_s += (int32_t)__popcll(bs);
-        }
-        mt.cells += (int64_t)m * n; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1;
-        __threadfence_block();
-      }
-      if (lane == 0) meta[iv] = mt;
-    }
-}
-
-
-
 // ================================================================================================================
 // Scan-formulated sweep (one wave per interval).  An anti-diagonal schedule needs m + n dependent steps whatever the
 // lanes do; the recurrence itself does not: only ONE of the two gap states depends on the cell computed just before
@@ -1089,7 +770,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
 // 105 stripes of 84 anti-diagonals.  Orientation B is the mirror image for a short profile against a long sequence:
 // columns on the lanes, row by row, Y the scanned state.  The orientation is chosen per progressive step by cost.
 // Values, tie rules (the first of M, X, Y that attains the maximum, found by comparing the unclamped candidates) and
-// the clamp at -2^29 are those of the systolic kernels: max is associative, the sums are exact in 32 bits for every
+// the clamp at -2^29 are those of the anti-diagonal sweeps above: max is associative, the sums are exact in 32 bits for every
 // interval the host admits here (dp3_admissible), so the traceback bytes of every reachable cell are identical.
 // ================================================================================================================
 template <int CTRL, int RM> __device__ __forceinline__ int32_t dpp_keep(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, RM, 0xf, false); }
@@ -1434,7 +1115,7 @@ __device__ __forceinline__ void dp3_sweep_b(int lane, int32_t m, int32_t n, cons
 #pragma unroll
         for (int r = 0; r < R; r++) {
             L.bases |= (uint32_t)(j0 + r < n ? seq[j0 + r] : 0) << (2 * r);
-            // row 0: only Y exists (analytic, not clamped: the systolic kernels' boundary row)
+            // row 0: only Y exists (analytic, not clamped: the anti-diagonal sweeps' boundary row)
             L.M[r] = DP_NEG_INF; L.X[r] = DP_NEG_INF; L.Y[r] = gyo + (j0 + r) * gye;
         }
         L.E = (lane + 1) * R * gye;
@@ -2303,6 +1984,59 @@ __global__ void __launch_bounds__(256) dp_gather_codes(const uint64_t *__restric
     }
 }
 
+// The sizing rule: what one interval needs and where it runs, from the lengths of its sequences alone.  Host sizing (dp_core) and
+// the device front end (dpf_desc, dpf_size_desc) both feed it with add(n) per sequence in genome order, and the kernels trust the
+// traceback and parked-row offsets made from its figures -- so there is one copy of it.  While the members go by, the profile is at
+// least as long as its longest member (mmin) and at most as long as their sum (mmax).
+//   need     traceback bytes: the worst step under those bounds, whichever kernel family runs the interval
+//   rows()   parked-row entries
+//   est      scan steps ONE wave would spend on it, from an ESTIMATE of the profile lengths: aligning a profile with one more sequence
+//            rarely makes it much longer than the longest sequence so far, e = min(mmax, mmin + mmin / 8 + 2)
+//   cand()   1: a step has several bands in one dimension, so it may get a workgroup (DpBigPick decides); 2: banded, it must
+//   cls()    sub-wave class of the register-blocked kernels, G lanes x DP2_R rows per interval and n + G steps in the LDS slice --
+//            4: G = 4 (sixteen per wave), 3: G = 8, 2: G = 16, 1: a wave of its own.  From the same estimate: the safe bound (the SUM
+//            of the lengths) would put nearly every 5-way interval of ~20-base gaps into the one-wave class; the kernels check the
+//            real lengths and fall back (dp2_groups).  class_mode 1: the safe bound (MAUVE_DP_CLASS=bound); 2: half the longest
+//            (=wild: tests the fallback)
+//   sizekey() launch order, largest traceback footprint first: 63 - floor(log2(need))
+struct DpSizing {
+    int64_t need = 0, est = 0;
+    __host__ __device__ DpSizing(int64_t band_from, bool no_mw_, bool no_groups_, int class_mode, int64_t longest)
+        : banded(longest > band_from), no_mw(no_mw_), no_groups(no_groups_), mode(class_mode) {}
+    __host__ __device__ void add(int64_t n)
+    {
+        if (n == 0) return;
+        if (first) { first = false; mmax = mmin = n; return; }
+        const int64_t tbo = dp_tb_need(mmin, mmax, n, banded);
+        const int64_t tbn = banded ? tbo : max2(tbo, max2(dp2_tb_need(mmax, n), dp3_tb_need(mmax, n)));
+        rneed = max2(rneed, dp3_rows_need(mmax, n));
+        need = max2(need, tbn);
+        nmax = max2(nmax, n);
+        const int64_t e_m = min2(mmax, mmin + mmin / 8 + 2);
+        if (max2(e_m, n) > DP3_BAND && !no_mw) wide = true;
+        est += dp3_scan_steps(e_m, n);
+        crows = max2(crows, mode == 0 ? e_m : min2(mmax, mode == 1 ? mmax : mmin / 2 + 1));
+        mmax += n; mmin = max2(mmin, n);
+    }
+    __host__ __device__ int64_t rows() const { return max2(6 * (nmax + 1), rneed); }
+    __host__ __device__ uint8_t cand() const { return banded && nmax ? 2 : (wide ? 1 : 0); }     // (banded steps exist only in the workgroup kernel)
+    __host__ __device__ uint8_t cls() const
+    {
+        if (no_groups || banded) return 1;
+        if (crows <= 4 * DP2_R && nmax + 4 <= DP2_T) return 4;
+        if (crows <= 8 * DP2_R && nmax + 8 <= DP2_T) return 3;
+        if (crows <= 16 * DP2_R && nmax + 16 <= DP2_T) return 2;
+        return 1;
+    }
+    __host__ __device__ static uint32_t sizekey(int64_t need) { int c = 0; for (int64_t f = need; f > 1; f >>= 1) c++; return (uint32_t)(63 - c); }
+    __host__ __device__ uint32_t sizekey() const { return sizekey(need); }
+private:
+    __host__ __device__ static int64_t max2(int64_t a, int64_t b) { return a > b ? a : b; }
+    __host__ __device__ static int64_t min2(int64_t a, int64_t b) { return a < b ? a : b; }
+    bool banded, no_mw, no_groups, wide = false, first = true; int mode;
+    int64_t mmin = 0, mmax = 0, nmax = 0, rneed = 0, crows = 0;       // crows: the longest profile the class estimate expects
+};
+
 // Which intervals get a workgroup (dp_step_big) instead of a wave: candidates (a step with several bands) whose single-wave estimate is
 // at least MAUVE_DP_WIDE_MIN scan steps, at most MAUVE_DP_BIG_MAX of them.
 static int dp_class_mode()
@@ -2310,13 +2044,12 @@ static int dp_class_mode()
     static const int m = []() { const char *e = getenv("MAUVE_DP_CLASS"); return !e ? 0 : (!strcmp(e, "bound") ? 1 : (!strcmp(e, "wild") ? 2 : 0)); }();
     return m;
 }
-static bool dp_old_kernels() { static const bool o = getenv("MAUVE_DP_OLD") != nullptr; return o; }   // A/B switch: the systolic one-row-per-lane kernels
 static int64_t dp_wide_min() { static const int64_t f = getenv("MAUVE_DP_WIDE_MIN") ? atoll(getenv("MAUVE_DP_WIDE_MIN")) : 1024; return f; }
 static int64_t dp_big_max() { static const int64_t m = getenv("MAUVE_DP_BIG_MAX") ? atoll(getenv("MAUVE_DP_BIG_MAX")) : 256; return m; }
-static bool dp_wide_on() { static const bool o = getenv("MAUVE_DP_NO_WIDE") == nullptr; return o; }   // A/B switch: the workgroup entries all through the systolic stripe pipeline
+static bool dp_wide_on() { static const bool o = getenv("MAUVE_DP_NO_WIDE") == nullptr; return o; }   // A/B switch: the workgroup entries all through the stripe pipeline
 
-// the two DP launches: dp_step_big (workgroup per interval, second stream) beside dp_step (wave / sub-wave per interval),
-// over the positions [a, b) of the launch list [workgroup | one wave | two per wave | four per wave]; tb_base is
+// the DP launches: the workgroup-per-interval kernels (dp_step_wide, dp_step_big) beside dp_step2 (wave / sub-wave per interval),
+// over the positions [a, b) of the launch list [workgroup | one wave | G = 16 | G = 8 | G = 4]; tb_base is
 // subtracted from the traceback offsets (rounds, below)
 static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64_t n_big, const DpClasses &full, const int64_t *d_seq_off,
                            const int64_t *d_tb_off, const int64_t *d_rows_off, const DpScoring &sc, int64_t tb_base, int64_t band_from)
@@ -2329,17 +2062,20 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
     clip(full.first_c, full.n_c, cl.first_c, cl.n_c);
     clip(full.first_s32, full.n_s32, cl.first_s32, cl.n_s32);
     clip(full.first_s16, full.n_s16, cl.first_s16, cl.n_s16);
-    const bool oldk = dp_old_kernels();
     static const bool no_scan = getenv("MAUVE_DP_NOSCAN") != nullptr;     // A/B switch: anti-diagonal sweep for the one-wave class too
     cl.scan = no_scan ? 0 : 1;
-    // intervals per workgroup: systolic kernels 4 waves x {1, 2, 4}; register-blocked kernels 2 waves x {1, 4, 8, 16}
-    const int64_t wpb = oldk ? 4 : DP2_WAVES, cap = oldk ? 256 * 8 : 256 * 16;
+    // intervals per workgroup: DP2_WAVES waves x {1, 4, 8, 16}
+    const int64_t wpb = DP2_WAVES, cap = 256 * 16;
     cl.blocks_med = (uint32_t)std::min<int64_t>((cl.n_med + wpb - 1) / wpb, cap);
     cl.blocks_c = (uint32_t)std::min<int64_t>((cl.n_c + 4 * wpb - 1) / (4 * wpb), cap);
-    cl.blocks_s32 = (uint32_t)std::min<int64_t>(oldk ? (cl.n_s32 + 7) / 8 : (cl.n_s32 + 8 * wpb - 1) / (8 * wpb), cap);
-    const uint32_t blocks = cl.blocks_med + cl.blocks_c + cl.blocks_s32 + (uint32_t)std::min<int64_t>(oldk ? (cl.n_s16 + 15) / 16 : (cl.n_s16 + 16 * wpb - 1) / (16 * wpb), cap);
+    cl.blocks_s32 = (uint32_t)std::min<int64_t>((cl.n_s32 + 8 * wpb - 1) / (8 * wpb), cap);
+    const uint32_t blocks = cl.blocks_med + cl.blocks_c + cl.blocks_s32 + (uint32_t)std::min<int64_t>((cl.n_s16 + 16 * wpb - 1) / (16 * wpb), cap);
     uint8_t *tb = ctx->dp_tb.as<uint8_t>() - tb_base;                   // only offsets >= tb_base are used in this round
-    KernelTimer t(ctx, MAUVE_K_DP, b - a);
+    KernelTimer t(ctx, MAUVE_K_DP, b - a);                              // (the profile calls this timer "dp_step": it names the stage, all launches below)
+    // what every DP kernel takes behind its list: the bases, the per-interval records, both profile buffers, traceback, parked rows, reversed ops, scores
+#define DP_STEP_ARGS ctx->dp_codes.as<uint8_t>(), d_seq_off, ctx->dp_meta.as<DpMeta>(), ctx->dp_prof_cnt.as<uint32_t>(), ctx->dp_prof_mask.as<uint32_t>(), \
+                     ctx->dp_prof2_cnt.as<uint32_t>(), ctx->dp_prof2_mask.as<uint32_t>(), tb, d_tb_off, ctx->dp_rows.as<int32_t>(), d_rows_off, \
+                     ctx->dp_score.as<uint8_t>(), sc
     // The workgroup-per-interval launches run beside the one-wave launch; THEY go first, on the main stream, and the one-wave launch follows on the
     // second stream behind an event: a two-wave workgroup of dp_step2 takes a quarter of a CU's LDS and registers, four of them leave room for
     // nothing else, and every slot one of them frees is refilled by the next -- a 1024-thread workgroup dispatched after them waits until that
@@ -2364,33 +2100,17 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
             flags = ctx->dp_wflags.as<unsigned long long>();
         }
 #define DPW_LAUNCH(RR, WW, first, count, K) hipLaunchKernelGGL((dp_step_wide<RR, WW>), dim3((uint32_t)((count) * (K))), dim3(64 * WW), 0, ctx->stream, nseq, \
-                               ctx->dp_list.as<int64_t>() + bf + (first), ctx->dp_codes.as<uint8_t>(), d_seq_off, ctx->dp_meta.as<DpMeta>(), \
-                               ctx->dp_prof_cnt.as<uint32_t>(), ctx->dp_prof_mask.as<uint32_t>(), ctx->dp_prof2_cnt.as<uint32_t>(), \
-                               ctx->dp_prof2_mask.as<uint32_t>(), tb, d_tb_off, ctx->dp_rows.as<int32_t>(), \
-                               d_rows_off, ctx->dp_score.as<uint8_t>(), sc, band_from, (int)(K), flags)
+                               ctx->dp_list.as<int64_t>() + bf + (first), DP_STEP_ARGS, band_from, (int)(K), flags)
         if (wide && r4) { if (n_cl) DPW_LAUNCH(4, 8, 0, n_cl, DPW_KMAX); if (bn > n_cl) DPW_LAUNCH(4, 8, n_cl, bn - n_cl, 1); }
         else if (wide) { if (n_cl) DPW_LAUNCH(2, 16, 0, n_cl, DPW_KMAX); if (bn > n_cl) DPW_LAUNCH(2, 16, n_cl, bn - n_cl, 1); }
 #undef DPW_LAUNCH
         // (the stripe pipeline: every entry without the wide sweep; with it, only where banded intervals or an inadmissible scoring scheme can occur)
         if (!wide || band_from != INT64_MAX || !dp3_admissible(1, nseq, sc.ge, sc.go))
-            hipLaunchKernelGGL(dp_step_big, dim3((uint32_t)bn), dim3(64 * DP_MW_WAVES), 0, ctx->stream, nseq,
-                               ctx->dp_list.as<int64_t>() + bf, ctx->dp_codes.as<uint8_t>(), d_seq_off, ctx->dp_meta.as<DpMeta>(),
-                               ctx->dp_prof_cnt.as<uint32_t>(), ctx->dp_prof_mask.as<uint32_t>(), ctx->dp_prof2_cnt.as<uint32_t>(),
-                               ctx->dp_prof2_mask.as<uint32_t>(), tb, d_tb_off, ctx->dp_rows.as<int32_t>(),
-                               d_rows_off, ctx->dp_score.as<uint8_t>(), sc, band_from, wide ? 1 : 0);
+            hipLaunchKernelGGL(dp_step_big, dim3((uint32_t)bn), dim3(64 * DP_MW_WAVES), 0, ctx->stream, nseq, ctx->dp_list.as<int64_t>() + bf, DP_STEP_ARGS,
+                               band_from, wide ? 1 : 0);
     }
-    if (blocks && oldk)
-        hipLaunchKernelGGL(dp_step, dim3(blocks), dim3(256), 0, small_stream, nseq, ctx->dp_list.as<int64_t>(), cl,
-                           ctx->dp_codes.as<uint8_t>(), d_seq_off, ctx->dp_meta.as<DpMeta>(), ctx->dp_prof_cnt.as<uint32_t>(),
-                           ctx->dp_prof_mask.as<uint32_t>(), ctx->dp_prof2_cnt.as<uint32_t>(),
-                           ctx->dp_prof2_mask.as<uint32_t>(), tb, d_tb_off, ctx->dp_rows.as<int32_t>(),
-                           d_rows_off, ctx->dp_score.as<uint8_t>(), sc);
-    else if (blocks)
-        hipLaunchKernelGGL(dp_step2, dim3(blocks), dim3(64 * DP2_WAVES), 0, small_stream, nseq, ctx->dp_list.as<int64_t>(), cl,
-                           ctx->dp_codes.as<uint8_t>(), d_seq_off, ctx->dp_meta.as<DpMeta>(), ctx->dp_prof_cnt.as<uint32_t>(),
-                           ctx->dp_prof_mask.as<uint32_t>(), ctx->dp_prof2_cnt.as<uint32_t>(),
-                           ctx->dp_prof2_mask.as<uint32_t>(), tb, d_tb_off, ctx->dp_rows.as<int32_t>(),
-                           d_rows_off, ctx->dp_score.as<uint8_t>(), sc);
+    if (blocks) hipLaunchKernelGGL(dp_step2, dim3(blocks), dim3(64 * DP2_WAVES), 0, small_stream, nseq, ctx->dp_list.as<int64_t>(), cl, DP_STEP_ARGS);
+#undef DP_STEP_ARGS
     if (bn) { HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2)); HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0)); }
     return MAUVE_OK;
 }
@@ -2425,6 +2145,37 @@ static int dp_launch_rounds(mauve_ctx *ctx, int nseq, int64_t n_iv, int64_t n_bi
     return MAUVE_OK;
 }
 
+// ---- what dp_core and the device front end both do around the launches ----
+static const char *const DP_ERR_CLUSTER = "dp: a cluster of workgroups could not make progress on an interval (wide sweep)";
+static DpScoring dp_scoring_of(const mauve_scoring *scoring)
+{
+    DpScoring sc; sc.go = scoring->gap_open; sc.ge = scoring->gap_extend; memcpy(sc.s, scoring->matrix, sizeof sc.s);
+    return sc;
+}
+// the buffers sized by the batch's totals: bases, traceback bytes (one round's worth at most), parked-row entries
+static int dp_ensure_batch(mauve_ctx *ctx, int64_t total, int64_t tbt, int64_t rwt)
+{
+    HIPCHK(ctx, ctx->dp_codes.ensure((size_t)total + 16));
+    HIPCHK(ctx, ctx->dp_prof_cnt.ensure((size_t)(total + 1) * 4));
+    HIPCHK(ctx, ctx->dp_prof_mask.ensure((size_t)(total + 1) * 4));
+    HIPCHK(ctx, ctx->dp_prof2_cnt.ensure((size_t)(total + 1) * 4));
+    HIPCHK(ctx, ctx->dp_prof2_mask.ensure((size_t)(total + 1) * 4));
+    HIPCHK(ctx, ctx->dp_tb.ensure((size_t)std::min<int64_t>(tbt, dp_tb_budget()) + 64));
+    HIPCHK(ctx, ctx->dp_rows.ensure((size_t)(rwt + 1) * 4));
+    HIPCHK(ctx, ctx->dp_score.ensure((size_t)total + 16));           // reversed-ops scratch
+    HIPCHK(ctx, ctx->dp_cols.ensure((size_t)(total + 1) * 4));
+    return MAUVE_OK;
+}
+// dp_codes from the nd descriptors in dp_desc (device) and their offsets
+static void dp_launch_gather_codes(mauve_ctx *ctx, const int64_t *d_seq_off, int64_t nd)
+{
+    DpGenomeWords gw; memset(&gw, 0, sizeof gw);
+    for (int g = 0; g < ctx->nseq; g++) gw.word_off[g] = ctx->word_off[g];
+    const uint32_t gb = (uint32_t)std::min<int64_t>((nd + 15) / 16, 256 * 8);
+    hipLaunchKernelGGL(dp_gather_codes, dim3(gb), dim3(256), 0, ctx->stream, ctx->genomes.as<uint64_t>(), gw, ctx->dp_desc.as<DpSeqDesc>(), d_seq_off, nd,
+                       ctx->dp_codes.as<uint8_t>());
+}
+
 // shared core: seq_off is a host array; the codes are either uploaded from `codes` or gathered from `desc`
 static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes, const DpSeqDesc *desc,
                    const int64_t *seq_off, const mauve_scoring *scoring, uint32_t *cols, int64_t *col_off,
@@ -2436,7 +2187,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     static const bool trace = getenv("MAUVE_TRACE") != nullptr;
     const double td0 = now_ms();
     const int64_t total = seq_off[n_iv * nseq];
-    // per-interval scratch: traceback (worst profile length before each step) and parked rows
+    // per-interval scratch: traceback and parked rows (DpSizing)
     mauve_ctx::DpHost &H = ctx->dph;
     std::vector<int64_t> &tb_off = H.tb_off, &rows_off = H.rows_off, &est = H.est;
     std::vector<uint8_t> &is_big = H.is_big;
@@ -2453,33 +2204,11 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     need_v.resize((size_t)n_iv); nmax_v.resize((size_t)n_iv);
     ctx->pool->parallel_for(n_iv, 2048, [&](int64_t b, int64_t e) {
         for (int64_t iv = b; iv < e; iv++) {
-            int64_t mmax = 0, mmin = 0, need = 0, nmax = 0, es = 0, longest = 0, rneed = 0; bool first = true; uint8_t big = 0;
-            DpClassEst ce; ce.mode = dp_class_mode();
+            int64_t longest = 0;
             for (int g = 0; g < nseq; g++) longest = std::max(longest, seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g]);
-            const bool banded = longest > band_from;
-            for (int g = 0; g < nseq; g++) {
-                const int64_t n = seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g];
-                ce.add(n);
-                if (n == 0) continue;
-                if (first) { first = false; mmax = mmin = n; continue; }
-                const int64_t tbo = dp_tb_need(mmin, mmax, n, banded);  // the profile is at least as long as its longest member
-                const int64_t tbn = banded ? tbo : std::max(tbo, std::max(dp2_tb_need(mmax, n), dp3_tb_need(mmax, n)));     // (any of the kernel families may run the interval)
-                rneed = std::max(rneed, dp3_rows_need(mmax, n));
-                need = std::max(need, tbn);
-                nmax = std::max(nmax, n);
-                // a step with several bands in one dimension spreads over the waves of a workgroup (wide sweep); weight: scan steps of one wave,
-                // from the estimate of the profile length (at least its longest member, rarely much more)
-                const int64_t e_m = std::min(mmax, mmin + mmin / 8 + 2);
-                if (std::max(e_m, n) > DP3_BAND && !no_mw) big = 1;
-                es += dp3_scan_steps(e_m, n);
-                mmax += n; mmin = std::max(mmin, n);
-            }
-            if (banded && nmax) big = 2;                               // banded steps exist only in the workgroup kernel
-            need_v[(size_t)iv] = need; nmax_v[(size_t)iv] = std::max(6 * (nmax + 1), rneed); est[(size_t)iv] = es; is_big[(size_t)iv] = big;
-            // sub-wave classes: every profile the interval will see fits G rows, every step fits the LDS slice
-            uint8_t k = 1;
-            if (!no_groups && !banded) k = (uint8_t)(dp_old_kernels() ? ce.klass(DP_GRP_TMAX) : ce.klass2(DP2_R, DP2_T));
-            cls[(size_t)iv] = k;
+            DpSizing z(band_from, no_mw, no_groups, dp_class_mode(), longest);
+            for (int g = 0; g < nseq; g++) z.add(seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g]);
+            need_v[(size_t)iv] = z.need; nmax_v[(size_t)iv] = z.rows(); est[(size_t)iv] = z.est; is_big[(size_t)iv] = z.cand(); cls[(size_t)iv] = z.cls();
         }
     });
     for (int64_t iv = 0; iv < n_iv; iv++) {
@@ -2489,12 +2218,12 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     }
     tb_off[n_iv] = tbt; rows_off[n_iv] = rwt;
 
-    DpScoring sc; sc.go = scoring->gap_open; sc.ge = scoring->gap_extend; memcpy(sc.s, scoring->matrix, sizeof sc.s);
+    const DpScoring sc = dp_scoring_of(scoring);
     // longest intervals first: one wave per interval, so the tail of the launch is its longest interval
     std::vector<int64_t> &lst = H.lst; lst.resize((size_t)n_iv);
     {   // counting sort by size class (log2 of the traceback footprint), largest class first
         int64_t cnt[66] = {0};
-        auto cls = [&](int64_t iv) { int64_t f = need_v[(size_t)iv]; int c = 0; while (f > 1) { f >>= 1; c++; } return 63 - c; };
+        auto cls = [&](int64_t iv) { return DpSizing::sizekey(need_v[(size_t)iv]); };
         for (int64_t iv = 0; iv < n_iv; iv++) cnt[cls(iv) + 1]++;
         for (int c = 0; c < 65; c++) cnt[c + 1] += cnt[c];
         for (int64_t iv = 0; iv < n_iv; iv++) lst[(size_t)cnt[cls(iv)]++] = iv;
@@ -2529,17 +2258,9 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     tb_list[(size_t)n_iv] = tbt; tb_off[n_iv] = tbt;
     const bool one_round = tbt <= dp_tb_budget();
 
-    HIPCHK(ctx, ctx->dp_codes.ensure((size_t)total + 16));
+    { int rce = dp_ensure_batch(ctx, total, tbt, rwt); if (rce) return rce; }
     HIPCHK(ctx, ctx->dp_off.ensure((size_t)(n_iv * nseq + 1 + 3 * (n_iv + 1)) * sizeof(int64_t)));
-    HIPCHK(ctx, ctx->dp_prof_cnt.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof2_cnt.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof2_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_tb.ensure((size_t)std::min<int64_t>(tbt, dp_tb_budget()) + 64));
-    HIPCHK(ctx, ctx->dp_rows.ensure((size_t)(rwt + 1) * 4));
     HIPCHK(ctx, ctx->dp_meta.ensure((size_t)n_iv * sizeof(DpMeta)));
-    HIPCHK(ctx, ctx->dp_score.ensure((size_t)total + 16));           // reversed-ops scratch
-    HIPCHK(ctx, ctx->dp_cols.ensure((size_t)(total + 1) * 4));
     int64_t *d_seq_off = ctx->dp_off.as<int64_t>();
     int64_t *d_tb_off = d_seq_off + (n_iv * nseq + 1);
     int64_t *d_rows_off = d_tb_off + (n_iv + 1);
@@ -2560,11 +2281,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
         char *pin_desc = reinterpret_cast<char *>(pin_off + n_so + 3 * n_o);
         memcpy(pin_desc, desc, desc_bytes);
         HIPCHK(ctx, hipMemcpyAsync(ctx->dp_desc.p, pin_desc, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
-        DpGenomeWords gw; memset(&gw, 0, sizeof gw);
-        for (int g = 0; g < ctx->nseq; g++) gw.word_off[g] = ctx->word_off[g];
-        const uint32_t gb = (uint32_t)std::min<int64_t>((nd + 15) / 16, 256 * 8);
-        hipLaunchKernelGGL(dp_gather_codes, dim3(gb), dim3(256), 0, ctx->stream, ctx->genomes.as<uint64_t>(), gw,
-                           ctx->dp_desc.as<DpSeqDesc>(), d_seq_off, nd, ctx->dp_codes.as<uint8_t>());
+        dp_launch_gather_codes(ctx, d_seq_off, nd);
     } else if (total) {
         HIPCHK(ctx, hipMemcpyAsync(ctx->dp_codes.p, codes, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -2585,7 +2302,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     const double td3 = now_ms();
     int64_t tc = 0, ncell = 0;
     for (int64_t iv = 0; iv < n_iv; iv++) {
-        if (hm[iv].pad) { ctx->err = "dp: a cluster of workgroups could not make progress on an interval (wide sweep)"; return MAUVE_ERR_HIP; }
+        if (hm[iv].pad) { ctx->err = DP_ERR_CLUSTER; return MAUVE_ERR_HIP; }
         col_off[iv] = tc; tc += hm[iv].m; ncell += hm[iv].cells;
         if (score) score[iv] = hm[iv].score;
     }
@@ -2680,88 +2397,50 @@ struct DpSlots {                             // DP gaps in chain order -> slots
     __device__ void total(uint32_t n, int) const { tot->n_dp = n; }
 };
 
-// per DP interval: descriptors of its sequences, traceback bytes (worst profile length before each step), parked
-// rows, single-wave step estimate, whether a step is long enough for the workgroup pipeline, sub-wave class
+// per DP interval: descriptors of its sequences and its sizing (DpSizing); slot s is its own value for the launch-order sort
+struct DpSizingOut {
+    int64_t *need, *rowsn, *est; uint8_t *cand, *cls; uint32_t *sizekey, *slotval;
+    __device__ void put(uint32_t s, const DpSizing &z) const
+    {
+        need[s] = z.need; rowsn[s] = z.rows(); est[s] = z.est; cand[s] = z.cand(); cls[s] = z.cls();
+        sizekey[s] = z.sizekey(); slotval[s] = s;
+    }
+};
 __global__ void __launch_bounds__(256) dpf_desc(const int32_t *__restrict__ alen, const int32_t *__restrict__ ast, int N,
                                                 const uint32_t *__restrict__ anchor_of, const DpFrontTotals *__restrict__ tot,
-                                                DpSeqDesc *__restrict__ desc, int64_t *__restrict__ need, int64_t *__restrict__ rowsn,
-                                                int64_t *__restrict__ est, uint8_t *__restrict__ cand, uint8_t *__restrict__ cls,
-                                                uint32_t *__restrict__ sizekey, uint32_t *__restrict__ slotval, int no_mw, int no_groups, int64_t band_from, int class_mode)
+                                                DpSeqDesc *__restrict__ desc, DpSizingOut out, int no_mw, int no_groups, int64_t band_from, int class_mode)
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s >= (uint32_t)tot->n_dp) return;
     const uint32_t k = anchor_of[s];
-    int64_t mmax = 0, mmin = 0, nd = 0, nmax = 0, es = 0, longest = 0, rneed = 0; bool first = true; uint8_t big = 0;
-    DpClassEst ce; ce.mode = class_mode & 7;                 // bit 3: the systolic kernels' classes (MAUVE_DP_OLD)
+    int64_t longest = 0;
     for (int g = 0; g < N; g++) {
         int64_t lo, n; bool rv;
         dpf_gap(alen, ast, N, k, g, lo, n, rv);
         longest = max(longest, n);
     }
-    const bool banded = longest > band_from;
+    DpSizing z(band_from, no_mw, no_groups, class_mode, longest);
     for (int g = 0; g < N; g++) {
         int64_t lo, n; bool rv;
         dpf_gap(alen, ast, N, k, g, lo, n, rv);
         DpSeqDesc d; d.genome = g; d.rev = rv; d.lo0 = lo - 1; d.len = n;
         desc[(size_t)s * N + g] = d;
-        ce.add(n);
-        if (n == 0) continue;
-        if (first) { first = false; mmax = mmin = n; continue; }
-        const int64_t tbo = dp_tb_need(mmin, mmax, n, banded);
-        const int64_t tbn = banded ? tbo : max(tbo, max(dp2_tb_need(mmax, n), dp3_tb_need(mmax, n)));
-        rneed = max(rneed, dp3_rows_need(mmax, n));
-        nd = max(nd, tbn);
-        nmax = max(nmax, n);
-        const int64_t e_m = min(mmax, mmin + mmin / 8 + 2);      // (dp_core: the same weights)
-        if (max(e_m, n) > DP3_BAND && !no_mw) big = 1;
-        es += dp3_scan_steps(e_m, n);
-        mmax += n; mmin = max(mmin, n);
+        z.add(n);
     }
-    if (banded && nmax) big = 2;                             // banded steps exist only in the workgroup kernel
-    need[s] = nd; rowsn[s] = max(6 * (nmax + 1), rneed); est[s] = es; cand[s] = big;
-    uint8_t kc = 1;
-    if (!no_groups && !banded) kc = (uint8_t)(class_mode & 8 ? ce.klass(DP_GRP_TMAX) : ce.klass2(DP2_R, DP2_T));
-    cls[s] = kc;
-    int c = 0; for (int64_t f = nd; f > 1; f >>= 1) c++;
-    sizekey[s] = (uint32_t)(63 - c);                         // largest traceback footprint first
-    slotval[s] = s;
+    out.put(s, z);
 }
 // the same sizing for a batch whose descriptors the host made (dp_run_from_desc: the intervals of a guide-tree node and their refinement candidates)
 __global__ void __launch_bounds__(256) dpf_size_desc(const DpSeqDesc *__restrict__ desc, int N, uint32_t n, DpFrontTotals *__restrict__ tot,
-                                                     int64_t *__restrict__ need, int64_t *__restrict__ rowsn, int64_t *__restrict__ est, uint8_t *__restrict__ cand,
-                                                     uint8_t *__restrict__ cls, uint32_t *__restrict__ sizekey, uint32_t *__restrict__ slotval, int no_mw, int no_groups,
-                                                     int64_t band_from, int class_mode)
+                                                     DpSizingOut out, int no_mw, int no_groups, int64_t band_from, int class_mode)
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s == 0) tot->n_dp = n;                               // (the block was cleared by a memset in front of this launch)
     if (s >= n) return;
-    int64_t mmax = 0, mmin = 0, nd = 0, nmax = 0, es = 0, longest = 0, rneed = 0; bool first = true; uint8_t big = 0;
-    DpClassEst ce; ce.mode = class_mode & 7;
+    int64_t longest = 0;
     for (int g = 0; g < N; g++) longest = max(longest, desc[(size_t)s * N + g].len);
-    const bool banded = longest > band_from;
-    for (int g = 0; g < N; g++) {
-        const int64_t nn = desc[(size_t)s * N + g].len;
-        ce.add(nn);
-        if (nn == 0) continue;
-        if (first) { first = false; mmax = mmin = nn; continue; }
-        const int64_t tbo = dp_tb_need(mmin, mmax, nn, banded);
-        const int64_t tbn = banded ? tbo : max(tbo, max(dp2_tb_need(mmax, nn), dp3_tb_need(mmax, nn)));
-        rneed = max(rneed, dp3_rows_need(mmax, nn));
-        nd = max(nd, tbn);
-        nmax = max(nmax, nn);
-        const int64_t e_m = min(mmax, mmin + mmin / 8 + 2);
-        if (max(e_m, nn) > DP3_BAND && !no_mw) big = 1;
-        es += dp3_scan_steps(e_m, nn);
-        mmax += nn; mmin = max(mmin, nn);
-    }
-    if (banded && nmax) big = 2;
-    need[s] = nd; rowsn[s] = max(6 * (nmax + 1), rneed); est[s] = es; cand[s] = big;
-    uint8_t kc = 1;
-    if (!no_groups && !banded) kc = (uint8_t)(class_mode & 8 ? ce.klass(DP_GRP_TMAX) : ce.klass2(DP2_R, DP2_T));
-    cls[s] = kc;
-    int c = 0; for (int64_t f = nd; f > 1; f >>= 1) c++;
-    sizekey[s] = (uint32_t)(63 - c);
-    slotval[s] = s;
+    DpSizing z(band_from, no_mw, no_groups, class_mode, longest);
+    for (int g = 0; g < N; g++) z.add(desc[(size_t)s * N + g].len);
+    out.put(s, z);
 }
 struct DescLen { const DpSeqDesc *d; __device__ int64_t value(uint32_t i) const { return d[i].len; } };
 struct ArrVal { const int64_t *a; __device__ int64_t value(uint32_t i) const { return a[i]; } };
@@ -2804,6 +2483,109 @@ __global__ void __launch_bounds__(256) dpf_scores(const DpMeta *__restrict__ met
 
 }  // namespace
 
+// The work area of the device front end, carved up for na slots (an upper bound of the DP intervals) of N genomes:
+// sizing arrays, sort pairs, tile counts and sums in dpf_work; the four offset tables in dp_off
+struct DpFrontWork {
+    DpSeqDesc *desc; DpFrontTotals *tot;
+    int64_t *need, *rowsn, *est; uint8_t *cand, *cls;
+    uint32_t *k1, *v1, *k2, *v2, *k3, *bcnt; int64_t *bsum, *bsum2;
+    int64_t *d_seq_off, *d_tb_off, *d_rows_off, *d_col_off;
+    DpSizingOut sizing() const { return DpSizingOut{need, rowsn, est, cand, cls, k1, v1}; }
+};
+static int dpf_work_area(mauve_ctx *ctx, uint32_t na, int N, DpFrontWork &W)
+{
+    const uint32_t nb = (na + TILE - 1) / TILE;
+    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+    // need / rows / est (int64), cand / cls (bytes), 5 x uint32 sort arrays, tile counts, tile sums (int64)
+    const size_t o_cand = (size_t)na * 24, o_k = up8(o_cand + 2 * (size_t)na), o_bcnt = o_k + (size_t)na * 20, o_bsum = up8(o_bcnt + (size_t)nb * 4),
+                 o_bsum2 = o_bsum + ((size_t)nb * N + 8) * 8, w_total = o_bsum2 + ((size_t)nb + 8) * 8;
+    HIPCHK(ctx, ctx->dp_desc.ensure((size_t)na * N * sizeof(DpSeqDesc)));
+    HIPCHK(ctx, ctx->dpf_work.ensure(w_total));
+    HIPCHK(ctx, ctx->dp_off.ensure(((size_t)na * N + 1 + 3 * ((size_t)na + 1)) * sizeof(int64_t)));
+    HIPCHK(ctx, ctx->dp_list.ensure((size_t)na * 8));
+    HIPCHK(ctx, ctx->dp_meta.ensure((size_t)na * sizeof(DpMeta)));
+    HIPCHK(ctx, ctx->dpf_tot.ensure(256));
+    char *wk = ctx->dpf_work.as<char>();
+    W.desc = ctx->dp_desc.as<DpSeqDesc>(); W.tot = ctx->dpf_tot.as<DpFrontTotals>();
+    W.need = reinterpret_cast<int64_t *>(wk); W.rowsn = W.need + na; W.est = W.rowsn + na;
+    W.cand = reinterpret_cast<uint8_t *>(wk + o_cand); W.cls = W.cand + na;
+    W.k1 = reinterpret_cast<uint32_t *>(wk + o_k); W.v1 = W.k1 + na; W.k2 = W.v1 + na; W.v2 = W.k2 + na; W.k3 = W.v2 + na;
+    W.bcnt = reinterpret_cast<uint32_t *>(wk + o_bcnt);
+    W.bsum = reinterpret_cast<int64_t *>(wk + o_bsum); W.bsum2 = reinterpret_cast<int64_t *>(wk + o_bsum2);
+    W.d_seq_off = ctx->dp_off.as<int64_t>();
+    W.d_tb_off = W.d_seq_off + ((size_t)na * N + 1); W.d_rows_off = W.d_tb_off + (na + 1); W.d_col_off = W.d_rows_off + (na + 1);
+    return MAUVE_OK;
+}
+
+// The front end proper.  In: the descriptors and sizing arrays of n_dp intervals are on the device (dpf_desc or dpf_size_desc is in the
+// stream) and the totals block holds n_dp.  Here: offsets by scans, the launch order, one read-back of the totals (*ht, page-locked) to
+// size the buffers, the bases gathered, the DP rounds, and the results laid out on the device -- column offsets in d_col_off, scores in
+// W.need (the sizing arrays are free by then), the cell count and the cluster error flag in the totals block, the columns compacted in
+// dp_cols.  Nothing after the rounds has been waited for when it returns.
+struct DpFrontRun { int64_t n_big; DpClasses cl; int rounds; double t_sized; };
+static int dpf_run(mauve_ctx *ctx, const DpFrontWork &W, int N, uint32_t n_dp, const DpScoring &sc, DpFrontTotals *ht, DpFrontRun &R)
+{
+    const uint32_t nbd = (n_dp + TILE - 1) / TILE, nbs = (n_dp * (uint32_t)N + TILE - 1) / TILE, blk_d = (n_dp + 255) / 256;
+    DpFrontTotals *tot = W.tot;
+    hipLaunchKernelGGL((vscan_partial<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{W.desc}, n_dp * (uint32_t)N, W.bsum);
+    hipLaunchKernelGGL((vscan_write<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{W.desc}, n_dp * (uint32_t)N, W.bsum, W.d_seq_off, &tot->codes);
+    hipLaunchKernelGGL((vscan_partial<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{W.rowsn}, n_dp, W.bsum);
+    hipLaunchKernelGGL((vscan_write<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{W.rowsn}, n_dp, W.bsum, W.d_rows_off, &tot->rows);
+    hipLaunchKernelGGL((vscan_partial<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{W.est}, n_dp, W.bsum2);
+    hipLaunchKernelGGL((vscan_write<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{W.est}, n_dp, W.bsum2, W.d_col_off /*scratch*/, &tot->est);
+    // launch order: size class (stable), the workgroup-pipeline pick in that order, then kernel class (stable)
+    uint32_t *ok = W.k1, *ov = W.v1;
+    int rc = sort_pairs_u32(ctx, n_dp, 6, &ok, &ov, W.k2, W.v2, MAUVE_K_MISC);
+    if (rc) return rc;
+    uint32_t *fk = ok == W.k1 ? W.k2 : W.k1, *fv = ov == W.v1 ? W.v2 : W.v1;        // free pair
+    const DpBigPick bp{ov, W.cand, W.cls, W.est, tot, fk, dp_wide_min(), (uint32_t)dp_big_max()};
+    hipLaunchKernelGGL((cmp_count<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, W.bcnt);
+    hipLaunchKernelGGL((cmp_write<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, W.bcnt);
+    uint32_t *ck = fk, *cv = ov;
+    rc = sort_pairs_u32(ctx, n_dp, 3, &ck, &cv, W.k3, fv, MAUVE_K_MISC);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dpf_list, dim3(blk_d), dim3(256), 0, ctx->stream, ck, cv, tot, ctx->dp_list.as<int64_t>());
+    // traceback offsets in list order (a round of the list then uses one contiguous piece of the buffer)
+    int64_t *tb_list_dev = W.d_col_off;                                 // scratch until the results need it
+    hipLaunchKernelGGL((vscan_partial<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{W.need, cv}, n_dp, W.bsum2);
+    hipLaunchKernelGGL((vscan_write<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{W.need, cv}, n_dp, W.bsum2, tb_list_dev, &tot->tb);
+    hipLaunchKernelGGL(dpf_tb_scatter, dim3(blk_d), dim3(256), 0, ctx->stream, tb_list_dev, cv, n_dp, W.d_tb_off);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ht, tot, sizeof(DpFrontTotals), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t total = ht->codes, tbt = ht->tb, rwt = ht->rows;
+    DpClasses &cl = R.cl; memset(&cl, 0, sizeof cl);
+    R.n_big = ht->first_med;
+    cl.first_med = ht->first_med; cl.n_med = ht->first_c - ht->first_med;
+    cl.first_c = ht->first_c; cl.n_c = ht->first_s32 - ht->first_c;
+    cl.first_s32 = ht->first_s32; cl.n_s32 = ht->first_s16 - ht->first_s32;
+    cl.first_s16 = ht->first_s16; cl.n_s16 = (int64_t)n_dp - ht->first_s16;          // (block counts: dp_launch_steps)
+    R.t_sized = now_ms();
+    rc = dp_ensure_batch(ctx, total, tbt, rwt);
+    if (rc) return rc;
+    std::vector<int64_t> &tb_list = ctx->dph.tb_list; tb_list.clear();
+    if (tbt > dp_tb_budget()) {                                         // several rounds: the host needs the cumulative bytes to cut them
+        tb_list.resize((size_t)n_dp + 1);
+        HIPCHK(ctx, hipMemcpy(tb_list.data(), tb_list_dev, ((size_t)n_dp + 1) * 8, hipMemcpyDeviceToHost));
+    }
+    dp_launch_gather_codes(ctx, W.d_seq_off, (int64_t)n_dp * N);
+    R.rounds = 1;
+    rc = dp_launch_rounds(ctx, N, n_dp, R.n_big, cl, W.d_seq_off, W.d_tb_off, W.d_rows_off, sc, tb_list.empty() ? nullptr : tb_list.data(), &R.rounds, ctx->dp_band_from);
+    if (rc) return rc;
+    // results: column offsets, scores and the cell count by scans over the per-interval records; the columns compacted
+    const DpMeta *meta = ctx->dp_meta.as<DpMeta>();
+    hipLaunchKernelGGL((vscan_partial<int64_t, MetaCols>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCols{meta}, n_dp, W.bsum);
+    hipLaunchKernelGGL((vscan_write<int64_t, MetaCols>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCols{meta}, n_dp, W.bsum, W.d_col_off, &tot->cols);
+    hipLaunchKernelGGL((vscan_partial<int64_t, MetaCells>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCells{meta}, n_dp, W.bsum2);
+    hipLaunchKernelGGL((vscan_write<int64_t, MetaCells>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCells{meta}, n_dp, W.bsum2, W.rowsn /*scratch*/, &tot->cells);
+    hipLaunchKernelGGL(dpf_scores, dim3(blk_d), dim3(256), 0, ctx->stream, meta, n_dp, W.need, tot);
+    const uint32_t gblocks = (uint32_t)std::min<int64_t>(((int64_t)n_dp + 3) / 4, 256 * 8);
+    hipLaunchKernelGGL(dp_gather, dim3(gblocks), dim3(256), 0, ctx->stream, N, (int64_t)n_dp, W.d_seq_off, meta, ctx->dp_prof_mask.as<uint32_t>(),
+                       ctx->dp_prof2_mask.as<uint32_t>(), W.d_col_off, ctx->dp_cols.as<uint32_t>());
+    HIPCHK(ctx, hipGetLastError());
+    return MAUVE_OK;
+}
+
 // anchors: na records in chain order (LCB by LCB, genome-0 order inside), host arrays (page-locked).  Out: gapcode[na]
 // (-1 / -2 / DP slot), n_dp, the DP columns in *dcols (page-locked, grown here), dcol_off[n_dp + 1], dscore[n_dp].
 // stay_on_device: the anchor arrays are device pointers and nothing but the totals comes back -- the gap codes, column
@@ -2825,46 +2607,27 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na64, const int32_t *h_le
     // device arrays sized by na (an upper bound of n_dp)
     const size_t w_anch = (size_t)na * (2 + (size_t)N) * 4;
     HIPCHK(ctx, ctx->dpf_anch.ensure(w_anch + (size_t)na * 4 * 2 + 64));                       // anchors, gapcode, anchor_of
-    HIPCHK(ctx, ctx->dp_desc.ensure((size_t)na * N * sizeof(DpSeqDesc)));
-    // work area: need / rows / est (int64), cand / cls (bytes), 5 x uint32 sort arrays, tile counts, tile sums (int64)
-    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
-    const size_t o_cand = (size_t)na * 24, o_k = up8(o_cand + 2 * (size_t)na), o_bcnt = o_k + (size_t)na * 20, o_bsum = up8(o_bcnt + (size_t)nb * 4),
-                 o_bsum2 = o_bsum + ((size_t)nb * N + 8) * 8, w_total = o_bsum2 + ((size_t)nb + 8) * 8;
-    HIPCHK(ctx, ctx->dpf_work.ensure(w_total));
-    HIPCHK(ctx, ctx->dp_off.ensure(((size_t)na * N + 1 + 3 * ((size_t)na + 1)) * sizeof(int64_t)));
-    HIPCHK(ctx, ctx->dp_list.ensure((size_t)na * 8));
-    HIPCHK(ctx, ctx->dp_meta.ensure((size_t)na * sizeof(DpMeta)));
-    HIPCHK(ctx, ctx->dpf_tot.ensure(256));
+    DpFrontWork W;
+    int rc = dpf_work_area(ctx, na, N, W);
+    if (rc) return rc;
+    DpFrontTotals *tot = W.tot;
     int32_t *alen = ctx->dpf_anch.as<int32_t>(), *ast = alen + na, *alcb = ast + (size_t)na * N, *d_gapcode = alcb + na;
     uint32_t *anchor_of = reinterpret_cast<uint32_t *>(d_gapcode + na);
     if (anchors_in_place) {          // the anchors are device arrays already: used where they are (no copy)
         alen = const_cast<int32_t *>(h_len); ast = const_cast<int32_t *>(h_st); alcb = const_cast<int32_t *>(h_lcb);
-    }
-    DpSeqDesc *desc = ctx->dp_desc.as<DpSeqDesc>();
-    char *wk = ctx->dpf_work.as<char>();
-    int64_t *need = reinterpret_cast<int64_t *>(wk), *rowsn = need + na, *est = rowsn + na;
-    uint8_t *cand = reinterpret_cast<uint8_t *>(wk + o_cand), *cls = cand + na;
-    uint32_t *k1 = reinterpret_cast<uint32_t *>(wk + o_k), *v1 = k1 + na, *k2 = v1 + na, *v2 = k2 + na, *k3 = v2 + na;
-    uint32_t *bcnt = reinterpret_cast<uint32_t *>(wk + o_bcnt);
-    int64_t *bsum = reinterpret_cast<int64_t *>(wk + o_bsum), *bsum2 = reinterpret_cast<int64_t *>(wk + o_bsum2);
-    DpFrontTotals *tot = ctx->dpf_tot.as<DpFrontTotals>();
-    int64_t *d_seq_off = ctx->dp_off.as<int64_t>();
-    int64_t *d_tb_off = d_seq_off + ((size_t)na * N + 1), *d_rows_off = d_tb_off + (na + 1), *d_col_off = d_rows_off + (na + 1);
-    if (!anchors_in_place) {
+    } else {
         HIPCHK(ctx, hipMemcpyAsync(alen, h_len, (size_t)na * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(ast, h_st, (size_t)na * N * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(alcb, h_lcb, (size_t)na * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     hipLaunchKernelGGL(dpf_gap_flags, dim3(blocks), dim3(256), 0, ctx->stream, alen, ast, alcb, na, N, gapped, max_gapped_len, d_gapcode, reinterpret_cast<uint32_t *>(tot));
     const DpSlots sl{d_gapcode, na, anchor_of, tot};
-    hipLaunchKernelGGL((cmp_count<DpSlots>), dim3(nb), dim3(256), 0, ctx->stream, sl, bcnt);
-    hipLaunchKernelGGL((cmp_write<DpSlots>), dim3(nb), dim3(256), 0, ctx->stream, sl, bcnt);
-    hipLaunchKernelGGL(dpf_desc, dim3(blocks), dim3(256), 0, ctx->stream, alen, ast, N, anchor_of, tot, desc, need, rowsn, est, cand, cls, k1, v1,
-                       (int)no_mw, (int)no_groups, ctx->dp_band_from, dp_class_mode() | (dp_old_kernels() ? 8 : 0));
-    // the counts below are device values; the launches cover na (>= n_dp) entries and the kernels stop at n_dp.
-    // Offsets: the value functors return 0 beyond n_dp because the arrays there are never read -- so clear them first.
-    // (need / rows / est / desc of slots >= n_dp are not written: scan over exactly n_dp needs the count -> two-phase:
-    //  read the small totals block back first.)
+    hipLaunchKernelGGL((cmp_count<DpSlots>), dim3(nb), dim3(256), 0, ctx->stream, sl, W.bcnt);
+    hipLaunchKernelGGL((cmp_write<DpSlots>), dim3(nb), dim3(256), 0, ctx->stream, sl, W.bcnt);
+    hipLaunchKernelGGL(dpf_desc, dim3(blocks), dim3(256), 0, ctx->stream, alen, ast, N, anchor_of, tot, W.desc, W.sizing(),
+                       (int)no_mw, (int)no_groups, ctx->dp_band_from, dp_class_mode());
+    // the launch covers na (>= n_dp) slots and the kernel stops at n_dp, a device value; the scans that follow run over exactly
+    // n_dp entries, so the small totals block is read back first
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, ctx->pin_dp_in.ensure(256 + (size_t)na * 4));
     DpFrontTotals *ht = ctx->pin_dp_in.as<DpFrontTotals>();
@@ -2875,95 +2638,25 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na64, const int32_t *h_le
     const uint32_t n_dp = (uint32_t)ht->n_dp;
     if (!stay_on_device) memcpy(gapcode, h_gapcode, (size_t)na * 4);
     *n_dp_out = n_dp;
+    int64_t *d_col_off = W.d_col_off, *d_score = W.need;                 // where dpf_run leaves the offsets and scores
     mauve_ctx::DpFrontOut &fo = ctx->dpf_out;
-    fo.alen = alen; fo.ast = ast; fo.alcb = alcb; fo.gapcode = d_gapcode; fo.col_off = d_col_off; fo.score = need; fo.cols = nullptr; fo.n_dp = n_dp; fo.n_cols = 0;
+    fo.alen = alen; fo.ast = ast; fo.alcb = alcb; fo.gapcode = d_gapcode; fo.col_off = d_col_off; fo.score = d_score; fo.cols = nullptr; fo.n_dp = n_dp; fo.n_cols = 0;
     const double t1 = now_ms();
     if (n_dp == 0) return MAUVE_OK;
-    const uint32_t nbd = (n_dp + TILE - 1) / TILE, nbs = (n_dp * (uint32_t)N + TILE - 1) / TILE, blk_d = (n_dp + 255) / 256;
-    hipLaunchKernelGGL((vscan_partial<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{desc}, n_dp * (uint32_t)N, bsum);
-    hipLaunchKernelGGL((vscan_write<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{desc}, n_dp * (uint32_t)N, bsum, d_seq_off, &tot->codes);
-    hipLaunchKernelGGL((vscan_partial<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{rowsn}, n_dp, bsum);
-    hipLaunchKernelGGL((vscan_write<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{rowsn}, n_dp, bsum, d_rows_off, &tot->rows);
-    hipLaunchKernelGGL((vscan_partial<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{est}, n_dp, bsum2);
-    hipLaunchKernelGGL((vscan_write<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{est}, n_dp, bsum2, d_col_off /*scratch*/, &tot->est);
-    // launch order: size class (stable), the workgroup-pipeline pick in that order, then kernel class (stable)
-    uint32_t *ok = k1, *ov = v1;
-    int rc = sort_pairs_u32(ctx, n_dp, 6, &ok, &ov, k2, v2, MAUVE_K_MISC);
+    DpFrontRun R;
+    rc = dpf_run(ctx, W, N, n_dp, dp_scoring_of(scoring), ht, R);
     if (rc) return rc;
-    uint32_t *fk = ok == k1 ? k2 : k1, *fv = ov == v1 ? v2 : v1;        // free pair
-    const DpBigPick bp{ov, cand, cls, est, tot, fk, dp_wide_min(), (uint32_t)dp_big_max()};
-    hipLaunchKernelGGL((cmp_count<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, bcnt);
-    hipLaunchKernelGGL((cmp_write<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, bcnt);
-    uint32_t *ck = fk, *cv = ov;
-    rc = sort_pairs_u32(ctx, n_dp, 3, &ck, &cv, k3, fv, MAUVE_K_MISC);
-    if (rc) return rc;
-    hipLaunchKernelGGL(dpf_list, dim3(blk_d), dim3(256), 0, ctx->stream, ck, cv, tot, ctx->dp_list.as<int64_t>());
-    // traceback offsets in list order (a round of the list then uses one contiguous piece of the buffer)
-    int64_t *tb_list_dev = d_col_off;                                   // scratch until the results need it
-    hipLaunchKernelGGL((vscan_partial<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{need, cv}, n_dp, bsum2);
-    hipLaunchKernelGGL((vscan_write<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{need, cv}, n_dp, bsum2, tb_list_dev, &tot->tb);
-    hipLaunchKernelGGL(dpf_tb_scatter, dim3(blk_d), dim3(256), 0, ctx->stream, tb_list_dev, cv, n_dp, d_tb_off);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ht, tot, sizeof(DpFrontTotals), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t total = ht->codes, tbt = ht->tb, rwt = ht->rows;
-    *code_total_out = total;
-    DpClasses cl; memset(&cl, 0, sizeof cl);
-    const int64_t n_big = ht->first_med;
-    cl.first_med = ht->first_med; cl.n_med = ht->first_c - ht->first_med;
-    cl.first_c = ht->first_c; cl.n_c = ht->first_s32 - ht->first_c;
-    cl.first_s32 = ht->first_s32; cl.n_s32 = ht->first_s16 - ht->first_s32;
-    cl.first_s16 = ht->first_s16; cl.n_s16 = (int64_t)n_dp - ht->first_s16;          // (block counts: dp_launch_steps)
-    const double t2 = now_ms();
-    HIPCHK(ctx, ctx->dp_codes.ensure((size_t)total + 16));
-    HIPCHK(ctx, ctx->dp_prof_cnt.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof2_cnt.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof2_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_tb.ensure((size_t)std::min<int64_t>(tbt, dp_tb_budget()) + 64));
-    HIPCHK(ctx, ctx->dp_rows.ensure((size_t)(rwt + 1) * 4));
-    HIPCHK(ctx, ctx->dp_score.ensure((size_t)total + 16));           // reversed-ops scratch
-    HIPCHK(ctx, ctx->dp_cols.ensure((size_t)(total + 1) * 4));
-    std::vector<int64_t> &tb_list = ctx->dph.tb_list; tb_list.clear();
-    if (tbt > dp_tb_budget()) {                                         // several rounds: the host needs the cumulative bytes to cut them
-        tb_list.resize((size_t)n_dp + 1);
-        HIPCHK(ctx, hipMemcpy(tb_list.data(), tb_list_dev, ((size_t)n_dp + 1) * 8, hipMemcpyDeviceToHost));
-    }
-    {
-        DpGenomeWords gw; memset(&gw, 0, sizeof gw);
-        for (int g = 0; g < ctx->nseq; g++) gw.word_off[g] = ctx->word_off[g];
-        const int64_t nd = (int64_t)n_dp * N;
-        const uint32_t gb = (uint32_t)std::min<int64_t>((nd + 15) / 16, 256 * 8);
-        hipLaunchKernelGGL(dp_gather_codes, dim3(gb), dim3(256), 0, ctx->stream, ctx->genomes.as<uint64_t>(), gw, desc, d_seq_off, nd,
-                           ctx->dp_codes.as<uint8_t>());
-    }
-    DpScoring sc; sc.go = scoring->gap_open; sc.ge = scoring->gap_extend; memcpy(sc.s, scoring->matrix, sizeof sc.s);
-    int rounds = 1;
-    rc = dp_launch_rounds(ctx, N, n_dp, n_big, cl, d_seq_off, d_tb_off, d_rows_off, sc, tb_list.empty() ? nullptr : tb_list.data(), &rounds, ctx->dp_band_from);
-    if (rc) return rc;
-    // results: column offsets, scores and the cell count by scans over the per-interval records; the columns compacted
-    const DpMeta *meta = ctx->dp_meta.as<DpMeta>();
-    int64_t *d_score = need;                                            // the sizing arrays are free again
-    hipLaunchKernelGGL((vscan_partial<int64_t, MetaCols>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCols{meta}, n_dp, bsum);
-    hipLaunchKernelGGL((vscan_write<int64_t, MetaCols>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCols{meta}, n_dp, bsum, d_col_off, &tot->cols);
-    hipLaunchKernelGGL((vscan_partial<int64_t, MetaCells>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCells{meta}, n_dp, bsum2);
-    hipLaunchKernelGGL((vscan_write<int64_t, MetaCells>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCells{meta}, n_dp, bsum2, rowsn /*scratch*/, &tot->cells);
-    hipLaunchKernelGGL(dpf_scores, dim3(blk_d), dim3(256), 0, ctx->stream, meta, n_dp, d_score, tot);
-    {
-        const uint32_t gblocks = (uint32_t)std::min<int64_t>(((int64_t)n_dp + 3) / 4, 256 * 8);
-        hipLaunchKernelGGL(dp_gather, dim3(gblocks), dim3(256), 0, ctx->stream, N, (int64_t)n_dp, d_seq_off, meta, ctx->dp_prof_mask.as<uint32_t>(),
-                           ctx->dp_prof2_mask.as<uint32_t>(), d_col_off, ctx->dp_cols.as<uint32_t>());
-    }
-    HIPCHK(ctx, hipGetLastError());
+    *code_total_out = ht->codes;
+    const double t2 = R.t_sized;
     if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // host work while the DP kernels run
     if (stay_on_device) {
         HIPCHK(ctx, hipMemcpyAsync(ht, tot, sizeof(DpFrontTotals), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ht->err) { ctx->err = "dp: a cluster of workgroups could not make progress on an interval (wide sweep)"; return MAUVE_ERR_HIP; }
+        if (ht->err) { ctx->err = DP_ERR_CLUSTER; return MAUVE_ERR_HIP; }
         if (cells) *cells = ht->cells;
         fo.cols = ctx->dp_cols.as<uint32_t>(); fo.n_cols = ht->cols;
         if (trace) fprintf(stderr, "[trace] dp (device front, results stay): %u intervals (%lld workgroup, %lld one-wave, %lld two/wave, %lld four/wave), %d round(s); gaps+slots %.3f ms, sizing+order %.3f, kernels+offsets %.3f\n",
-                           n_dp, (long long)n_big, (long long)cl.n_med, (long long)cl.n_s32, (long long)cl.n_s16, rounds, t1 - t0, t2 - t1, now_ms() - t2);
+                           n_dp, (long long)R.n_big, (long long)R.cl.n_med, (long long)R.cl.n_s32, (long long)R.cl.n_s16, R.rounds, t1 - t0, t2 - t1, now_ms() - t2);
         return MAUVE_OK;
     }
     dcol_off.resize((size_t)n_dp + 1); dscore.resize((size_t)n_dp);
@@ -2974,7 +2667,7 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na64, const int32_t *h_le
     HIPCHK(ctx, hipMemcpyAsync(p_score, d_score, (size_t)n_dp * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const double t3 = now_ms();
-    if (ht->err) { ctx->err = "dp: a cluster of workgroups could not make progress on an interval (wide sweep)"; return MAUVE_ERR_HIP; }
+    if (ht->err) { ctx->err = DP_ERR_CLUSTER; return MAUVE_ERR_HIP; }
     const int64_t tc = ht->cols;
     if (cells) *cells = ht->cells;
     memcpy(dcol_off.data(), p_off, ((size_t)n_dp + 1) * 8);
@@ -2985,13 +2678,13 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na64, const int32_t *h_le
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (trace) fprintf(stderr, "[trace] dp (device front): %u intervals (%lld workgroup, %lld one-wave, %lld two/wave, %lld four/wave), %d round(s); gaps+slots %.3f ms, sizing+order %.3f, kernels+offsets %.3f, columns %.3f\n",
-                       n_dp, (long long)n_big, (long long)cl.n_med, (long long)cl.n_s32, (long long)cl.n_s16, rounds, t1 - t0, t2 - t1, t3 - t2, now_ms() - t3);
+                       n_dp, (long long)R.n_big, (long long)R.cl.n_med, (long long)R.cl.n_s32, (long long)R.cl.n_s16, R.rounds, t1 - t0, t2 - t1, t3 - t2, now_ms() - t3);
     return MAUVE_OK;
 }
 
 // A batch of intervals given by descriptors (the progressive path: the intervals of a guide-tree node and all their refinement candidates, 86 000 at
 // C4's root), through the device front end: the descriptors go up once, sizing, offsets and launch order are made by the kernels and scans of
-// dp_run_from_anchors (dp_core's host loops took 7 ms for that batch, beside 4 ms of DP kernels), the result offsets come from scans as well.
+// dpf_run (dp_core's host loops took 7 ms for that batch, beside 4 ms of DP kernels), the result offsets come from scans as well.
 // cols == nullptr: the columns stay in dp_cols (dp_fetch_picked).  sp: the refinement objective (dp_sp_scores), or nullptr.
 // The refinement candidates of a guide-tree node made where they are used: rows [n_orig, n_orig + cbase[n_orig]) of the descriptor table are
 // rotations of the intervals in front of them -- candidate cbase[iv] + r - 1 holds interval iv's non-empty sequences rotated by r, empty slots behind -- so
@@ -3029,29 +2722,15 @@ int dp_run_from_desc(mauve_ctx *ctx, int N, int64_t n_iv, const DpSeqDesc *h_des
     col_off[0] = 0;
     if (n_iv == 0) return MAUVE_OK;
     if (n_iv >= (1LL << 31) / std::max(N, 1)) { ctx->err = "dp: too many intervals"; return MAUVE_ERR_LIMIT; }
-    const uint32_t na = (uint32_t)n_iv, n_dp = na, nb = (na + TILE - 1) / TILE;
-    HIPCHK(ctx, ctx->dp_desc.ensure((size_t)na * N * sizeof(DpSeqDesc)));
-    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
-    const size_t o_cand = (size_t)na * 24, o_k = up8(o_cand + 2 * (size_t)na), o_bcnt = o_k + (size_t)na * 20, o_bsum = up8(o_bcnt + (size_t)nb * 4),
-                 o_bsum2 = o_bsum + ((size_t)nb * N + 8) * 8, w_total = o_bsum2 + ((size_t)nb + 8) * 8;
-    HIPCHK(ctx, ctx->dpf_work.ensure(w_total));
-    HIPCHK(ctx, ctx->dp_off.ensure(((size_t)na * N + 1 + 3 * ((size_t)na + 1)) * sizeof(int64_t)));
-    HIPCHK(ctx, ctx->dp_list.ensure((size_t)na * 8));
-    HIPCHK(ctx, ctx->dp_meta.ensure((size_t)na * sizeof(DpMeta)));
-    HIPCHK(ctx, ctx->dpf_tot.ensure(256));
-    DpSeqDesc *desc = ctx->dp_desc.as<DpSeqDesc>();
-    char *wk = ctx->dpf_work.as<char>();
-    int64_t *need = reinterpret_cast<int64_t *>(wk), *rowsn = need + na, *est = rowsn + na;
-    uint8_t *cand = reinterpret_cast<uint8_t *>(wk + o_cand), *cls = cand + na;
-    uint32_t *k1 = reinterpret_cast<uint32_t *>(wk + o_k), *v1 = k1 + na, *k2 = v1 + na, *v2 = k2 + na, *k3 = v2 + na;
-    uint32_t *bcnt = reinterpret_cast<uint32_t *>(wk + o_bcnt);
-    int64_t *bsum = reinterpret_cast<int64_t *>(wk + o_bsum), *bsum2 = reinterpret_cast<int64_t *>(wk + o_bsum2);
-    DpFrontTotals *tot = ctx->dpf_tot.as<DpFrontTotals>();
-    int64_t *d_seq_off = ctx->dp_off.as<int64_t>();
-    int64_t *d_tb_off = d_seq_off + ((size_t)na * N + 1), *d_rows_off = d_tb_off + (na + 1), *d_col_off = d_rows_off + (na + 1);
+    const uint32_t n_dp = (uint32_t)n_iv;
+    DpFrontWork W;
+    int rc = dpf_work_area(ctx, n_dp, N, W);
+    if (rc) return rc;
+    DpSeqDesc *desc = W.desc;
+    DpFrontTotals *tot = W.tot;
     // cbase: only the first n_orig rows come from the host, the rest are their rotations (dpf_rotate_desc)
     const bool rot = cbase != nullptr && n_orig >= 0 && n_orig < n_iv;
-    const size_t rows_up = rot ? (size_t)n_orig : (size_t)na;
+    const size_t rows_up = rot ? (size_t)n_orig : (size_t)n_dp;
     const size_t desc_bytes = rows_up * N * sizeof(DpSeqDesc), cb_bytes = rot ? ((size_t)n_orig + 1) * 4 : 0;
     HIPCHK(ctx, ctx->pin_dp_in.ensure(256 + desc_bytes + cb_bytes + 64));
     DpFrontTotals *ht = ctx->pin_dp_in.as<DpFrontTotals>();
@@ -3061,87 +2740,23 @@ int dp_run_from_desc(mauve_ctx *ctx, int N, int64_t n_iv, const DpSeqDesc *h_des
         if ((int64_t)cbase[n_orig] != n_iv - n_orig) { ctx->err = "dp: the rotation table does not match the batch"; return MAUVE_ERR_ARG; }
         char *pcb = ctx->pin_dp_in.as<char>() + 256 + ((desc_bytes + 7) & ~(size_t)7);
         memcpy(pcb, cbase, cb_bytes);
-        int32_t *d_cb = reinterpret_cast<int32_t *>(k1);                 // (the sort's key array is free until dpf_size_desc fills it)
+        int32_t *d_cb = reinterpret_cast<int32_t *>(W.k1);               // (the sort's key array is free until dpf_size_desc fills it)
         HIPCHK(ctx, hipMemcpyAsync(d_cb, pcb, cb_bytes, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(dpf_rotate_desc, dim3((uint32_t)((n_orig + 255) / 256)), dim3(256), 0, ctx->stream, desc, N, (uint32_t)n_orig, d_cb);
     }
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 256, ctx->stream));
-    const uint32_t blk_d = (n_dp + 255) / 256;
-    hipLaunchKernelGGL(dpf_size_desc, dim3(blk_d), dim3(256), 0, ctx->stream, desc, N, n_dp, tot, need, rowsn, est, cand, cls, k1, v1, (int)no_mw, (int)no_groups,
-                       ctx->dp_band_from, dp_class_mode() | (dp_old_kernels() ? 8 : 0));
-    const uint32_t nbd = (n_dp + TILE - 1) / TILE, nbs = (n_dp * (uint32_t)N + TILE - 1) / TILE;
-    hipLaunchKernelGGL((vscan_partial<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{desc}, n_dp * (uint32_t)N, bsum);
-    hipLaunchKernelGGL((vscan_write<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{desc}, n_dp * (uint32_t)N, bsum, d_seq_off, &tot->codes);
-    hipLaunchKernelGGL((vscan_partial<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{rowsn}, n_dp, bsum);
-    hipLaunchKernelGGL((vscan_write<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{rowsn}, n_dp, bsum, d_rows_off, &tot->rows);
-    hipLaunchKernelGGL((vscan_partial<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{est}, n_dp, bsum2);
-    hipLaunchKernelGGL((vscan_write<int64_t, ArrVal>), dim3(nbd), dim3(256), 0, ctx->stream, ArrVal{est}, n_dp, bsum2, d_col_off /*scratch*/, &tot->est);
-    uint32_t *ok = k1, *ov = v1;
-    int rc = sort_pairs_u32(ctx, n_dp, 6, &ok, &ov, k2, v2, MAUVE_K_MISC);
+    hipLaunchKernelGGL(dpf_size_desc, dim3((n_dp + 255) / 256), dim3(256), 0, ctx->stream, desc, N, n_dp, tot, W.sizing(), (int)no_mw, (int)no_groups,
+                       ctx->dp_band_from, dp_class_mode());
+    const DpScoring sc = dp_scoring_of(scoring);
+    DpFrontRun R;
+    rc = dpf_run(ctx, W, N, n_dp, sc, ht, R);
     if (rc) return rc;
-    uint32_t *fk = ok == k1 ? k2 : k1, *fv = ov == v1 ? v2 : v1;
-    const DpBigPick bp{ov, cand, cls, est, tot, fk, dp_wide_min(), (uint32_t)dp_big_max()};
-    hipLaunchKernelGGL((cmp_count<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, bcnt);
-    hipLaunchKernelGGL((cmp_write<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, bcnt);
-    uint32_t *ck = fk, *cv = ov;
-    rc = sort_pairs_u32(ctx, n_dp, 3, &ck, &cv, k3, fv, MAUVE_K_MISC);
-    if (rc) return rc;
-    hipLaunchKernelGGL(dpf_list, dim3(blk_d), dim3(256), 0, ctx->stream, ck, cv, tot, ctx->dp_list.as<int64_t>());
-    int64_t *tb_list_dev = d_col_off;
-    hipLaunchKernelGGL((vscan_partial<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{need, cv}, n_dp, bsum2);
-    hipLaunchKernelGGL((vscan_write<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{need, cv}, n_dp, bsum2, tb_list_dev, &tot->tb);
-    hipLaunchKernelGGL(dpf_tb_scatter, dim3(blk_d), dim3(256), 0, ctx->stream, tb_list_dev, cv, n_dp, d_tb_off);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ht, tot, sizeof(DpFrontTotals), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t total = ht->codes, tbt = ht->tb, rwt = ht->rows;
-    DpClasses cl; memset(&cl, 0, sizeof cl);
-    const int64_t n_big = ht->first_med;
-    cl.first_med = ht->first_med; cl.n_med = ht->first_c - ht->first_med;
-    cl.first_c = ht->first_c; cl.n_c = ht->first_s32 - ht->first_c;
-    cl.first_s32 = ht->first_s32; cl.n_s32 = ht->first_s16 - ht->first_s32;
-    cl.first_s16 = ht->first_s16; cl.n_s16 = (int64_t)n_dp - ht->first_s16;
-    const double t1 = now_ms();
-    HIPCHK(ctx, ctx->dp_codes.ensure((size_t)total + 16));
-    HIPCHK(ctx, ctx->dp_prof_cnt.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof2_cnt.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_prof2_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_tb.ensure((size_t)std::min<int64_t>(tbt, dp_tb_budget()) + 64));
-    HIPCHK(ctx, ctx->dp_rows.ensure((size_t)(rwt + 1) * 4));
-    HIPCHK(ctx, ctx->dp_score.ensure((size_t)total + 16));
-    HIPCHK(ctx, ctx->dp_cols.ensure((size_t)(total + 1) * 4));
-    std::vector<int64_t> &tb_list = ctx->dph.tb_list; tb_list.clear();
-    if (tbt > dp_tb_budget()) {
-        tb_list.resize((size_t)n_dp + 1);
-        HIPCHK(ctx, hipMemcpy(tb_list.data(), tb_list_dev, ((size_t)n_dp + 1) * 8, hipMemcpyDeviceToHost));
-    }
-    {
-        DpGenomeWords gw; memset(&gw, 0, sizeof gw);
-        for (int g = 0; g < ctx->nseq; g++) gw.word_off[g] = ctx->word_off[g];
-        const int64_t nd = (int64_t)n_dp * N;
-        hipLaunchKernelGGL(dp_gather_codes, dim3((uint32_t)std::min<int64_t>((nd + 15) / 16, 256 * 8)), dim3(256), 0, ctx->stream, ctx->genomes.as<uint64_t>(), gw, desc, d_seq_off, nd,
-                           ctx->dp_codes.as<uint8_t>());
-    }
-    DpScoring sc; sc.go = scoring->gap_open; sc.ge = scoring->gap_extend; memcpy(sc.s, scoring->matrix, sizeof sc.s);
-    int rounds = 1;
-    rc = dp_launch_rounds(ctx, N, n_dp, n_big, cl, d_seq_off, d_tb_off, d_rows_off, sc, tb_list.empty() ? nullptr : tb_list.data(), &rounds, ctx->dp_band_from);
-    if (rc) return rc;
-    const DpMeta *meta = ctx->dp_meta.as<DpMeta>();
-    int64_t *d_score = need;
-    hipLaunchKernelGGL((vscan_partial<int64_t, MetaCols>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCols{meta}, n_dp, bsum);
-    hipLaunchKernelGGL((vscan_write<int64_t, MetaCols>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCols{meta}, n_dp, bsum, d_col_off, &tot->cols);
-    hipLaunchKernelGGL((vscan_partial<int64_t, MetaCells>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCells{meta}, n_dp, bsum2);
-    hipLaunchKernelGGL((vscan_write<int64_t, MetaCells>), dim3(nbd), dim3(256), 0, ctx->stream, MetaCells{meta}, n_dp, bsum2, rowsn /*scratch*/, &tot->cells);
-    hipLaunchKernelGGL(dpf_scores, dim3(blk_d), dim3(256), 0, ctx->stream, meta, n_dp, d_score, tot);
-    hipLaunchKernelGGL(dp_gather, dim3((uint32_t)std::min<int64_t>(((int64_t)n_dp + 3) / 4, 256 * 8)), dim3(256), 0, ctx->stream, N, (int64_t)n_dp, d_seq_off, meta,
-                       ctx->dp_prof_mask.as<uint32_t>(), ctx->dp_prof2_mask.as<uint32_t>(), d_col_off, ctx->dp_cols.as<uint32_t>());
-    HIPCHK(ctx, hipGetLastError());
+    int64_t *d_col_off = W.d_col_off, *d_score = W.need;                 // where dpf_run leaves the offsets and scores
     HIPCHK(ctx, ctx->pin_meta.ensure(((size_t)n_dp * 3 + 2) * 8));
     int64_t *p_off = ctx->pin_meta.as<int64_t>(), *p_score = p_off + n_dp + 1, *p_sp = p_score + n_dp;
     if (sp && N >= 2) {                     // the refinement's objective, from the columns while they are here
         HIPCHK(ctx, ctx->dp_sp.ensure((size_t)n_dp * 8 + 64));
-        hipLaunchKernelGGL(dp_sp_scores, dim3((uint32_t)std::min<int64_t>(((int64_t)n_dp + 3) / 4, 256 * 16)), dim3(256), 0, ctx->stream, N, (int64_t)n_dp, ctx->dp_codes.as<uint8_t>(), d_seq_off,
+        hipLaunchKernelGGL(dp_sp_scores, dim3((uint32_t)std::min<int64_t>(((int64_t)n_dp + 3) / 4, 256 * 16)), dim3(256), 0, ctx->stream, N, (int64_t)n_dp, ctx->dp_codes.as<uint8_t>(), W.d_seq_off,
                            ctx->dp_cols.as<uint32_t>(), d_col_off, sc, ctx->dp_sp.as<unsigned long long>());
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(p_sp, ctx->dp_sp.p, (size_t)n_dp * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3150,7 +2765,7 @@ int dp_run_from_desc(mauve_ctx *ctx, int N, int64_t n_iv, const DpSeqDesc *h_des
     HIPCHK(ctx, hipMemcpyAsync(p_off, d_col_off, ((size_t)n_dp + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(p_score, d_score, (size_t)n_dp * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ht->err) { ctx->err = "dp: a cluster of workgroups could not make progress on an interval (wide sweep)"; return MAUVE_ERR_HIP; }
+    if (ht->err) { ctx->err = DP_ERR_CLUSTER; return MAUVE_ERR_HIP; }
     const int64_t tc = ht->cols;
     if (cells) *cells = ht->cells;
     memcpy(col_off, p_off, ((size_t)n_dp + 1) * 8);
@@ -3163,7 +2778,7 @@ int dp_run_from_desc(mauve_ctx *ctx, int N, int64_t n_iv, const DpSeqDesc *h_des
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (trace) fprintf(stderr, "[trace] dp (descriptor batch, device front): %u intervals (%lld workgroup, %lld one-wave, %lld two/wave, %lld four/wave), %d round(s); upload+sizing+order %.3f ms, kernels+results %.3f\n",
-                       n_dp, (long long)n_big, (long long)cl.n_med, (long long)cl.n_s32, (long long)cl.n_s16, rounds, t1 - t0, now_ms() - t1);
+                       n_dp, (long long)R.n_big, (long long)R.cl.n_med, (long long)R.cl.n_s32, (long long)R.cl.n_s16, R.rounds, R.t_sized - t0, now_ms() - R.t_sized);
     return MAUVE_OK;
 }
 
