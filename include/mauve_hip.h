@@ -283,6 +283,18 @@ int mauve_align_fetch_compact(mauve_ctx *ctx, int col_bytes,
                               int32_t *anchor_length, int32_t *anchor_start, int32_t *anchor_lcb,
                               int64_t *iv_left, int64_t *iv_right, int8_t *iv_reverse,
                               int64_t *col_off, void *cols, int64_t *dp_score);
+/* Optional, before mauve_align: where that call may leave the two bulk tables of its result, in the types of mauve_align_fetch_compact, while
+   it is still running (no reference counterpart).  The match list and the anchor table are final long before the pass ends -- the gapped
+   alignment and the assembly follow -- so their copies run beside that work on a queue of their own instead of behind it in the fetch.
+   All five pointers are page-locked (mauve_host_alloc); mum_cap and anchor_cap are the capacities in records (mum_length[mum_cap],
+   mum_start[mum_cap * nseq], anchor_length[anchor_cap], anchor_start[anchor_cap * nseq], anchor_lcb[anchor_cap]).  One shot: it holds for
+   the next mauve_align only, whatever path that call takes.  A table whose pointers are NULL or pageable, whose capacity is too small for
+   the result, or that the call's path does not keep on the device (host chains, recursion into gaps, score-weighted LCBs) is simply not sent:
+   nothing fails, and mauve_align_fetch_compact copies it as it always did.  A table that was sent is in place when mauve_align returns; a
+   following mauve_align_fetch_compact that passes the same pointers skips its copy (any other pointer gets a copy from the device as before).
+   The buffers must not be written or freed between this call and that fetch, or the next call on the context if no fetch follows. */
+int mauve_align_prefetch(mauve_ctx *ctx, int32_t *mum_length, int32_t *mum_start, int64_t mum_cap,
+                         int32_t *anchor_length, int32_t *anchor_start, int32_t *anchor_lcb, int64_t anchor_cap);
 /* ---- the same path in three phases, for sharding the gapped alignment of ONE alignment over several GPUs
         (mauveAligner.cpp:130-131 --realign-lcb "for parallelization of LCB alignment").  Every rank
         calls mauve_align_begin (deterministic: identical anchors and interval table everywhere), aligns its

@@ -26,7 +26,7 @@ EXPORTS = [
     "mauve_default_params", "mauve_default_progressive_params", "mauve_packed_words", "mauve_pack_ascii", "mauve_pack_codes", "mauve_set_genomes", "mauve_set_genomes_contigs",
     "mauve_ambiguity_bitmap",
     "mauve_sorted_mer_list", "mauve_seed_mums", "mauve_get_matches", "mauve_extend_hits", "mauve_seed_match_enumerate",
-    "mauve_eliminate_overlaps", "mauve_lcb_chain", "mauve_dp_batch", "mauve_dp_batch_banded", "mauve_match_sp_scores", "mauve_align", "mauve_align_fetch", "mauve_align_fetch_compact",
+    "mauve_eliminate_overlaps", "mauve_lcb_chain", "mauve_dp_batch", "mauve_dp_batch_banded", "mauve_match_sp_scores", "mauve_align", "mauve_align_fetch", "mauve_align_fetch_compact", "mauve_align_prefetch",
     "mauve_align_matches", "mauve_align_lcbs", "mauve_align_begin", "mauve_align_begin_matches", "mauve_align_dp_anchors", "mauve_align_dp_cost", "mauve_align_dp", "mauve_align_finish",
     "mauve_guide_tree", "mauve_breakpoint_counts", "mauve_hmm_params_from", "mauve_apply_homology", "mauve_apply_homology_alignment", "mauve_progressive_align", "mauve_progressive_align_tree",
     "mauve_backbone", "mauve_backbone_alignment", "mauve_backbone_fetch", "mauve_merge_matches",
@@ -90,6 +90,7 @@ def load():
     L.mauve_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
     L.mauve_host_free.argtypes = [C.c_void_p]
     L.mauve_host_free.restype = None
+    L.mauve_align_prefetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
     return L
 
@@ -512,11 +513,25 @@ class Context:
         """out: a ResultBuffers the result arrays are fetched into (reused from call to call; views)"""
         p = params or default_params()
         sz = AlignSizes()
+        if out is not None and compact and not want_xmfa:
+            self._prefetch_tables(out)
         self._chk(self.L.mauve_align(self.h, C.byref(p), C.byref(sz)), "mauve_align")
         res = {k: int(getattr(sz, k)) for k, _ in AlignSizes._fields_}
         if not fetch:
             return res
         return self._fetch(sz, names, want_xmfa, out, compact)
+
+    def _prefetch_tables(self, bufs):
+        """mauve_align_prefetch: the match and anchor tables of the coming mauve_align may travel into `bufs` while the pass runs.  Only the
+        buffers an earlier fetch left in `bufs` are named (ResultBuffers.get hands out views from the base of a block that moves only when it
+        grows, so the fetch that follows passes the same pointers; after a regrow it does not, and the library copies as before)."""
+        N = self.nseq
+        a = [bufs._a.get("c_" + k) for k in ("mum_length", "mum_start", "anchor_length", "anchor_start", "anchor_lcb")]
+        if N < 1 or any(x is None or x.dtype != np.int32 for x in a):
+            return
+        vp = lambda x: x.ctypes.data
+        self._chk(self.L.mauve_align_prefetch(self.h, vp(a[0]), vp(a[1]), min(a[0].size, a[1].size // N), vp(a[2]), vp(a[3]), vp(a[4]),
+                                              min(a[2].size, a[3].size // N, a[4].size)), "mauve_align_prefetch")
 
     def _fetch_compact(self, sz, bufs=None):
         """mauve_align_fetch_compact: columns in 1 / 2 / 4 bytes by the genome count, match and anchor tables as int32"""

@@ -273,7 +273,11 @@ int assemble_device(mauve_ctx *c, int64_t na64, int64_t cells, mauve_align_sizes
     }
     R.dev_alen = fo.alen; R.dev_ast = fo.ast; R.dev_alcb = fo.alcb;
     HIPCHK(c, hipGetLastError());
+    // tables that set out when the chains were final (prefetch_tables_enqueue) have had the DP stage to arrive: the stream joins them here,
+    // so that nothing of them is in flight when the call returns and the buffers they read (pf_mums, ch_anch / ch_anch2) are free again
+    if (c->pf.inflight) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_io_done, 0));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pf.inflight = false;
     const double t1 = now_ms();
     const int64_t *h_col = h_rows, *h_left = h_col + nl + 1, *h_right = h_left + nl * N, *h_score = h_right + nl * N, *h_lw = h_score + nl;
     const int64_t lcb_cols = h_lw[nl];
@@ -338,6 +342,13 @@ int assemble_device(mauve_ctx *c, int64_t na64, int64_t cells, mauve_align_sizes
         }
     }
     R.dev_pending = true; R.cols_pending = true; R.dev_na = host_chains ? 0 : na; R.cols_ext = nullptr;
+    {
+        mauve_ctx::TablePrefetch &P = c->pf;
+        const bool dm = P.got_mums && !host_chains, da = P.got_anchors && !host_chains;
+        R.del_mum_length = dm ? P.mum_length : nullptr; R.del_mum_start = dm ? P.mum_start : nullptr;
+        R.del_alen = da ? P.anchor_length : nullptr; R.del_ast = da ? P.anchor_start : nullptr; R.del_alcb = da ? P.anchor_lcb : nullptr;
+        P.got_mums = P.got_anchors = false;
+    }
     R.cols_fill = 0; R.cols_dirty.clear();                       // the host column buffer no longer holds the "all anchors" state
     R.sz.n_mums = S.nm; R.sz.n_lcb = nl; R.sz.n_anchor = na; R.sz.n_iv = niv; R.sz.n_cols = ncols;
     R.sz.n_gap_dp = fo.n_dp; R.sz.n_dp_cells = cells;
@@ -357,6 +368,7 @@ int assemble_device(mauve_ctx *c, int64_t na64, int64_t cells, mauve_align_sizes
 int materialize_tables(mauve_ctx *c)
 {
     AlignResult &R = c->res;
+    R.del_mum_length = R.del_mum_start = R.del_alen = R.del_ast = R.del_alcb = nullptr;      // whoever comes here is not the fetch the prefetched tables wait for
     if (!R.dev_pending) return MAUVE_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->ast.N; const size_t na = R.dev_na;
@@ -453,16 +465,20 @@ bool fetch_compact_direct(mauve_ctx *c, int col_bytes, int32_t *mum_length, int3
     auto chk = [&](hipError_t e) { if (e != hipSuccess && *rc_out == MAUVE_OK) { c->err = std::string("fetch_compact: ") + hipGetErrorString(e); *rc_out = MAUVE_ERR_HIP; } };
     const int N = c->ast.N; const size_t na = R.dev_na, nm = R.dev_nm;
     bool any = false;
+    // a table that mauve_align_prefetch sent ahead into these very buffers is there already (the pass waited for it: assemble_device)
+    const bool have_m = R.del_mum_length && R.del_mum_length == mum_length && R.del_mum_start == mum_start;
+    const bool have_a = R.del_alen && R.del_alen == anchor_length && R.del_ast == anchor_start && R.del_alcb == anchor_lcb;
+    R.del_mum_length = R.del_mum_start = R.del_alen = R.del_ast = R.del_alcb = nullptr;      // one fetch: the caller may write its buffers afterwards
     if (R.dev_pending && mum_length && mum_start && anchor_length && anchor_start && anchor_lcb &&
-        (!nm || (host_pointer_is_pinned(mum_length) && host_pointer_is_pinned(mum_start))) &&
-        (!na || (host_pointer_is_pinned(anchor_length) && host_pointer_is_pinned(anchor_start) && host_pointer_is_pinned(anchor_lcb)))) {
+        (!nm || have_m || (host_pointer_is_pinned(mum_length) && host_pointer_is_pinned(mum_start))) &&
+        (!na || have_a || (host_pointer_is_pinned(anchor_length) && host_pointer_is_pinned(anchor_start) && host_pointer_is_pinned(anchor_lcb)))) {
         chk(hipSetDevice(c->device));
-        if (na) {
+        if (na && !have_a) {
             chk(hipMemcpyAsync(anchor_length, R.dev_alen, na * 4, hipMemcpyDeviceToHost, c->stream));
             chk(hipMemcpyAsync(anchor_start, R.dev_ast, na * N * 4, hipMemcpyDeviceToHost, c->stream));
             chk(hipMemcpyAsync(anchor_lcb, R.dev_alcb, na * 4, hipMemcpyDeviceToHost, c->stream));
         }
-        if (nm) {
+        if (nm && !have_m) {
             const size_t n = nm * (1 + (size_t)N);
             chk(c->as_wide.ensure(n * 4 + 64));
             if (*rc_out) return true;
@@ -490,6 +506,45 @@ bool fetch_compact_direct(mauve_ctx *c, int col_bytes, int32_t *mum_length, int3
     }
     if (any) chk(hipStreamSynchronize(c->stream));
     return any;
+}
+
+// mauve_align_prefetch, device tail of mauve_align: the anchor table and -- if the seed pass left it on the device only -- the match list go to the
+// buffers the caller named, on stream_io, behind ev_io_fork (recorded on the main stream when the chains were final: align_begin), while the DP
+// kernels and the assembly run on the main stream.  Both are read where they lie -- the match list narrowed into a buffer of its own first --
+// and nothing writes sorted_rec, ch_anch or ch_anch2 before the next call: the DP front end and the assembly only read them, and the assembly
+// waits for ev_io_done.  A table whose buffer is missing or too small stays behind for the fetch.
+int prefetch_tables_enqueue(mauve_ctx *c, int N, int64_t na, const int32_t *alen, const int32_t *ast, const int32_t *alcb)
+{
+    mauve_ctx::TablePrefetch &P = c->pf;
+    P.got_mums = P.got_anchors = false;
+    if (!P.live) return MAUVE_OK;
+    P.live = false;
+    const size_t nm = c->matches_pending && c->dev_rec_n == c->n_matches ? (size_t)c->n_matches : 0;
+    const bool mums = nm && P.mum_length && P.mum_start && (int64_t)nm <= P.mum_cap;
+    const bool anch = na > 0 && P.anchor_length && P.anchor_start && P.anchor_lcb && na <= P.anchor_cap;
+    if (!mums && !anch) return MAUVE_OK;
+    const size_t n = nm * (1 + (size_t)N);
+    if (mums) {
+        HIPCHK(c, c->pf_mums.ensure(n * 4 + 64));
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream_io, c->ev_io_fork, 0));
+    P.inflight = true;
+    if (mums) {
+        hipLaunchKernelGGL(as_narrow_i64, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream_io, c->sorted_rec.as<int64_t>(), n, c->pf_mums.as<int32_t>());
+        HIPCHK(c, hipGetLastError());
+    }
+    if (anch) {
+        HIPCHK(c, hipMemcpyAsync(P.anchor_length, alen, (size_t)na * 4, hipMemcpyDeviceToHost, c->stream_io));
+        HIPCHK(c, hipMemcpyAsync(P.anchor_start, ast, (size_t)na * N * 4, hipMemcpyDeviceToHost, c->stream_io));
+        HIPCHK(c, hipMemcpyAsync(P.anchor_lcb, alcb, (size_t)na * 4, hipMemcpyDeviceToHost, c->stream_io));
+    }
+    if (mums) {
+        HIPCHK(c, hipMemcpyAsync(P.mum_length, c->pf_mums.as<int32_t>(), nm * 4, hipMemcpyDeviceToHost, c->stream_io));
+        HIPCHK(c, hipMemcpyAsync(P.mum_start, c->pf_mums.as<int32_t>() + nm, nm * N * 4, hipMemcpyDeviceToHost, c->stream_io));
+    }
+    HIPCHK(c, hipEventRecord(c->ev_io_done, c->stream_io));
+    P.got_mums = mums; P.got_anchors = anch;
+    return MAUVE_OK;
 }
 
 // ... and the columns into page-locked staging (the XMFA writer, a fetch into pageable memory); idempotent

@@ -136,6 +136,9 @@ struct AlignResult {
     size_t dev_na = 0, dev_nm = 0;          // anchors; matches still on the device (0: mum_* are filled)
     const int32_t *dev_alen = nullptr, *dev_ast = nullptr, *dev_alcb = nullptr;     // ... where the anchors are (chain_order_device's arrays)
     const uint32_t *cols_ext = nullptr;      // the columns in page-locked staging after materialize_result (else: cols)
+    // bulk tables that travelled while the pass ran (mauve_align_prefetch): the caller's buffers they are in, nullptr = not delivered; a fetch
+    // that names the same buffers skips that table's copies (fetch_compact_direct), any fetch uses them up
+    const int32_t *del_mum_length = nullptr, *del_mum_start = nullptr, *del_alen = nullptr, *del_ast = nullptr, *del_alcb = nullptr;
     const uint32_t *cols_data() const { return cols_ext ? cols_ext : cols.data(); }
 };
 
@@ -199,6 +202,19 @@ struct mauve_ctx {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;           // the one-wave DP launch runs here when there are workgroup launches (those go first, on `stream`)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // third queue (with `stream` and `stream2`; the runtime opens four by default): copies that run beside the pass (the bulk tables of mauve_align_prefetch).  It starts behind ev_io_fork, recorded on `stream`,
+    // and `stream` waits on ev_io_done before the pass's last synchronisation: when an entry point returns, nothing is in flight here.
+    hipStream_t stream_io = nullptr;
+    hipEvent_t ev_io_fork = nullptr, ev_io_done = nullptr;
+    struct TablePrefetch {
+        int32_t *mum_length = nullptr, *mum_start = nullptr, *anchor_length = nullptr, *anchor_start = nullptr, *anchor_lcb = nullptr;
+        int64_t mum_cap = 0, anchor_cap = 0;           // records
+        bool armed = false;                             // registered, the next mauve_align takes it
+        bool live = false;                              // ... which is running
+        bool inflight = false;                          // copies queued on stream_io that `stream` has not waited for yet
+        bool got_mums = false, got_anchors = false;     // what they deliver
+    } pf;
+    DevBuf pf_mums;                      // the match list narrowed to int32 on its way out (as_wide belongs to the fetch)
     std::string err;
     char devname[256] = {0};
     int cus = 256;                       // compute units of the device (launches sized to a whole number of waves per SIMD)
@@ -452,6 +468,8 @@ int materialize_tables(mauve_ctx *c);
 int fetch_columns(mauve_ctx *c, uint32_t *dst);
 bool fetch_compact_direct(mauve_ctx *c, int col_bytes, int32_t *mum_length, int32_t *mum_start, int32_t *anchor_length, int32_t *anchor_start, int32_t *anchor_lcb,
                           void *cols, bool *tables_done, bool *cols_done, int *rc_out);
+// device tail of mauve_align: the two bulk tables start for the buffers mauve_align_prefetch named (assemble_dev.hip)
+int prefetch_tables_enqueue(mauve_ctx *c, int N, int64_t na, const int32_t *alen, const int32_t *ast, const int32_t *alcb);
 bool fetch_tables_direct(mauve_ctx *c, int64_t *mum_length, int64_t *mum_start, int64_t *anchor_length, int64_t *anchor_start, int64_t *anchor_lcb, int *rc_out);
 bool host_pointer_is_pinned(const void *p);
 int host_genomes(mauve_ctx *c);

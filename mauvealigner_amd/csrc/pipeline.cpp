@@ -425,6 +425,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
                 if (ext_declined) { S.dv_len = S.dv_st = S.dv_lcb = nullptr; }
                 else if (na >= 2 && (!p->recursive || nrec == 0)) {
                     S.nl = nl; S.n_anchor = na; S.dev_tail = true;
+                    if (c->pf.live) HIPCHK(c, hipEventRecord(c->ev_io_fork, c->stream));      // both bulk tables are final behind this point (mauve_align_prefetch)
                     const double t2 = now_ms();
                     c->stage.chain_ms = t2 - t1;
                     if (g_trace_pipeline) fprintf(stderr, "[trace] chain: on the device %.3f ms, %lld anchors in %lld LCBs stay there\n", t2 - t1, (long long)na, (long long)nl);
@@ -868,9 +869,43 @@ static int align_tail_host_chains(mauve_ctx *c, mauve_align_sizes *sizes)
 
 extern "C" {
 
+// where the next mauve_align may leave the two bulk tables while it is still running (mauve_hip.h)
+int mauve_align_prefetch(mauve_ctx *c, int32_t *mum_length, int32_t *mum_start, int64_t mum_cap, int32_t *anchor_length, int32_t *anchor_start,
+                         int32_t *anchor_lcb, int64_t anchor_cap)
+{
+    if (!c) return MAUVE_ERR_ARG;
+    mauve_ctx::TablePrefetch &P = c->pf;
+    // the same buffers as last time (a loop over one set of result buffers): not asked about again -- five queries cost more than a launch, and
+    // page-locked memory is what makes the copies overlap, not what makes them right
+    if (mum_cap > 0 && anchor_cap > 0 && P.mum_length && P.anchor_length && mum_length == P.mum_length && mum_start == P.mum_start && mum_cap == P.mum_cap &&
+        anchor_length == P.anchor_length && anchor_start == P.anchor_start && anchor_lcb == P.anchor_lcb && anchor_cap == P.anchor_cap) { P.armed = true; return MAUVE_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool m = mum_cap > 0 && host_pointer_is_pinned(mum_length) && host_pointer_is_pinned(mum_start);
+    const bool a = anchor_cap > 0 && host_pointer_is_pinned(anchor_length) && host_pointer_is_pinned(anchor_start) && host_pointer_is_pinned(anchor_lcb);
+    P.mum_length = m ? mum_length : nullptr; P.mum_start = m ? mum_start : nullptr; P.mum_cap = m ? mum_cap : 0;
+    P.anchor_length = a ? anchor_length : nullptr; P.anchor_start = a ? anchor_start : nullptr; P.anchor_lcb = a ? anchor_lcb : nullptr; P.anchor_cap = a ? anchor_cap : 0;
+    P.armed = m || a;
+    return MAUVE_OK;
+}
+
+static int align_whole(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes);
+
 int mauve_align(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
 {
     if (!c || !p || !sizes) return MAUVE_ERR_ARG;
+    mauve_ctx::TablePrefetch &P = c->pf;
+    P.live = P.armed; P.armed = false;                   // one shot: this call, whichever path it takes
+    const int rc = align_whole(c, p, sizes);
+    P.live = false;
+    if (P.inflight) {                                    // the call ended between the tables' start and the assembly's wait for them (an error)
+        (void)hipStreamSynchronize(c->stream_io);
+        P.inflight = false; P.got_mums = P.got_anchors = false;
+    }
+    return rc;
+}
+
+static int align_whole(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
+{
     { const int rg = refuse_past_2g(c, "align"); if (rg) return rg; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -884,9 +919,14 @@ int mauve_align(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
         // chains, DP and assembly on the device: anchors from chain_order_device, results left in HBM until they are fetched
         const int32_t *d_len = S.dv_len, *d_st = S.dv_st, *d_lcb = S.dv_lcb;
         c->dp_band_from = dp_band_from_of(&S.p);
+        // the tables of mauve_align_prefetch set out while the DP kernels run: the host queues their copies where it would only wait (the shadow slot),
+        // not between the small launches of the DP front end, which the host paces
+        int rc_pf = MAUVE_OK;
+        if (c->pf.live) { const int N = S.N; const int64_t na = S.n_anchor; c->shadow = [=, &rc_pf]() { rc_pf = prefetch_tables_enqueue(c, N, na, d_len, d_st, d_lcb); }; }
         rc = dp_run_from_anchors(c, S.N, S.n_anchor, d_len, d_st, d_lcb, S.p.gapped, dp_len_limit(&S.p), &S.p.scoring, nullptr, &S.n_dp, &S.code_total,
                                  nullptr, S.dcol_off, S.dscore, &cells, 1);
-        if (rc) return rc;
+        if (c->shadow) { std::function<void()> f; f.swap(c->shadow); if (!rc) f(); }      // no interval went to the DP: nothing ran it
+        if (rc || rc_pf) return rc ? rc : rc_pf;
         return assemble_device(c, S.n_anchor, cells, sizes);
     }
     if (host_front) {
