@@ -114,6 +114,21 @@ struct HostHits { uint32_t n; const uint32_t *rec; };
 // SeedMatchEnumerator on the device: rule in, CSR result out (mult / start_off / starts may be null: counts only)
 struct EnumRequest { int64_t min_multi, max_multi; int direct_only; int64_t n, ns; int64_t *mult, *start_off, *starts; };
 
+// What one seed pass is asked to do; the entry points of seed_pass.hip fill it.
+struct SeedRequest {
+    int mode = MAUVE_MODE_MEM;
+    uint64_t mask = 0;
+    int extend = 0;
+    int only_seq = -1;                           // >= 0: the sorted mer list of that genome alone (the two exports)
+    const uint32_t *seg = nullptr;               // segmented set (recursive anchoring): device array [nseq][nseg + 1] of segment starts
+    uint32_t nseg = 0;
+    const HostHits *hits = nullptr;              // mauve_extend_hits: the hits come from the host, no sort, no join
+    EnumRequest *enumerate = nullptr;            // mauve_seed_match_enumerate: rule in, CSR result out
+    std::vector<uint64_t> *out_keys = nullptr;   // sorted-mer-list export
+    std::vector<uint32_t> *out_vals = nullptr;
+    int64_t *n_matches = nullptr;
+};
+
 struct AlignResult {
     mauve_align_sizes sz{};
     std::vector<int64_t> mum_length, mum_start;
@@ -273,8 +288,6 @@ struct mauve_ctx {
     // last match list (canonical order, host) + nseq it refers to
     std::vector<int64_t> match_len, match_start;
     int64_t n_matches = 0;
-    EnumRequest *enum_req = nullptr;       // set for the duration of mauve_seed_match_enumerate
-    const HostHits *host_hits = nullptr;  // set for the duration of mauve_extend_hits
     int64_t dev_rec_n = -1;              // >= 0: sorted_rec holds that many records (int64 length[n], start[n*nseq]) in canonical order
 
     // DP workspace
@@ -411,6 +424,32 @@ int seedpass_sorted_list(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t 
 
 int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io, uint32_t **vals_io, uint32_t *keys_alt, uint32_t *vals_alt,
                    int timer_id);
+int sort_pairs_u64(mauve_ctx *ctx, uint32_t n, int key_bits, uint64_t **keys_io, uint32_t **vals_io, uint64_t *keys_alt, uint32_t *vals_alt,
+                   int timer_id);
+// The two translation units of the seed pass: seed_pass.hip (everything that depends on the key and index widths) hands over to
+// seed_finish.hip once the ncand candidate records of all finder passes are in ctx->mlen / mstart (on_host: in ctx->sdh.hl / hs
+// already): the guide tree's per-pair sums (ctx->pair_sums_only) or the match list in canonical order.
+int seed_finish(mauve_ctx *ctx, const GenomeSet &gs, const SeedRequest &rq, uint32_t ncand, bool on_host, double &trace_t0);
+bool seed_trace_on();                    // MAUVE_TRACE
+uint32_t canon_device_min();             // candidates from which the canonical order is made on the device (below: the host sorts)
+inline void seed_trace(mauve_ctx *ctx, const char *label, double &t0)
+{
+    if (!seed_trace_on()) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    const double t = now_ms();
+    fprintf(stderr, "[trace] %-22s +%.3f ms\n", label, t - t0);
+    t0 = t;
+}
+// The first `bytes` of the seed pass's counter block, in page-locked memory once the stream has drained.  (pin_seed also carries
+// slice tables and records behind its first 64 bytes: whoever reuses it has synchronised first.)
+inline int seed_counters(mauve_ctx *ctx, size_t bytes, const uint32_t **words)
+{
+    HIPCHK(ctx, ctx->pin_seed.ensure(64));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *words = ctx->pin_seed.as<uint32_t>();
+    return MAUVE_OK;
+}
 // device chain (chain_dev.hip): EliminateOverlaps + LCBs of the N-way list the seed pass left in ctx->sorted_rec
 int chain_device(mauve_ctx *c, int N, int64_t min_weight, bool collinear, MatchVec &m, std::vector<int64_t> &match_lcb, int64_t &n_lcb, const mauve_scoring *sp_scoring = nullptr);
 struct ChainGraphHost { uint32_t na, K; int64_t *weight; uint32_t *orient; int32_t *prev, *next; int32_t *final_stage; int32_t *final_dev; };

@@ -8,6 +8,8 @@
 // progressiveMauve.cpp:490-501), with the in-tree rules of UniqueMatchFinder.cpp:36-60 and
 // SeedMatchEnumerator.h:71-141.  Semantics are frozen in DESIGN.md S3/S4 and checked bit-exactly
 // against oracle/ by tests/ (the oracle is never linked here).
+// The host side runs a pass in stages (seedpass_stages); what follows the extension -- the guide tree's sums, the canonical order --
+// does not depend on the key and index widths and lives in seed_finish.hip.
 //
 // All kernels are HBM-bound integer work: coalesced 4/8-byte streams, LDS staging for
 // the scatter, wave64 ballots for ranking and for the extension walk.  No MFMA by design.
@@ -17,9 +19,7 @@
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
-
-static const bool g_trace = getenv("MAUVE_TRACE") != nullptr;
-#define TRACE(ctx, label) do { if (g_trace) { (void)hipStreamSynchronize((ctx)->stream); double t__ = now_ms(); fprintf(stderr, "[trace] %-22s +%.3f ms\n", label, t__ - trace_t0); trace_t0 = t__; } } while (0)
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // device helpers
@@ -83,29 +83,10 @@ __device__ __forceinline__ uint32_t digit_reverse32(uint32_t k, int weight)
     return ((x & 0xAAAAAAAAu) >> 1) | ((x & 0x55555555u) << 1);
 }
 
-// the 2-bit window of `span` bases starting at base p, as a 128-bit little-endian digit string
-__device__ __forceinline__ void window_at(const uint64_t *__restrict__ G, uint32_t p, uint64_t &lo, uint64_t &hi)
-{
-    uint32_t q = p >> 5; int r = (p & 31) * 2;
-    uint64_t w0 = G[q], w1 = G[q + 1], w2 = G[q + 2];
-    lo = r ? ((w0 >> r) | (w1 << (64 - r))) : w0;
-    hi = r ? ((w1 >> r) | (w2 << (64 - r))) : w1;
-}
-
 __device__ __forceinline__ uint64_t digit_reverse64(uint64_t x)
 {
     x = __brevll(x);
     return ((x & 0xAAAAAAAAAAAAAAAAULL) >> 1) | ((x & 0x5555555555555555ULL) << 1);
-}
-
-// reverse complement of a span-base window (digits reversed, complemented); bits above 2*span are garbage
-// that the care mask removes
-__device__ __forceinline__ void window_revcomp(uint64_t lo, uint64_t hi, int span, uint64_t &rlo, uint64_t &rhi)
-{
-    const uint64_t nlo = digit_reverse64(~hi), nhi = digit_reverse64(~lo);   // 128-bit digit reversal
-    const int s = 128 - 2 * span;                                            // 30 <= s <= 126 (span 1..49)
-    if (s >= 64) { rlo = nhi >> (s - 64); rhi = 0; }
-    else { rlo = (nlo >> s) | (nhi << (64 - s)); rhi = nhi >> s; }
 }
 
 // reverse the order of the 2-bit digits of a 2*weight-bit value
@@ -834,7 +815,7 @@ __global__ void __launch_bounds__(256) hits_scatter(const uint32_t *__restrict__
 // ------------------------------------------------------------------------------------------------
 // PairwiseMatchFinder: N(N-1)/2 finder passes over ONE sorted mer list.  Instead of re-reading all P sorted entries
 // per pair, one pass (run_summary) lists the runs of identical mers that could matter to any pair -- where the run
-// starts, how long it is, which genomes occur in it exactly once -- and each pair's join (join_pair) walks that
+// starts, how long it is, which genomes occur in it exactly once -- and the join of a group of pairs (join_pair_group) walks that
 // list: a run is a hit of pair (i, j) iff both genomes are in its exactly-once set (MemHash restricted to the two
 // genomes: entries of the others are invisible to it).  The order of the list does not matter: hits go to the
 // dense table by anchor position.
@@ -878,30 +859,6 @@ __global__ void __launch_bounds__(256) run_summary(const KeyT *__restrict__ keys
 #pragma unroll
     for (int it = 0; it < ITEMS; it++)
         if (uniq[it]) { if (r < cap) { rstart[r] = base + it * 256 + threadIdx.x; rlen[r] = len[it]; runiq[r] = uniq[it]; } r++; }   // (the counter keeps counting: the host sees a list that outgrew its buffer)
-}
-
-template <typename ValT = uint32_t>
-__global__ void __launch_bounds__(256) join_pair(const ValT *__restrict__ vals, GenomeTab tab, const uint32_t *__restrict__ rstart,
-                                                 const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ runiq,
-                                                 uint32_t nruns, int gi, int gj, uint32_t *__restrict__ tmask,
-                                                 uint32_t *__restrict__ tpos)
-{
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nruns) return;
-    const uint32_t u = runiq[r];
-    if (!((u >> gi) & (u >> gj) & 1u)) return;
-    const uint32_t s = rstart[r], L = rlen[r];
-    ValT vi = 0, vj = 0;
-    for (uint32_t t = s; t < s + L; t++) {
-        const ValT v = vals[t];
-        const int g = genome_of(win_idx(v), tab);
-        if (g == gi) vi = v;
-        if (g == gj) vj = v;
-    }
-    const uint32_t ap = win_idx(vi);                    // gi < gj: the anchor is genome gi's window
-    tmask[ap] = (1u << gi) | (1u << gj);
-    tpos[(size_t)ap * tab.nseq + gi] = hit_word(vi, tab.gpos_off[gi]);
-    tpos[(size_t)ap * tab.nseq + gj] = hit_word(vj, tab.gpos_off[gj]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1309,7 +1266,6 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const uint64_t spanmask = (sh.span >= 64) ? ~0ULL : ((1ULL << sh.span) - 1ULL);
     const int N = tab.nseq;
     ExtComp *comp = s_comp[wv];
 #ifdef MAUVE_EXT_STATS
@@ -1428,137 +1384,28 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
     }
 #endif
 }
-
-// ------------------------------------------------------------------------------------------------
-// canonical order on the device (large candidate sets): key = first component << pos_bits | |its start| per candidate
-// (pos_bits = bits of the longest genome: fewer radix passes than a fixed 32)
-// (dropped candidates get first component = nseq and sort behind everything), the radix sort above on
-// (key, candidate index), then a gather of the surviving records as int64 in sorted order.
-// ------------------------------------------------------------------------------------------------
-// guide tree (progressive.cpp): all it needs of the pairwise matches is the sum of their lengths per genome pair -- no
-// canonical order, no copy of the (hundreds of thousands of) records.  Block-level sums in LDS, then one atomic per pair.
-__global__ void __launch_bounds__(256) pair_length_sums(const int32_t *__restrict__ mlen, const int32_t *__restrict__ mstart, uint32_t ncand,
-                                                        int nseq, unsigned long long *__restrict__ sums)
-{
-    __shared__ unsigned long long s[MAUVE_MAX_SEQ * MAUVE_MAX_SEQ];
-    for (int i = threadIdx.x; i < nseq * nseq; i += 256) s[i] = 0;
-    __syncthreads();
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < ncand; i += gridDim.x * 256u) {
-        const int32_t len = mlen[i];
-        if (len == 0) continue;
-        int a = -1, b = -1;
-        for (int g = 0; g < nseq; g++) if (mstart[(size_t)i * nseq + g]) { if (a < 0) a = g; else if (b < 0) b = g; }
-        if (b >= 0) atomicAdd(&s[a * nseq + b], (unsigned long long)len);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nseq * nseq; i += 256) if (s[i]) atomicAdd(&sums[i], s[i]);
-}
-
-// ---- pairwise breakpoint estimate (progressive.cpp scales node weights by it) ----
-// Of every genome pair's matches (length >= min_len): order by position in the lower genome, rank by position in the higher one,
-// and count the adjacencies that are not conserved.  Small kernels around three stable radix sorts of (pair, position) keys: by the
-// higher genome first (position, strand), so that the order along the lower genome breaks its ties that way, then the ranks.
-__device__ __forceinline__ bool bp_pair_of(const int32_t *__restrict__ st, int nseq, int *a, int *b)
-{
-    int x = -1, y = -1;
-    for (int g = 0; g < nseq; g++) if (st[g]) { if (x < 0) x = g; else if (y < 0) y = g; }
-    *a = x; *b = y;
-    return y >= 0;
-}
-// which = 1: key by the higher genome (position, strand bit); 0: by the lower genome.  order == nullptr: record j itself (first sort:
-// records that do not count get the pair id nseq * nseq, behind every pair).  vals: the record index (keep_record) or j.
-__global__ void __launch_bounds__(256) bp_keys(const int32_t *__restrict__ mlen, const int32_t *__restrict__ mstart, const uint32_t *__restrict__ order, uint32_t n, int nseq,
-                                               int pos_bits, int32_t min_len, int which, int keep_record, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
-                                               uint32_t *__restrict__ n_valid)
-{
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    bool valid = false;
-    if (j < n) {
-        const uint32_t i = order ? order[j] : j;
-        uint64_t key = (uint64_t)(nseq * nseq) << (pos_bits + 1);
-        const int32_t len = mlen[i];
-        int a, b;
-        if (len != 0 && len >= min_len && bp_pair_of(mstart + (size_t)i * nseq, nseq, &a, &b)) {
-            const int32_t sx = mstart[(size_t)i * nseq + (which ? b : a)];
-            key = ((uint64_t)(a * nseq + b) << (pos_bits + 1)) | ((uint64_t)(sx < 0 ? -sx : sx) << 1) | (uint64_t)(sx < 0);
-            valid = true;
-        }
-        keys[j] = key; vals[j] = keep_record ? i : j;
-    }
-    if (n_valid) { const uint64_t bal = __ballot(valid); if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_valid, (uint32_t)__popcll(bal)); }
-}
-__global__ void __launch_bounds__(256) bp_rank(const uint32_t *__restrict__ order_b, uint32_t nv, uint32_t *__restrict__ rank)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < nv) rank[order_b[t]] = t;
-}
-__global__ void __launch_bounds__(256) bp_count(const uint64_t *__restrict__ keys_a, const uint32_t *__restrict__ order_a, const uint32_t *__restrict__ rank,
-                                                const int32_t *__restrict__ mstart, uint32_t nv, int nseq, int pos_bits, unsigned long long *__restrict__ out)
-{
-    __shared__ uint32_t s[MAUVE_MAX_SEQ * MAUVE_MAX_SEQ];
-    for (int i = threadIdx.x; i < nseq * nseq; i += 256) s[i] = 0;
-    __syncthreads();
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j + 1 < nv; j += gridDim.x * 256u) {
-        const uint32_t pair = (uint32_t)(keys_a[j] >> (pos_bits + 1));
-        if ((uint32_t)(keys_a[j + 1] >> (pos_bits + 1)) != pair) continue;
-        const uint32_t b = pair % (uint32_t)nseq;
-        const int32_t s0 = mstart[(size_t)order_a[j] * nseq + b], s1 = mstart[(size_t)order_a[j + 1] * nseq + b];
-        const uint32_t r0 = rank[j], r1 = rank[j + 1];
-        const bool conserved = (s0 > 0 && s1 > 0 && r1 == r0 + 1) || (s0 < 0 && s1 < 0 && r1 + 1 == r0);
-        if (!conserved) atomicAdd(&s[pair], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nseq * nseq; i += 256) if (s[i]) atomicAdd(&out[i], (unsigned long long)s[i]);
-}
-
-__global__ void __launch_bounds__(256) canon_keys(const int32_t *__restrict__ mlen, const int32_t *__restrict__ mstart, uint32_t ncand,
-                                                  int nseq, int pos_bits, int inval, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
-                                                  uint32_t *__restrict__ n_valid)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool valid = false;
-    if (i < ncand) {
-        uint64_t key = (uint64_t)inval << pos_bits;                 // dropped candidates: behind every match
-        if (mlen[i] != 0) {
-            const int32_t *s = mstart + (size_t)i * nseq;
-            int f = 0; while (f < nseq && s[f] == 0) f++;
-            const uint32_t a = f < nseq ? (uint32_t)(s[f] < 0 ? -s[f] : s[f]) : 0u;
-            key = ((uint64_t)f << pos_bits) | a;
-            valid = true;
-        }
-        keys[i] = key; vals[i] = i;
-    }
-    const uint64_t b = __ballot(valid);
-    if (b && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)b) - 1)) atomicAdd(n_valid, (uint32_t)__popcll(b));
-}
-
-// The number of surviving records is still on the device (*n_valid): the launch covers all candidates, the output is
-// out[0 .. nm) lengths followed by nm * nseq starts.  Two neighbours with the same key (first component, start) are a
-// tie the key alone does not order: *ties is raised and the host finishes the order (rare).
-__global__ void __launch_bounds__(256) canon_gather(const int32_t *__restrict__ mlen, const int32_t *__restrict__ mstart,
-                                                    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
-                                                    const uint32_t *__restrict__ n_valid, int nseq, int64_t *__restrict__ out,
-                                                    uint32_t *__restrict__ ties)
-{
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t nm = *n_valid;
-    if (r >= nm) return;
-    int64_t *out_len = out, *out_start = out + nm;
-    if (r > 0 && keys[r] == keys[r - 1]) atomicOr(ties, 1u);
-    const uint32_t src = vals[r];
-    out_len[r] = mlen[src];
-    for (int g = 0; g < nseq; g++) out_start[(size_t)r * nseq + g] = mstart[(size_t)src * nseq + g];
-}
-
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// candidates from which the canonical order is made on the device (below: the host sorts; MAUVE_CANON_DEVICE_MIN: tests force the device path)
-static uint32_t canon_device_min()
+// The switches that tests and tools set ("Seed pass host side", names who sets which).  Each is read once, when it
+// is first asked for -- not when the library is loaded: a test sets MAUVE_CANON_DEVICE_MIN after it has opened its context.
+bool seed_trace_on() { static const bool v = getenv("MAUVE_TRACE") != nullptr; return v; }
+// a pass of a few thousand windows takes the hash join like any other
+static bool no_tiny() { static const bool v = getenv("MAUVE_NO_TINY") != nullptr; return v; }
+// MAUVE_SMALL_SORT=0: sorts of up to SS_CAP pairs take the tiled path too
+static bool small_sort_on() { static const bool v = [] { const char *e = getenv("MAUVE_SMALL_SORT"); return !(e && e[0] == '0'); }(); return v; }
+// shrinks the compacted lists so that the capacity checks can be seen to fire (0: off)
+static uint32_t list_cap_env() { static const uint32_t v = getenv("MAUVE_LIST_CAP") ? (uint32_t)strtoul(getenv("MAUVE_LIST_CAP"), nullptr, 10) : 0u; return v; }
+// candidates from which the canonical order is made on the device (below: the host sorts; tests force the device path)
+uint32_t canon_device_min() { static const uint32_t v = getenv("MAUVE_CANON_DEVICE_MIN") ? (uint32_t)atol(getenv("MAUVE_CANON_DEVICE_MIN")) : 16384u; return v; }
+// Index width of a seed pass (DESIGN.md S3): wide values when the pass has 2^31 windows or more; MAUVE_WIDE_INDEX=1 forces them for every
+// pass (test switch: small inputs take the wide kernels against the oracle).  Every other pass runs the narrow instantiations.
+bool seedpass_wide(int64_t total_windows)
 {
-    static const uint32_t v = getenv("MAUVE_CANON_DEVICE_MIN") ? (uint32_t)atol(getenv("MAUVE_CANON_DEVICE_MIN")) : 16384u;
-    return v;
+    static const bool force = [] { const char *e = getenv("MAUVE_WIDE_INDEX"); return e && e[0] == '1' && e[1] == 0; }();
+    return force || total_windows >= (1LL << 31);
 }
+
 bool make_seed_shape(uint64_t pattern, SeedShape *sh)
 {
     memset(sh, 0, sizeof *sh);
@@ -1615,8 +1462,7 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
     // per-kernel figures of the main sort)
     const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scan = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCAN,
               k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
-    static const bool small_on = [] { const char *e = getenv("MAUVE_SMALL_SORT"); return !(e && e[0] == '0'); }();   // A/B switch
-    if (small_on && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
+    if (small_sort_on() && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
         HIPCHK(ctx, ctx->hist.ensure(ss_ws_words(n) * sizeof(uint32_t)));
         small_sort<KeyT>(ctx->stream, n, key_bits, shift_lo, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
                          [&](bool scatter, auto &&launch) { KernelTimer t(ctx, scatter ? k_scat : k_hist, n); launch(); });
@@ -1631,8 +1477,7 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
         if (!(shift == shift_lo && have_hist0)) { KernelTimer t(ctx, k_hist, n);
           hipLaunchKernelGGL(rs_hist<KeyT>, dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, n, shift,
                              ctx->hist.as<uint32_t>(), nblk); }
-        static const bool no_raw = getenv("MAUVE_SORT_ROWSCAN") != nullptr;        // A/B switch
-        if (nblk <= 64 && !no_raw) {      // small sort: no row scan launch, the scatter reads the raw tile histograms
+        if (nblk <= 64) {      // small sort: no row scan launch, the scatter reads the raw tile histograms
             KernelTimer t(ctx, k_scat, n);
             hipLaunchKernelGGL((rs_scatter<KeyT, true, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
                                shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk);
@@ -1652,793 +1497,637 @@ static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, 
     return MAUVE_OK;
 }
 
-// One seed pass over a genome set.  SEG: the set is segmented (recursive anchoring); seg = device array
-// [nseq][nseg+1] of segment starts.  Results land in ctx->match_len / match_start (canonical order).
-// ValT: the sort value, uint32_t (narrow) or uint64_t (wide: a pass of 2^31 windows or more, or MAUVE_WIDE_INDEX=1).  A wide
-// pass's hit table and host-side hit records hold windows local to their genome (hit_word); out_vals are then local too.
-template <typename KeyT, bool SEG, typename ValT = uint32_t>
-static int seedpass_impl(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, int64_t total,
-                         int mode, uint64_t mask, int extend, int only_seq, const uint32_t *seg, uint32_t nseg,
-                         int64_t *n_matches, std::vector<uint64_t> *out_keys, std::vector<uint32_t> *out_vals)
+// stable LSD radix sort of (32-bit key, 32-bit value) pairs for the other translation units (chain_dev.hip) ...
+int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io, uint32_t **vals_io, uint32_t *keys_alt, uint32_t *vals_alt,
+                   int timer_id)
 {
-    constexpr bool WIDEV = sizeof(ValT) == 8;
-    const uint32_t n = (uint32_t)total;
-    double trace_t0 = now_ms();
-    if (g_trace) fprintf(stderr, "[trace] seed pass: %u windows, %d-bit keys, %s window index (%d-bit values)\n", n, (int)sizeof(KeyT) * 8,
-                         WIDEV ? "wide" : "narrow", (int)sizeof(ValT) * 8);
+    return sort_pairs<uint32_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
+}
+// ... and of (64-bit key, 32-bit value) pairs (seed_finish.hip)
+int sort_pairs_u64(mauve_ctx *ctx, uint32_t n, int key_bits, uint64_t **keys_io, uint32_t **vals_io, uint64_t *keys_alt, uint32_t *vals_alt,
+                   int timer_id)
+{
+    return sort_pairs<uint64_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
+}
+
+// ---- what the stages of a pass share ----
+struct FinderPass { uint32_t consider, want; int rule; };
+
+// The decisions of a pass, made once (seed_plan) and read by the stages.
+struct SeedPlan {
+    bool seg;           // segmented set
+    bool hash_path;     // partial sort + join_hash (else: full sort)
+    bool tiny;          // no key arrays at all: tiny_join
+    bool compact;       // only the valid windows go into the sort (valid_count / seed_extract_compact)
+    bool has_invalid;   // some windows are unusable (placed or ambiguous bases, contig joins) and sit in the sorted list, with all-ones keys
+    bool use_summary;   // pairwise finder over several pairs: one run list for all of them (run_summary)
+    int segbits;        // segmented keys: segment id above the mer; ids 0 .. nseg-1, the all-ones id is left to the invalid (all-ones) key
+    int full_bits;      // key bits a full sort orders
+    // globally sorted bits: 8-bit passes until a bucket averages <= 512 entries; a segmented list sorts at least the
+    // segment id, so that the invalid windows form the last bucket on their own.  The passes order bits [low_bits, full_bits); 0 = full sort
+    int low_bits(uint32_t entries) const
+    {
+        if (!hash_path) return 0;
+        int G = 0;
+        while (G < full_bits && ((uint64_t)entries >> G) > 512) G += 8;
+        if (seg) G = std::max(G, (segbits + 7) / 8 * 8);
+        return full_bits - std::min(G, full_bits);
+    }
+};
+
+// Which join a pass runs, in the order the stages ask:
+//   host-supplied hits            : none (hits_scatter fills the hit table)
+//   use_summary                   : run_summary once, then join_pair_group per group of pairs
+//   tiny                          : tiny_join, a pass of a few thousand windows
+//   hash_path                     : the LDS hash join over a partial sort (join_hash) for the one-pass finders; the slices it hands
+//                                   back are sorted in full and joined by mum_join_slices
+//   otherwise                     : the full sort and the serial join (mum_join): a single pair of PairwiseMatchFinder (its run
+//                                   list needs sorted order), the two exports (sort only), segmented masked passes
+static int seed_plan(mauve_ctx *ctx, const SeedShape &sh, const GenomeTab &tab, const SeedRequest &rq, uint32_t n, bool masked, bool seg,
+                     int key_type_bits, SeedPlan *pl, std::vector<FinderPass> *passes)
+{
+    pl->seg = seg;
+    pl->hash_path = !rq.hits && rq.mode != MAUVE_MODE_PAIRWISE && !rq.out_keys && !rq.enumerate && rq.only_seq < 0 && !(masked && seg);
+    pl->segbits = 0;
+    if (seg) while (pl->segbits < 32 && (1ull << pl->segbits) <= (uint64_t)rq.nseg) pl->segbits++;
+    if (seg && 2 * sh.weight + pl->segbits > 64) { ctx->err = "recursive anchoring: segment id and mer do not fit 64 bits"; return MAUVE_ERR_LIMIT; }
+    pl->full_bits = seg ? 2 * sh.weight + pl->segbits : ((masked && rq.only_seq >= 0) ? key_type_bits : 2 * sh.weight);
+    pl->tiny = pl->hash_path && !no_tiny() && n <= (uint32_t)TJ_MAX && tab.nseq <= 16 && 2 * sh.weight + pl->segbits <= 32;
+    pl->compact = !rq.hits && !pl->tiny && rq.only_seq < 0 && masked && !seg;
+    pl->has_invalid = masked && !pl->compact;
+    // one pass, or one per genome pair for PairwiseMatchFinder
+    const int N = tab.nseq;
+    if (rq.mode == MAUVE_MODE_PAIRWISE) {
+        // (guide tree over several contexts, mauve_set_shard: this rank's share of the pairs, dealt round robin; the sums are exchanged)
+        int pi = 0;
+        for (int i = 0; i < N; i++) for (int j = i + 1; j < N; j++, pi++)
+            if (!ctx->pair_sums_only || !ctx->shard_on || pi % ctx->shard_world == ctx->shard_rank)
+                passes->push_back({(1u << i) | (1u << j), (1u << i) | (1u << j), MAUVE_MODE_MEM});
+    } else passes->push_back({0xffffffffu, (uint32_t)rq.mask, rq.mode});
+    pl->use_summary = rq.mode == MAUVE_MODE_PAIRWISE && !seg && !rq.hits && (passes->size() > 1 || (ctx->pair_sums_only && ctx->shard_on && !passes->empty()));
+    return MAUVE_OK;
+}
+
+// State of one pass.  KeyT / ValT: key and sort-value types; ValT is uint32_t (narrow) or uint64_t (wide: a pass of 2^31 windows or
+// more, or MAUVE_WIDE_INDEX=1).  A wide pass's hit table and host-side hit records hold windows local to their genome
+// (hit_word); out_vals are then local too.
+struct SeedState {
+    mauve_ctx *ctx; const GenomeSet &gs; const SeedShape &sh; const GenomeTab &tab; const SeedRequest &rq;
+    uint32_t P;                                    // windows of the set
+    const uint64_t *packed, *vmask, *cmask;
+    SeedPlan pl;
+    std::vector<FinderPass> passes;
+    uint32_t ns = 0;                               // entries of the sorted list (all windows, or the valid ones)
+    int L = 0;                                     // pl.low_bits(ns)
+    uint32_t *tmask = nullptr, *tpos = nullptr;    // the hit table: [P] component sets, [P][N] values
+    uint32_t cand_cap = 0;
+    uint32_t cand_total = 0;                       // one record slot per candidate of every pass; length 0 = not a leftmost hit
+    bool records_on_host = false;                  // ctx->sdh.hl / hs hold the candidates' records already (tiny_pass)
+    double trace_t0 = 0;
+};
+template <typename KeyT, typename ValT>
+struct SeedPass : SeedState {
+    KeyT *keys = nullptr; ValT *vals = nullptr;    // the list the sort takes and leaves
+    bool have_hist0 = false;                       // ctx->hist holds the tile histograms of the first sort pass (seed_extract_all)
+    SeedPass(const SeedState &s) : SeedState(s) {}
+};
+
+template <typename KeyT, typename ValT>
+static int ensure_sort_buffers(mauve_ctx *ctx, uint32_t n)
+{
     HIPCHK(ctx, ctx->keysA.ensure((size_t)n * sizeof(KeyT)));
     HIPCHK(ctx, ctx->keysB.ensure((size_t)n * sizeof(KeyT)));
     HIPCHK(ctx, ctx->valsA.ensure((size_t)n * sizeof(ValT)));
     HIPCHK(ctx, ctx->valsB.ensure((size_t)n * sizeof(ValT)));
-    HIPCHK(ctx, ctx->counters.ensure(64));
-    KeyT *keys = ctx->keysA.as<KeyT>(); ValT *vals = ctx->valsA.as<ValT>();
-    const uint64_t *packed = gs.buf->as<uint64_t>();
-    const uint64_t *vmask = gs.vmask ? gs.vmask->as<uint64_t>() : nullptr;
-    const uint64_t *cmask = gs.cmask ? gs.cmask->as<uint64_t>() : nullptr;
-    const bool masked = vmask || cmask;              // some windows are unusable: placed or ambiguous bases, contig joins
+    return MAUVE_OK;
+}
 
-    uint32_t sorted_n = 0;
-    bool have_hist0 = false;
-    bool compacted = false;
-    // Which join: the LDS hash join over a partial sort (join_hash) for the one-pass finders; the full sort and the
-    // serial join for PairwiseMatchFinder (its run list needs sorted order), for the sorted-mer-list export and for
-    // slices join_hash hands back.  MAUVE_OLD_JOIN forces the second (A/B switch).
-    static const bool force_old_join = getenv("MAUVE_OLD_JOIN") != nullptr;
-    const HostHits *hh = ctx->host_hits;                      // mauve_extend_hits: the hits come from the host, no sort, no join
-    const bool hash_path = !hh && mode != MAUVE_MODE_PAIRWISE && !out_keys && !ctx->enum_req && only_seq < 0 && !force_old_join && !(masked && SEG);
-    // segmented keys: segment id above the mer; ids 0 .. nseg-1, the all-ones id is left to the invalid (all-ones) key
-    int segbits = 0;
-    if (SEG) while (segbits < 32 && (1ull << segbits) <= (uint64_t)nseg) segbits++;
-    if (SEG && 2 * sh.weight + segbits > 64) { ctx->err = "recursive anchoring: segment id and mer do not fit 64 bits"; return MAUVE_ERR_LIMIT; }
-    const int full_bits = SEG ? 2 * sh.weight + segbits : ((masked && (SEG || only_seq >= 0)) ? (int)sizeof(KeyT) * 8 : 2 * sh.weight);
-    // globally sorted bits: 8-bit passes until a bucket averages <= 512 entries; a segmented list sorts at least the
-    // segment id, so that the invalid windows form the last bucket on their own
-    auto low_bits = [&](uint32_t entries) {
-        if (!hash_path) return 0;
-        int G = 0;
-        while (G < full_bits && ((uint64_t)entries >> G) > 512) G += 8;
-        if (SEG) G = std::max(G, (segbits + 7) / 8 * 8);
-        return full_bits - std::min(G, full_bits);
-    };
-    // a pass of a few thousand windows: no key arrays at all (tiny_join).  MAUVE_NO_TINY: A/B switch
-    static const bool no_tiny = getenv("MAUVE_NO_TINY") != nullptr;
-    const bool tiny = hash_path && only_seq < 0 && !no_tiny && n <= (uint32_t)TJ_MAX && tab.nseq <= 16 && 2 * sh.weight + (SEG ? segbits : 0) <= 32;
-    if (hh) sorted_n = 1;
-    else if (tiny) sorted_n = n;
-    else if (only_seq < 0 && masked && !SEG) {
+// The NARROW instantiations of seed_extract_all / seed_extract_compact: launch(std::true_type) when the seed fits them
+template <typename F>
+static void launch_narrow_or_not(const SeedShape &sh, F &&launch)
+{
+    if (sh.span <= 32 && sh.weight <= 15) launch(std::true_type{});
+    else launch(std::false_type{});
+}
+
+// keys and values of all n windows into keys / vals, the tile histograms of the first sort pass (digit at hshift) into ctx->hist
+template <typename KeyT, bool SEG, typename ValT>
+static int extract_all(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, uint32_t n, const uint32_t *seg, uint32_t nseg,
+                       int hshift, KeyT *keys, ValT *vals)
+{
+    const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
+    HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
+    const uint64_t *packed = gs.buf->as<uint64_t>();
+    const uint64_t *vmask = gs.vmask ? gs.vmask->as<uint64_t>() : nullptr;      // placed or ambiguous bases
+    const uint64_t *cmask = gs.cmask ? gs.cmask->as<uint64_t>() : nullptr;      // contig joins
+    KernelTimer t(ctx, MAUVE_K_EXTRACT, n);
+    launch_narrow_or_not(sh, [&](auto narrow) {
+        hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, decltype(narrow)::value, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
+                           vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask);
+    });
+    return MAUVE_OK;
+}
+
+// Stage 1: the (key, value) list the sort takes: ps.keys / vals / ns / have_hist0
+template <typename KeyT, bool SEG, typename ValT>
+static int extract(SeedPass<KeyT, ValT> &ps)
+{
+    mauve_ctx *ctx = ps.ctx; const SeedRequest &rq = ps.rq; const uint32_t n = ps.P;
+    if (int rc = ensure_sort_buffers<KeyT, ValT>(ctx, n)) return rc;
+    HIPCHK(ctx, ctx->counters.ensure(64));
+    KeyT *keys = ps.keys = ctx->keysA.as<KeyT>(); ValT *vals = ps.vals = ctx->valsA.as<ValT>();
+    if (rq.hits) ps.ns = 1;
+    else if (ps.pl.tiny) ps.ns = n;
+    else if (ps.pl.compact) {
         // masked pass: only the valid windows go into the sort (see valid_count / seed_extract_compact)
         const uint32_t nblk = (n + 4095) / 4096;
         HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));     // the tile counts live in the histogram buffer
         uint32_t *tile_cnt = ctx->hist.as<uint32_t>();
         {
             KernelTimer t(ctx, MAUVE_K_EXTRACT, n);
-            hipLaunchKernelGGL(valid_count, dim3(nblk), dim3(256), 0, ctx->stream, tab, sh.span, n, vmask, tile_cnt, cmask);
+            hipLaunchKernelGGL(valid_count, dim3(nblk), dim3(256), 0, ctx->stream, ps.tab, ps.sh.span, n, ps.vmask, tile_cnt, ps.cmask);
             hipLaunchKernelGGL(tile_scan, dim3(1), dim3(256), 0, ctx->stream, tile_cnt, nblk, ctx->counters.as<uint32_t>());
-            if (sh.span <= 32 && sh.weight <= 15)
-                hipLaunchKernelGGL((seed_extract_compact<KeyT, true, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys, vals, n,
-                                   vmask, tile_cnt, cmask);
-            else
-                hipLaunchKernelGGL((seed_extract_compact<KeyT, false, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys, vals, n,
-                                   vmask, tile_cnt, cmask);
+            launch_narrow_or_not(ps.sh, [&](auto narrow) {
+                hipLaunchKernelGGL((seed_extract_compact<KeyT, decltype(narrow)::value, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, ps.packed, ps.tab, ps.sh,
+                                   keys, vals, n, ps.vmask, tile_cnt, ps.cmask);
+            });
         }
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, ctx->pin_seed.ensure(64));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        sorted_n = ctx->pin_seed.as<uint32_t>()[0];
-        compacted = true;
-    } else if (only_seq < 0) {
-        const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
-        HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
-        KernelTimer t(ctx, MAUVE_K_EXTRACT, n);
-        const int hshift = low_bits(n);
-        if (sh.span <= 32 && sh.weight <= 15)
-            hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, true, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
-                               vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask);
-        else
-            hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, false, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
-                               vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask);
-        sorted_n = n; have_hist0 = true;
+        const uint32_t *cw;
+        if (int rc = seed_counters(ctx, 16, &cw)) return rc;       // (ctx->shadow stays for the pass's wait behind the run detection)
+        ps.ns = cw[0];
+    } else if (rq.only_seq < 0) {
+        if (int rc = extract_all<KeyT, SEG, ValT>(ctx, ps.gs, ps.sh, ps.tab, n, rq.seg, rq.nseg, ps.pl.low_bits(n), keys, vals)) return rc;
+        ps.ns = n; ps.have_hist0 = true;
     } else {
-        const int g = only_seq;
-        uint32_t nw = tab.nwin[g];
+        const int g = rq.only_seq;
+        uint32_t nw = ps.tab.nwin[g];
         if (nw) {
             uint32_t blocks = std::min<uint32_t>((nw + 255) / 256, 256 * 16);
             KernelTimer t(ctx, MAUVE_K_EXTRACT, nw);
-            hipLaunchKernelGGL((seed_extract<KeyT, SEG, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, g, keys,
-                               vals, 0u, seg, nseg);
-            sorted_n = nw;
+            hipLaunchKernelGGL((seed_extract<KeyT, SEG, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, ps.packed, ps.tab, ps.sh, g, keys,
+                               vals, 0u, rq.seg, rq.nseg);
+            ps.ns = nw;
         }
     }
     HIPCHK(ctx, hipGetLastError());
-    TRACE(ctx, "extract");
-    if (sorted_n == 0) { if (n_matches) *n_matches = 0; return MAUVE_OK; }
-    const int key_bits = full_bits;
-    const int has_invalid = masked && !compacted;
-    const uint32_t ns = sorted_n;                   // entries of the sorted list (all windows, or the valid ones)
-    const int L = low_bits(ns);                     // the passes order bits [L, key_bits); 0 = full sort
-    int rc = (hh || tiny) ? MAUVE_OK : sort_pairs<KeyT, ValT>(ctx, sorted_n, key_bits, &keys, &vals, ctx->keysB.as<KeyT>(), ctx->valsB.as<ValT>(), have_hist0, -1, L);
-    if (rc) return rc;
-    TRACE(ctx, "sort");
-
-    if (ctx->enum_req) {   // SeedMatchEnumerator: runs -> matches on the device, only the CSR result goes to the host
-        EnumRequest &q = *ctx->enum_req;
-        using namespace devscan;
-        const uint32_t nb = (sorted_n + TILE - 1) / TILE, blocks = (sorted_n + 255) / 256;
-        HIPCHK(ctx, ctx->run_sum.ensure((size_t)sorted_n * 4 + 64 + ((size_t)sorted_n + 2) * 8 * 3 + (size_t)nb * 16 + 256));
-        uint32_t *emit = ctx->run_sum.as<uint32_t>();
-        int64_t *soff = reinterpret_cast<int64_t *>(ctx->run_sum.as<char>() + (((size_t)sorted_n * 4 + 63) & ~(size_t)63));
-        int64_t *d_mult = soff + sorted_n + 2, *d_off = d_mult + sorted_n + 2, *bsum = d_off + sorted_n + 2, *tot = bsum + nb + 2;
-        uint32_t *bcnt = reinterpret_cast<uint32_t *>(tot + 4);
-        hipLaunchKernelGGL((enum_runs<KeyT, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.min_multi, q.max_multi, q.direct_only, emit);
-        hipLaunchKernelGGL((vscan_partial<int64_t, EmitVal>), dim3(nb), dim3(256), 0, ctx->stream, EmitVal{emit}, sorted_n, bsum);
-        hipLaunchKernelGGL((vscan_write<int64_t, EmitVal>), dim3(nb), dim3(256), 0, ctx->stream, EmitVal{emit}, sorted_n, bsum, soff, tot + 1);
-        const EnumRuns er{emit, soff, sorted_n, d_mult, d_off, tot};
-        hipLaunchKernelGGL((cmp_count<EnumRuns>), dim3(nb), dim3(256), 0, ctx->stream, er, bcnt);
-        hipLaunchKernelGGL((cmp_write<EnumRuns>), dim3(nb), dim3(256), 0, ctx->stream, er, bcnt);
-        HIPCHK(ctx, hipGetLastError());
-        int64_t ht[2] = {0, 0};
-        HIPCHK(ctx, hipMemcpyAsync(ht, tot, 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        q.n = ht[0]; q.ns = ht[1];
-        if (q.starts) {
-            HIPCHK(ctx, ctx->sorted_rec.ensure(((size_t)q.ns + 1) * 8));
-            hipLaunchKernelGGL((enum_write<KeyT, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.direct_only, emit, soff,
-                               tab.gpos_off[only_seq], ctx->sorted_rec.as<int64_t>());
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(q.mult, d_mult, (size_t)q.n * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(q.start_off, d_off, ((size_t)q.n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(q.starts, ctx->sorted_rec.p, (size_t)q.ns * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        return MAUVE_OK;
-    }
-    if (out_keys) {   // sorted-mer-list export: hand the sorted pairs to the host
-        std::vector<KeyT> hk(sorted_n);
-        out_vals->resize(sorted_n);
-        std::vector<ValT> hv(WIDEV ? sorted_n : 0);
-        HIPCHK(ctx, hipMemcpyAsync(hk.data(), keys, (size_t)sorted_n * sizeof(KeyT), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(WIDEV ? (void *)hv.data() : (void *)out_vals->data(), vals, (size_t)sorted_n * sizeof(ValT), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        out_keys->resize(sorted_n);
-        for (uint32_t i = 0; i < sorted_n; i++) (*out_keys)[i] = (uint64_t)hk[i];
-        if (WIDEV) {                                // wide: local to the genome already (index | strand << 31), as the narrow caller makes them
-            const uint32_t g0 = tab.gpos_off[only_seq];
-            for (uint32_t i = 0; i < sorted_n; i++) (*out_vals)[i] = ((uint32_t)hv[i] - g0) | ((uint32_t)((uint64_t)hv[i] >> 63) << 31);
-        }
-        return MAUVE_OK;
-    }
-
-    // ---- join + extension, once per finder pass (one pass, or one per genome pair for PairwiseMatchFinder) ----
-    const int N = tab.nseq;
-    const uint32_t P = n;
-    HIPCHK(ctx, ctx->posmask.ensure((size_t)P * 4));             // tmask
-    HIPCHK(ctx, ctx->hit_pos.ensure((size_t)P * 4 * N));         // tpos [P][N]
-    // Capacities of the compacted lists are handed to the kernels that fill them (a store past the end is skipped, the counter still counts)
-    // and checked against the counts that come back.  MAUVE_LIST_CAP: test knob, shrinks them so that the check can be seen to fire.
-    static const uint32_t list_cap_env = getenv("MAUVE_LIST_CAP") ? (uint32_t)strtoul(getenv("MAUVE_LIST_CAP"), nullptr, 10) : 0u;
-    uint32_t cand_cap = P / 2 + 1;                               // a hit needs >= 2 entries
-    HIPCHK(ctx, ctx->cand.ensure((size_t)cand_cap * 4));
-    if (list_cap_env) cand_cap = std::min(cand_cap, list_cap_env);
-    auto cand_overflow = [&](uint32_t nc) { if (nc <= cand_cap) return false; ctx->err = "seed pass: " + std::to_string(nc) + " candidates for a list of " + std::to_string(cand_cap); return true; };
-    uint32_t *tmask = ctx->posmask.as<uint32_t>(), *tpos = ctx->hit_pos.as<uint32_t>();
-    struct FinderPass { uint32_t consider, want; int rule; };
-    std::vector<FinderPass> passes;
-    if (mode == MAUVE_MODE_PAIRWISE) {
-        // (guide tree over several contexts, mauve_set_shard: this rank's share of the pairs, dealt round robin; the sums are exchanged)
-        int pi = 0;
-        for (int i = 0; i < N; i++) for (int j = i + 1; j < N; j++, pi++)
-            if (!ctx->pair_sums_only || !ctx->shard_on || pi % ctx->shard_world == ctx->shard_rank)
-                passes.push_back({(1u << i) | (1u << j), (1u << i) | (1u << j), MAUVE_MODE_MEM});
-    } else passes.push_back({0xffffffffu, (uint32_t)mask, mode});
-    ctx->n_matches = 0; ctx->match_len.clear(); ctx->match_start.clear(); ctx->matches_pending = false;
-    if (n_matches) *n_matches = 0;
-    // one record slot per candidate of every pass; length 0 = not a leftmost hit (host scratch kept across calls)
-    std::vector<int32_t> &hl = ctx->sdh.hl, &hs = ctx->sdh.hs; hl.clear(); hs.clear();
-    uint32_t cand_total = 0;
-    bool records_on_host = false;                 // hl / hs hold the candidates' records already (the one-round-trip form of a tiny pass)
-    // pairwise mode: the runs that can matter to any pair, listed once (see run_summary)
-    uint32_t nruns = 0;
-    const bool use_summary = mode == MAUVE_MODE_PAIRWISE && !SEG && (passes.size() > 1 || (ctx->pair_sums_only && ctx->shard_on && !passes.empty()));
-    uint32_t *rstart = nullptr, *rlen = nullptr, *runiq = nullptr;
-    if (use_summary) {
-        const size_t cap = (size_t)ns / 2 + 1;
-        const uint32_t run_cap = list_cap_env ? std::min<uint32_t>((uint32_t)cap, list_cap_env) : (uint32_t)cap;
-        HIPCHK(ctx, ctx->run_sum.ensure(3 * cap * 4));
-        rstart = ctx->run_sum.as<uint32_t>(); rlen = rstart + cap; runiq = rlen + cap;
-        HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-        { KernelTimer t(ctx, MAUVE_K_JOIN, ns);
-          hipLaunchKernelGGL((run_summary<KeyT, ValT>), dim3((ns + 1023) / 1024), dim3(256), 0, ctx->stream, keys, vals, ns, tab,
-                             has_invalid, rstart, rlen, runiq, ctx->counters.as<uint32_t>() + 2, run_cap); }
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, ctx->pin_seed.ensure(64));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        nruns = ctx->pin_seed.as<uint32_t>()[2];
-        if (nruns > run_cap) { ctx->err = "seed pass: " + std::to_string(nruns) + " runs for a list of " + std::to_string(run_cap); return MAUVE_ERR_LIMIT; }
-        TRACE(ctx, "run summary");
-    }
-    // ---- the passes of the pairwise finder in groups: pairs with different lower genomes write disjoint slices of the hit table, so up to
-    // N - 1 of them share one join launch (the run list is read once per group instead of once per pair), one run-detection launch
-    // (blockIdx.y = pair), one candidate list, one round trip and one extension launch: 28 passes of an 8-genome guide tree are 7 groups.
-    // MAUVE_PAIR_SERIAL: A/B switch (one pass per pair, the loop below).
-    static const bool pair_serial = getenv("MAUVE_PAIR_SERIAL") != nullptr;
-    if (use_summary && nruns && !pair_serial && !hh && !SEG) {
-        // one candidate list per group: a pair has at most one hit per window of its lower genome, the lower genomes of a group are
-        // different, so a group has at most P candidates (a single pass: P / 2, "a hit needs two entries" -- not enough here)
-        HIPCHK(ctx, ctx->cand.ensure(((size_t)P + 1) * 4));
-        cand_cap = list_cap_env ? std::min<uint32_t>(P + 1, list_cap_env) : P + 1;
-        std::vector<char> used(passes.size(), 0);
-        for (size_t left = passes.size(); left;) {
-            PairGroup grp; memset(&grp, 0, sizeof grp);
-            uint32_t amask = 0, maxslice = 0, slices = 0;
-            for (size_t q = 0; q < passes.size(); q++) {
-                if (used[q]) continue;
-                const int ga = __builtin_ctz(passes[q].consider), gb = 31 - __builtin_clz(passes[q].consider);
-                if (amask >> ga & 1u) continue;
-                used[q] = 1; left--;
-                const uint32_t lo = tab.gpos_off[ga], hi = std::min<uint32_t>(tab.gpos_off[ga + 1], P);
-                if (hi <= lo) continue;                            // (a genome shorter than the seed has no window)
-                grp.ga[grp.n] = ga; grp.gb[grp.n] = gb; grp.lo[grp.n] = lo; grp.hi[grp.n] = hi; grp.n++;
-                amask |= 1u << ga; maxslice = std::max(maxslice, hi - lo); slices += hi - lo;
-            }
-            if (!grp.n) continue;
-            for (int y = 0; y < grp.n; y++) HIPCHK(ctx, hipMemsetAsync(ctx->posmask.as<uint32_t>() + grp.lo[y], 0, (size_t)(grp.hi[y] - grp.lo[y]) * 4, ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-            { KernelTimer t(ctx, MAUVE_K_JOIN, nruns);
-              hipLaunchKernelGGL(join_pair_group<ValT>, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, vals, tab, rstart, rlen, runiq, nruns, grp, tmask, tpos); }
-            HIPCHK(ctx, hipGetLastError());
-            TRACE(ctx, "join");
-            { KernelTimer t(ctx, MAUVE_K_RUNS, slices);
-              hipLaunchKernelGGL(mum_runs_group, dim3((maxslice + RUNS_TILE - 1) / RUNS_TILE, (uint32_t)grp.n), dim3(256), 0, ctx->stream, tab, sh.span, tmask, tpos, grp,
-                                 extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), cand_cap); }
-            HIPCHK(ctx, hipGetLastError());
-            if (ctx->shadow) { std::function<void()> fsh; fsh.swap(ctx->shadow); fsh(); }
-            HIPCHK(ctx, ctx->pin_seed.ensure(64));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            const uint32_t nc = ctx->pin_seed.as<uint32_t>()[1];
-            if (cand_overflow(nc)) return MAUVE_ERR_LIMIT;
-            TRACE(ctx, "runs");
-            if (g_trace) fprintf(stderr, "[trace]   %u candidates of %u windows (%d pairs at once)\n", nc, slices, grp.n);
-            if (nc == 0) continue;
-            HIPCHK(ctx, ctx->mlen.ensure_keep((size_t)(cand_total + nc) * 4 + 4, (size_t)cand_total * 4, ctx->stream));
-            HIPCHK(ctx, ctx->mstart.ensure_keep((size_t)(cand_total + nc) * 4 * N + 4, (size_t)cand_total * 4 * N, ctx->stream));
-            {
-                const uint32_t blocks = std::min<uint32_t>((nc + 3) / 4, 256 * 8);
-                KernelTimer t(ctx, MAUVE_K_EXTEND, nc);
-                hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P, ctx->cand.as<uint32_t>(), nc, extend,
-                                   ctx->mlen.as<int32_t>() + cand_total, ctx->mstart.as<int32_t>() + (size_t)cand_total * N, seg, nseg, vmask, cmask);
-                HIPCHK(ctx, hipGetLastError());
-            }
-            cand_total += nc;
-            TRACE(ctx, "extend");
-        }
-        passes.clear();                                        // done: nothing left for the loop below
-    }
-    for (const FinderPass &fp : passes) {
-        // the hit table is indexed by the anchor's window = a window of the lowest genome of the pass: a pass over one genome pair
-        // (the guide tree runs N (N - 1) / 2 of them) clears and scans that genome's slice only
-        uint32_t s_lo = 0, s_hi = P;
-        if (use_summary && fp.consider) { const int ga = __builtin_ctz(fp.consider); s_lo = tab.gpos_off[ga]; s_hi = std::min<uint32_t>(tab.gpos_off[ga + 1], P); }
-        if (s_hi <= s_lo) continue;                              // (a genome shorter than the seed has no window: nothing can be anchored in it)
-        const bool tiny_clears = tiny && !hh && !use_summary;           // tiny_join clears for itself
-        if (!tiny_clears) {
-            HIPCHK(ctx, hipMemsetAsync(ctx->posmask.as<uint32_t>() + s_lo, 0, (size_t)(s_hi - s_lo) * 4, ctx->stream));
-            HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-        }
-        if (hh) {
-            HIPCHK(ctx, ctx->run_sum.ensure((size_t)hh->n * (N + 1) * 4 + 64));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->run_sum.p, hh->rec, (size_t)hh->n * (N + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-            if (hh->n) hipLaunchKernelGGL(hits_scatter<WIDEV>, dim3((hh->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->run_sum.as<uint32_t>(), hh->n, N, P, tmask, tpos, tab);
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the host records must outlive the copy
-        } else if (use_summary) {
-            KernelTimer t(ctx, MAUVE_K_JOIN, nruns);
-            if (nruns)
-                hipLaunchKernelGGL(join_pair<ValT>, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, vals, tab, rstart, rlen, runiq, nruns,
-                                   __builtin_ctz(fp.consider), 31 - __builtin_clz(fp.consider), tmask, tpos);
-        } else if (tiny) {
-            static const bool tj_attr = []() { return hipFuncSetAttribute(reinterpret_cast<const void *>(tiny_join<WIDEV>), hipFuncAttributeMaxDynamicSharedMemorySize, TJ_SLOTS * 8) == hipSuccess; }();
-            if (!tj_attr) { ctx->err = "tiny_join: cannot reserve its LDS"; return MAUVE_ERR_HIP; }
-            KernelTimer t(ctx, MAUVE_K_JOIN, P);
-            hipLaunchKernelGGL(tiny_join<WIDEV>, dim3(1), dim3(1024), TJ_SLOTS * 8, ctx->stream, packed, tab, sh, P, vmask, cmask, fp.rule, fp.want, tmask, tpos,
-                               ctx->counters.as<uint32_t>() + 9, SEG ? seg : (const uint32_t *)nullptr, nseg, ctx->counters.as<uint32_t>(), s_lo, s_hi);
-        } else if (hash_path) {
-            const uint32_t nchunk = (ns + HJ_T - 1) / HJ_T;
-            HIPCHK(ctx, ctx->join_ovf.ensure((2 + 2 * (size_t)HJ_OVF_CAP) * 4));        // the ranges; their count sits in the counter block (words 8, 9)
-            KernelTimer t(ctx, MAUVE_K_JOIN, ns);
-            HIPCHK(ctx, ctx->join_bound.ensure(((size_t)nchunk + 2) * 4));
-            hipLaunchKernelGGL((join_bounds<KeyT>), dim3((nchunk + 1 + 3) / 4), dim3(256), 0, ctx->stream, keys, ns, L, nchunk,
-                               ctx->join_bound.as<uint32_t>());
-#define JH_LAUNCH(W) hipLaunchKernelGGL((join_hash<KeyT, W, ValT>), dim3(nchunk), dim3(256), 0, ctx->stream, keys, vals, ns, \
-                                           ctx->join_bound.as<uint32_t>(), tab, fp.rule, fp.want, tmask, tpos, ctx->counters.as<uint32_t>() + 8, ctx->join_ovf.as<uint32_t>(), P)
-            if (N > 16) JH_LAUNCH(true);
-            else JH_LAUNCH(false);
-#undef JH_LAUNCH
-        } else
-        { KernelTimer t(ctx, MAUVE_K_JOIN, ns);
-          hipLaunchKernelGGL((mum_join<KeyT, SEG, ValT>), dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, keys, vals, ns, tab, fp.rule,
-                             fp.want, fp.consider, tmask, tpos, P, has_invalid); }
-        HIPCHK(ctx, hipGetLastError());
-        TRACE(ctx, "join");
-        // extension phase A: run starts from the table
-        { KernelTimer t(ctx, MAUVE_K_RUNS, s_hi - s_lo);
-          hipLaunchKernelGGL((mum_runs<SEG>), dim3((s_hi - s_lo + RUNS_TILE - 1) / RUNS_TILE), dim3(256), 0, ctx->stream, tab,
-                             sh.span, tmask, tpos, s_hi, extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), seg,
-                             nseg, cand_cap, s_lo); }
-        HIPCHK(ctx, hipGetLastError());
-        if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // the kernels above are still running
-        if (tiny && !hh && passes.size() == 1 && cand_total == 0 && cand_cap <= 8192) {
-            // A tiny pass (a round of the LCB extension, a small guide-tree node, a small recursion batch) is a handful of 5-10 us kernels: the round
-            // trip that fetched the candidate count before the extension kernel could be launched cost as much as the pass.  Its candidate list has
-            // at most a few thousand entries, so the extension is launched for the CAPACITY of the list with the count left on the device, and the
-            // counters come back together with the records: one synchronisation per pass instead of two.
-            // The records and the counters go straight into page-locked host memory (the device writes it in place: a handful of candidates), so the
-            // round trip is one synchronisation and no copy kernel.  (Not when the canonical order is to be made on the device -- a test setting for
-            // lists this small: then the records stay in device memory and are copied as well.)
-            const size_t lbytes = ((size_t)cand_cap * 4 + 63) & ~(size_t)63, sbytes = (size_t)cand_cap * 4 * N;
-            HIPCHK(ctx, ctx->pin_seed.ensure(64 + lbytes + sbytes));
-            char *pin = ctx->pin_seed.as<char>();
-            const bool host_out = cand_cap < canon_device_min();
-            if (!host_out) { HIPCHK(ctx, ctx->mlen.ensure((size_t)cand_cap * 4 + 4)); HIPCHK(ctx, ctx->mstart.ensure((size_t)cand_cap * 4 * N + 4)); }
-            int32_t *o_len = host_out ? reinterpret_cast<int32_t *>(pin + 64) : ctx->mlen.as<int32_t>();
-            int32_t *o_st = host_out ? reinterpret_cast<int32_t *>(pin + 64 + lbytes) : ctx->mstart.as<int32_t>();
-            { KernelTimer t(ctx, MAUVE_K_EXTEND, cand_cap);
-              hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(std::min<uint32_t>((cand_cap + 3) / 4, 512)), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P,
-                                 ctx->cand.as<uint32_t>(), cand_cap, extend, o_len, o_st, seg, nseg, vmask, cmask,
-                                 ctx->counters.as<uint32_t>() + 1, reinterpret_cast<uint32_t *>(pin)); }
-            HIPCHK(ctx, hipGetLastError());
-            if (!host_out) {
-                HIPCHK(ctx, hipMemcpyAsync(pin + 64, ctx->mlen.p, (size_t)cand_cap * 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(pin + 64 + lbytes, ctx->mstart.p, sbytes, hipMemcpyDeviceToHost, ctx->stream));
-            }
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            const uint32_t nc = reinterpret_cast<const uint32_t *>(pin)[1];
-            if (reinterpret_cast<const uint32_t *>(pin)[9]) { ctx->err = "tiny_join: anchor out of range (internal error)"; return MAUVE_ERR_HIP; }
-            if (cand_overflow(nc)) return MAUVE_ERR_LIMIT;
-            TRACE(ctx, "runs + extend (one round trip)");
-            if (g_trace) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
-            hl.assign(reinterpret_cast<const int32_t *>(pin + 64), reinterpret_cast<const int32_t *>(pin + 64) + nc);
-            hs.assign(reinterpret_cast<const int32_t *>(pin + 64 + lbytes), reinterpret_cast<const int32_t *>(pin + 64 + lbytes) + (size_t)nc * N);
-            cand_total = nc; records_on_host = true;
-            continue;
-        }
-        HIPCHK(ctx, ctx->pin_seed.ensure(64));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, 48, hipMemcpyDeviceToHost, ctx->stream));     // run counters + join_hash's overflow count
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        uint32_t nc = ctx->pin_seed.as<uint32_t>()[1];
-        const uint32_t novf = hash_path && !tiny ? ctx->pin_seed.as<uint32_t>()[8] : 0u;
-        if (hash_path && ctx->pin_seed.as<uint32_t>()[9]) { ctx->err = "join_hash: anchor out of range (internal error)"; return MAUVE_ERR_HIP; }
-        if (novf) {
-            // ranges join_hash declined (a bucket beyond its LDS table): full sort + serial join of each slice, or of
-            // the whole list when there are more of them than the list holds; then the run detection again
-            std::vector<uint32_t> rng;
-            if (novf > (uint32_t)HJ_OVF_CAP) rng = {0u, ns};
-            else {
-                rng.resize(2 * (size_t)novf);
-                HIPCHK(ctx, hipMemcpy(rng.data(), ctx->join_ovf.as<uint32_t>() + 2, rng.size() * 4, hipMemcpyDeviceToHost));
-            }
-            KeyT *alt_k = keys == ctx->keysA.as<KeyT>() ? ctx->keysB.as<KeyT>() : ctx->keysA.as<KeyT>();
-            ValT *alt_v = vals == ctx->valsA.as<ValT>() ? ctx->valsB.as<ValT>() : ctx->valsA.as<ValT>();
-            // each slice sorted in full where it lies (the sorted pairs end up in this buffer or the other one), then ONE join over all slices
-            const size_t nsl = rng.size() / 2;
-            std::vector<uint32_t> sl_lo(nsl), sl_pre(nsl + 1, 0);
-            const KeyT *jk = keys; const ValT *jv = vals;
-            uint64_t tot_sl = 0;
-            for (size_t q = 0; q < nsl; q++) {
-                const uint32_t s0 = rng[2 * q], cnt = rng[2 * q + 1] - rng[2 * q];
-                KeyT *kp = keys + s0; ValT *vp = vals + s0;
-                int rc3 = sort_pairs<KeyT, ValT>(ctx, cnt, key_bits, &kp, &vp, alt_k + s0, alt_v + s0, false, MAUVE_K_JOIN);
-                if (rc3) return rc3;
-                if (kp != keys + s0) {           // an odd number of passes: the slice now lies in the other buffer -- copy it back
-                    HIPCHK(ctx, hipMemcpyAsync(keys + s0, kp, (size_t)cnt * sizeof(KeyT), hipMemcpyDeviceToDevice, ctx->stream));
-                    HIPCHK(ctx, hipMemcpyAsync(vals + s0, vp, (size_t)cnt * sizeof(ValT), hipMemcpyDeviceToDevice, ctx->stream));
-                }
-                sl_lo[q] = s0; tot_sl += cnt; sl_pre[q + 1] = (uint32_t)tot_sl;
-            }
-            if (tot_sl) {
-                HIPCHK(ctx, ctx->join_bound.ensure((2 * nsl + 1) * 4));
-                HIPCHK(ctx, ctx->pin_seed.ensure(64 + (2 * nsl + 1) * 4));
-                uint32_t *hp = reinterpret_cast<uint32_t *>(ctx->pin_seed.as<char>() + 64);
-                memcpy(hp, sl_lo.data(), nsl * 4); memcpy(hp + nsl, sl_pre.data(), (nsl + 1) * 4);
-                HIPCHK(ctx, hipMemcpyAsync(ctx->join_bound.p, hp, (2 * nsl + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-                KernelTimer t(ctx, MAUVE_K_JOIN, (uint32_t)tot_sl);
-                hipLaunchKernelGGL((mum_join_slices<KeyT, SEG, ValT>), dim3((uint32_t)((tot_sl + 255) / 256)), dim3(256), 0, ctx->stream, jk, jv,
-                                   ctx->join_bound.as<uint32_t>(), ctx->join_bound.as<uint32_t>() + nsl, (uint32_t)nsl, tab, fp.rule, fp.want,
-                                   fp.consider, tmask, tpos, has_invalid);
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));     // the page-locked slice table is reused by the counter copy below
-            }
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-            { KernelTimer t(ctx, MAUVE_K_RUNS, P);
-              hipLaunchKernelGGL((mum_runs<SEG>), dim3((P + RUNS_TILE - 1) / RUNS_TILE), dim3(256), 0, ctx->stream, tab,
-                                 sh.span, tmask, tpos, P, extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), seg,
-                                 nseg, cand_cap); }
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            nc = ctx->pin_seed.as<uint32_t>()[1];
-            if (g_trace) fprintf(stderr, "[trace]   join_hash handed back %u range(s)\n", novf);
-        }
-        if (cand_overflow(nc)) return MAUVE_ERR_LIMIT;
-        TRACE(ctx, "runs");
-        if (g_trace) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
-        if (nc == 0) continue;
-        // extension phase B: the records of all passes accumulate on the device
-        HIPCHK(ctx, ctx->mlen.ensure_keep((size_t)(cand_total + nc) * 4 + 4, (size_t)cand_total * 4, ctx->stream));
-        HIPCHK(ctx, ctx->mstart.ensure_keep((size_t)(cand_total + nc) * 4 * N + 4, (size_t)cand_total * 4 * N, ctx->stream));
-        {
-            // six waves per SIMD fit (77 registers); two rounds of workgroups even out the candidates' different lengths (measured: 5 .. 8 per compute unit
-            // within 5 % of each other, 12 .. 14 another 10 % faster)
-            static const int per_cu = getenv("MAUVE_EXT_BLOCKS_PER_CU") ? atoi(getenv("MAUVE_EXT_BLOCKS_PER_CU")) : 12;
-            uint32_t blocks = std::min<uint32_t>((nc + 3) / 4, (uint32_t)(ctx->cus * per_cu));
-            KernelTimer t(ctx, MAUVE_K_EXTEND, nc);
-            hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(blocks), dim3(256), 0, ctx->stream, packed, tab, sh, tmask, tpos, P,
-                               ctx->cand.as<uint32_t>(), nc, extend, ctx->mlen.as<int32_t>() + cand_total,
-                               ctx->mstart.as<int32_t>() + (size_t)cand_total * N, seg, nseg, vmask, cmask);
-            HIPCHK(ctx, hipGetLastError());
-#ifdef MAUVE_EXT_STATS
-            if (g_trace) {
-                unsigned long long h[8]; hipStreamSynchronize(ctx->stream);
-                hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ext_stats), sizeof h); unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_ext_stats), z, sizeof z);
-                fprintf(stderr, "[trace]   extend stats: %llu rounds, %llu waves, wave time mean %.1f us max %.1f us (setup %.1f, left walk %.1f, right walk %.1f), most rounds of a wave %llu\n", h[0], h[4],
-                        h[4] ? h[2] / (double)h[4] / 100.0 : 0.0, h[3] / 100.0, h[4] ? h[1] / (double)h[4] / 100.0 : 0.0, h[4] ? h[6] / (double)h[4] / 100.0 : 0.0,
-                        h[4] ? h[7] / (double)h[4] / 100.0 : 0.0, h[5]);
-            }
-#endif
-        }
-        cand_total += nc;
-        TRACE(ctx, "extend");
-    }
-    const uint32_t ncand = cand_total;
-    if (ctx->pair_sums_only) {                   // the guide tree's view of the pairwise matches
-        ctx->pair_sums.assign((size_t)N * N, 0);
-        if (ncand) {
-            HIPCHK(ctx, ctx->run_sum.ensure((size_t)N * N * 8 + 64));
-            unsigned long long *d = ctx->run_sum.as<unsigned long long>();
-            HIPCHK(ctx, hipMemsetAsync(d, 0, (size_t)N * N * 8, ctx->stream));
-            hipLaunchKernelGGL(pair_length_sums, dim3(std::min<uint32_t>((ncand + 255) / 256, 1024)), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(),
-                               ctx->mstart.as<int32_t>(), ncand, N, d);
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, ctx->pin_seed.ensure(64 + (size_t)N * N * 8));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.as<char>() + 64, d, (size_t)N * N * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            memcpy(ctx->pair_sums.data(), ctx->pin_seed.as<char>() + 64, (size_t)N * N * 8);
-        }
-        TRACE(ctx, "pair length sums");
-        if (ctx->bp_min_len >= 0) {              // broken adjacencies per pair, from the same records
-            ctx->pair_bp.assign((size_t)N * N, 0);
-            if (ncand >= 2) {
-                HIPCHK(ctx, ctx->canon_k1.ensure((size_t)ncand * 8 + 64)); HIPCHK(ctx, ctx->canon_k2.ensure((size_t)ncand * 8 + 64));
-                HIPCHK(ctx, ctx->canon_v1.ensure((size_t)ncand * 4 + 64)); HIPCHK(ctx, ctx->canon_v2.ensure((size_t)ncand * 4 + 64));
-                HIPCHK(ctx, ctx->bp_work.ensure((size_t)ncand * 8 * 2 + (size_t)ncand * 4 * 3 + (size_t)N * N * 8 + 256));
-                uint64_t *ck = ctx->canon_k1.as<uint64_t>(), *ck2 = ctx->canon_k2.as<uint64_t>();
-                uint32_t *cv = ctx->canon_v1.as<uint32_t>(), *cv2 = ctx->canon_v2.as<uint32_t>();
-                uint64_t *bk = ctx->bp_work.as<uint64_t>(), *bk2 = bk + ncand;
-                uint32_t *bv = reinterpret_cast<uint32_t *>(bk2 + ncand), *bv2 = bv + ncand, *rank = bv2 + ncand;
-                unsigned long long *dbp = reinterpret_cast<unsigned long long *>(ctx->bp_work.as<char>() + (((size_t)ncand * 28 + 63) & ~(size_t)63));
-                HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-                HIPCHK(ctx, hipMemsetAsync(dbp, 0, (size_t)N * N * 8, ctx->stream));
-                int64_t maxlen = 1; for (int g = 0; g < N; g++) maxlen = std::max<int64_t>(maxlen, gs.lens[(size_t)g]);
-                int pos_bits = 1; while (pos_bits < 32 && (1LL << pos_bits) <= maxlen) pos_bits++;
-                int pid_bits = 1; while ((1 << pid_bits) <= N * N) pid_bits++;
-                const int32_t min_len = (int32_t)std::min<int64_t>(ctx->bp_min_len, INT32_MAX);
-                const int kb = pos_bits + 1 + pid_bits;
-                // 1. by the higher genome (position, strand): only to break the ties of the next order
-                hipLaunchKernelGGL(bp_keys, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(), ctx->mstart.as<int32_t>(), (const uint32_t *)nullptr, ncand, N,
-                                   pos_bits, min_len, 1, 1, ck, cv, ctx->counters.as<uint32_t>() + 3);
-                HIPCHK(ctx, hipGetLastError());
-                int rc2 = sort_pairs<uint64_t>(ctx, ncand, kb, &ck, &cv, ck2, cv2, false, MAUVE_K_CANON);
-                if (rc2) return rc2;
-                HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.as<char>(), ctx->counters.as<uint32_t>() + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                const uint32_t nv = ctx->pin_seed.as<uint32_t>()[0];
-                if (nv >= 2) {
-                    // 2. along the lower genome: record indices in that order (stable: ties stay in the order of 1.)
-                    hipLaunchKernelGGL(bp_keys, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(), ctx->mstart.as<int32_t>(), cv, nv, N, pos_bits, min_len, 0, 1,
-                                       bk, bv, (uint32_t *)nullptr);
-                    HIPCHK(ctx, hipGetLastError());
-                    uint64_t *ak = bk; uint32_t *av = bv;
-                    rc2 = sort_pairs<uint64_t>(ctx, nv, kb, &ak, &av, bk2, bv2, false, MAUVE_K_CANON);
-                    if (rc2) return rc2;
-                    // 3. ranks along the higher genome (ties in the order of 2.); the canonical-sort buffers are free again
-                    uint64_t *sk = ctx->canon_k1.as<uint64_t>(); uint32_t *sv = ctx->canon_v1.as<uint32_t>();
-                    hipLaunchKernelGGL(bp_keys, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(), ctx->mstart.as<int32_t>(), av, nv, N, pos_bits, min_len, 1, 0,
-                                       sk, sv, (uint32_t *)nullptr);
-                    HIPCHK(ctx, hipGetLastError());
-                    rc2 = sort_pairs<uint64_t>(ctx, nv, kb, &sk, &sv, ctx->canon_k2.as<uint64_t>(), ctx->canon_v2.as<uint32_t>(), false, MAUVE_K_CANON);
-                    if (rc2) return rc2;
-                    ck = ak; cv = av;                        // the order along the lower genome, for the count
-                    hipLaunchKernelGGL(bp_rank, dim3((nv + 255) / 256), dim3(256), 0, ctx->stream, sv, nv, rank);
-                    hipLaunchKernelGGL(bp_count, dim3(std::min<uint32_t>((nv + 255) / 256, 1024)), dim3(256), 0, ctx->stream, ck, cv, rank, ctx->mstart.as<int32_t>(), nv, N, pos_bits, dbp);
-                    HIPCHK(ctx, hipGetLastError());
-                    HIPCHK(ctx, ctx->pin_seed.ensure(64 + (size_t)N * N * 8));
-                    HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.as<char>() + 64, dbp, (size_t)N * N * 8, hipMemcpyDeviceToHost, ctx->stream));
-                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                    memcpy(ctx->pair_bp.data(), ctx->pin_seed.as<char>() + 64, (size_t)N * N * 8);
-                }
-            }
-            TRACE(ctx, "pair breakpoints");
-        }
-        return MAUVE_OK;
-    }
-    if (ncand == 0) return MAUVE_OK;
-    // ---- canonical order (first component, |start|, mask, starts, length) ----
-    const uint32_t dev_sort_min = canon_device_min();
-    if (ncand >= dev_sort_min) {
-        // large sets: sort on the device, gather, copy out in order.  (Own buffers: over several finder passes the
-        // candidates can outnumber the windows, so the sorted-mer buffers are not guaranteed to be big enough.)
-        HIPCHK(ctx, ctx->canon_k1.ensure((size_t)ncand * 8 + 64)); HIPCHK(ctx, ctx->canon_k2.ensure((size_t)ncand * 8 + 64));
-        HIPCHK(ctx, ctx->canon_v1.ensure((size_t)ncand * 4 + 64)); HIPCHK(ctx, ctx->canon_v2.ensure((size_t)ncand * 4 + 64));
-        uint64_t *ck = ctx->canon_k1.as<uint64_t>(), *ck2 = ctx->canon_k2.as<uint64_t>();
-        uint32_t *cv = ctx->canon_v1.as<uint32_t>(), *cv2 = ctx->canon_v2.as<uint32_t>();
-        HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-        int64_t maxlen = 1; for (int g = 0; g < N; g++) maxlen = std::max<int64_t>(maxlen, gs.lens[(size_t)g]);
-        int pos_bits = 1; while (pos_bits < 32 && (1LL << pos_bits) <= maxlen) pos_bits++;
-        // the bits above the position hold the first component (0 .. N-1; N = dropped).  An N-way search (mask = every genome) only
-        // has matches that start in genome 0: one bit tells them from the dropped ones, which at bacterial sizes saves a sort pass
-        const uint32_t full_mask = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
-        const bool nway_only = mask != 0 && (uint32_t)mask == full_mask && mode != MAUVE_MODE_PAIRWISE;
-        int fbits = 1; if (!nway_only) while ((1 << fbits) <= N) fbits++;
-        { KernelTimer t(ctx, MAUVE_K_CANON, ncand);
-          hipLaunchKernelGGL(canon_keys, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(),
-                             ctx->mstart.as<int32_t>(), ncand, N, pos_bits, nway_only ? 1 : N, ck, cv, ctx->counters.as<uint32_t>() + 3); }
-        HIPCHK(ctx, hipGetLastError());
-        int rc2 = sort_pairs<uint64_t>(ctx, ncand, pos_bits + fbits, &ck, &cv, ck2, cv2, false, MAUVE_K_CANON);
-        if (rc2) return rc2;
-        HIPCHK(ctx, ctx->sorted_rec.ensure((size_t)ncand * (1 + N) * 8 + 64));
-        hipLaunchKernelGGL(canon_gather, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(),
-                           ctx->mstart.as<int32_t>(), ck, cv, ctx->counters.as<uint32_t>() + 3, N, ctx->sorted_rec.as<int64_t>(),
-                           ctx->counters.as<uint32_t>() + 4);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, ctx->pin_seed.ensure(64));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->pin_seed.p, ctx->counters.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t nm = ctx->pin_seed.as<uint32_t>()[3];
-        const bool dev_ties = ctx->pin_seed.as<uint32_t>()[4] != 0;
-        if (ctx->lazy_matches_ok && nm && !dev_ties) {
-            // the caller keeps working on the device copy (sorted_rec); the host copy is made when somebody asks for it
-            ctx->match_len.clear(); ctx->match_start.clear();
-            ctx->matches_pending = true; ctx->match_nseq = N;
-            ctx->n_matches = nm; ctx->dev_rec_n = (int64_t)nm;
-            if (n_matches) *n_matches = nm;
-            TRACE(ctx, "canonical sort (device, list stays)");
-            return MAUVE_OK;
-        }
-        ctx->match_len.resize(nm); ctx->match_start.resize((size_t)nm * N);
-        bool canon_ties = false;
-        if (nm) {
-            int64_t *ol = ctx->sorted_rec.as<int64_t>();
-            // through page-locked staging: a pageable destination of tens of MB copies at a fraction of the link rate
-            const size_t rbytes = (size_t)nm * (1 + N) * 8;
-            HIPCHK(ctx, ctx->pin_seed.ensure(64 + rbytes));
-            char *pin = ctx->pin_seed.as<char>() + 64;
-            HIPCHK(ctx, hipMemcpyAsync(pin, ol, rbytes, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            memcpy(ctx->match_len.data(), pin, (size_t)nm * 8);
-            memcpy(ctx->match_start.data(), pin + (size_t)nm * 8, (size_t)nm * N * 8);
-            // equal (first component, start) groups: order by the rest of the comparator (rare)
-            auto k1of = [&](uint32_t r) {
-                const int64_t *st = &ctx->match_start[(size_t)r * N];
-                int f = 0; while (f < N && st[f] == 0) f++;
-                return ((uint64_t)f << 32) | (uint64_t)(f < N ? std::llabs(st[f]) : 0);
-            };
-            auto rec_less = [&](const std::vector<int64_t> &x, const std::vector<int64_t> &y) {     // [len, starts...]
-                uint32_t ma = 0, mb = 0;
-                for (int g = 0; g < N; g++) { if (x[1 + g]) ma |= 1u << g; if (y[1 + g]) mb |= 1u << g; }
-                if (ma != mb) return ma < mb;
-                for (int g = 0; g < N; g++) if (x[1 + g] != y[1 + g]) return x[1 + g] < y[1 + g];
-                return x[0] < y[0];
-            };
-            uint64_t prev = k1of(0);
-            for (uint32_t i = 0; i < nm;) {
-                uint32_t j = i + 1; uint64_t kj = 0;
-                while (j < nm && (kj = k1of(j)) == prev) j++;
-                if (j - i > 1) {
-                    canon_ties = true;
-                    std::vector<std::vector<int64_t>> grp;
-                    for (uint32_t r = i; r < j; r++) {
-                        std::vector<int64_t> rec(1 + N); rec[0] = ctx->match_len[r];
-                        std::copy(&ctx->match_start[(size_t)r * N], &ctx->match_start[(size_t)r * N] + N, rec.begin() + 1);
-                        grp.push_back(rec);
-                    }
-                    std::sort(grp.begin(), grp.end(), rec_less);
-                    for (uint32_t r = i; r < j; r++) {
-                        ctx->match_len[r] = grp[r - i][0];
-                        std::copy(grp[r - i].begin() + 1, grp[r - i].end(), &ctx->match_start[(size_t)r * N]);
-                    }
-                }
-                prev = kj; i = j;
-            }
-        }
-        ctx->n_matches = nm;
-        if (canon_ties && nm) {
-            // the host finished the order inside the tie groups: the device copy follows (the chaining stages read it)
-            char *pin = ctx->pin_seed.as<char>() + 64;
-            memcpy(pin, ctx->match_len.data(), (size_t)nm * 8);
-            memcpy(pin + (size_t)nm * 8, ctx->match_start.data(), (size_t)nm * N * 8);
-            HIPCHK(ctx, hipMemcpyAsync(ctx->sorted_rec.p, pin, (size_t)nm * (1 + N) * 8, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        ctx->dev_rec_n = (int64_t)nm;                          // sorted_rec holds the list in canonical order
-        if (n_matches) *n_matches = nm;
-        TRACE(ctx, "canonical sort (device)");
-        return MAUVE_OK;
-    }
-    // small sets: records to the host (page-locked staging), host sort
-    if (!records_on_host) {
-        hl.resize(ncand); hs.resize((size_t)ncand * N);
-        const size_t lbytes = ((size_t)ncand * 4 + 63) & ~(size_t)63, sbytes = (size_t)ncand * 4 * N;
-        HIPCHK(ctx, ctx->pin_seed.ensure(64 + lbytes + sbytes));
-        char *pin = ctx->pin_seed.as<char>() + 64;
-        HIPCHK(ctx, hipMemcpyAsync(pin, ctx->mlen.p, (size_t)ncand * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(pin + lbytes, ctx->mstart.p, sbytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(hl.data(), pin, (size_t)ncand * 4);
-        memcpy(hs.data(), pin + lbytes, sbytes);
-        TRACE(ctx, "records copy");
-    }
-    std::vector<uint32_t> &order = ctx->sdh.order; order.clear(); order.reserve(ncand);
-    std::vector<uint64_t> &k1 = ctx->sdh.k1; k1.resize(ncand);   // (first component, |start|) packed for a fast first-level compare
-    for (uint32_t i = 0; i < ncand; i++) {
-        if (hl[i] == 0) continue;
-        order.push_back(i);
-        const int32_t *s = &hs[(size_t)i * N];
-        int f = 0; while (f < N && s[f] == 0) f++;
-        uint64_t a = f < N ? (uint64_t)std::abs((int64_t)s[f]) : 0;
-        k1[i] = ((uint64_t)f << 40) | a;
-    }
-    const uint32_t nm = (uint32_t)order.size();
-    {   // LSD radix sort of the record indices by k1 (first component << 40 | start): 4 passes of 12 bits,
-        // then the rare equal-k1 groups are ordered with the full comparator
-        std::vector<uint32_t> &tmp = ctx->sdh.tmp; tmp.resize(nm);
-        uint32_t *src = order.data(), *dst = tmp.data();
-        for (int pass = 0; pass < 4; pass++) {
-            const int sh = 12 * pass;
-            uint32_t cnt[4097] = {0};
-            for (uint32_t i = 0; i < nm; i++) cnt[(((k1[src[i]] & 0xffffffffULL) | ((k1[src[i]] >> 40) << 32)) >> sh & 4095) + 1]++;
-            for (int b = 0; b < 4096; b++) cnt[b + 1] += cnt[b];
-            for (uint32_t i = 0; i < nm; i++) dst[cnt[((k1[src[i]] & 0xffffffffULL) | ((k1[src[i]] >> 40) << 32)) >> sh & 4095]++] = src[i];
-            std::swap(src, dst);
-        }
-        if (src != order.data()) std::copy(src, src + nm, order.data());
-        auto full_less = [&](uint32_t x, uint32_t y) {
-            const int32_t *a = &hs[(size_t)x * N], *b = &hs[(size_t)y * N];
-            uint32_t ma = 0, mb = 0;
-            for (int g = 0; g < N; g++) { if (a[g]) ma |= 1u << g; if (b[g]) mb |= 1u << g; }
-            if (ma != mb) return ma < mb;
-            for (int g = 0; g < N; g++) if (a[g] != b[g]) return a[g] < b[g];
-            return hl[x] < hl[y];
-        };
-        for (uint32_t i = 0; i < nm;) {
-            uint32_t j = i + 1;
-            while (j < nm && k1[order[j]] == k1[order[i]]) j++;
-            if (j - i > 1) std::sort(order.begin() + i, order.begin() + j, full_less);
-            i = j;
-        }
-    }
-    ctx->match_len.resize(nm); ctx->match_start.resize((size_t)nm * N);
-    for (uint32_t i = 0; i < nm; i++) {
-        uint32_t o = order[i];
-        ctx->match_len[i] = hl[o];
-        for (int g = 0; g < N; g++) ctx->match_start[(size_t)i * N + g] = hs[(size_t)o * N + g];
-    }
-    ctx->n_matches = nm;
-    if (n_matches) *n_matches = nm;
-    TRACE(ctx, "canonical sort");
+    seed_trace(ctx, "extract", ps.trace_t0);
     return MAUVE_OK;
 }
 
-// stable LSD radix sort of (32-bit key, 32-bit value) pairs for the other translation units (chain_dev.hip)
-int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io, uint32_t **vals_io, uint32_t *keys_alt, uint32_t *vals_alt,
-                   int timer_id)
+// SeedMatchEnumerator: runs -> matches on the device, only the CSR result goes to the host
+template <typename KeyT, typename ValT>
+static int export_enumerator(SeedPass<KeyT, ValT> &ps)
 {
-    return sort_pairs<uint32_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
+    mauve_ctx *ctx = ps.ctx; const uint32_t sorted_n = ps.ns; KeyT *keys = ps.keys; ValT *vals = ps.vals;
+    EnumRequest &q = *ps.rq.enumerate;
+    using namespace devscan;
+    const uint32_t nb = (sorted_n + TILE - 1) / TILE, blocks = (sorted_n + 255) / 256;
+    HIPCHK(ctx, ctx->run_sum.ensure((size_t)sorted_n * 4 + 64 + ((size_t)sorted_n + 2) * 8 * 3 + (size_t)nb * 16 + 256));
+    uint32_t *emit = ctx->run_sum.as<uint32_t>();
+    int64_t *soff = reinterpret_cast<int64_t *>(ctx->run_sum.as<char>() + (((size_t)sorted_n * 4 + 63) & ~(size_t)63));
+    int64_t *d_mult = soff + sorted_n + 2, *d_off = d_mult + sorted_n + 2, *bsum = d_off + sorted_n + 2, *tot = bsum + nb + 2;
+    uint32_t *bcnt = reinterpret_cast<uint32_t *>(tot + 4);
+    hipLaunchKernelGGL((enum_runs<KeyT, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.min_multi, q.max_multi, q.direct_only, emit);
+    hipLaunchKernelGGL((vscan_partial<int64_t, EmitVal>), dim3(nb), dim3(256), 0, ctx->stream, EmitVal{emit}, sorted_n, bsum);
+    hipLaunchKernelGGL((vscan_write<int64_t, EmitVal>), dim3(nb), dim3(256), 0, ctx->stream, EmitVal{emit}, sorted_n, bsum, soff, tot + 1);
+    const EnumRuns er{emit, soff, sorted_n, d_mult, d_off, tot};
+    hipLaunchKernelGGL((cmp_count<EnumRuns>), dim3(nb), dim3(256), 0, ctx->stream, er, bcnt);
+    hipLaunchKernelGGL((cmp_write<EnumRuns>), dim3(nb), dim3(256), 0, ctx->stream, er, bcnt);
+    HIPCHK(ctx, hipGetLastError());
+    int64_t ht[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(ht, tot, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    q.n = ht[0]; q.ns = ht[1];
+    if (q.starts) {
+        HIPCHK(ctx, ctx->sorted_rec.ensure(((size_t)q.ns + 1) * 8));
+        hipLaunchKernelGGL((enum_write<KeyT, ValT>), dim3(blocks), dim3(256), 0, ctx->stream, keys, vals, sorted_n, q.direct_only, emit, soff,
+                           ps.tab.gpos_off[ps.rq.only_seq], ctx->sorted_rec.as<int64_t>());
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(q.mult, d_mult, (size_t)q.n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(q.start_off, d_off, ((size_t)q.n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(q.starts, ctx->sorted_rec.p, (size_t)q.ns * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return MAUVE_OK;
 }
 
-// Index width of a seed pass (DESIGN.md S3): wide values when the pass has 2^31 windows or more; MAUVE_WIDE_INDEX=1 forces them for every
-// pass (test switch: small inputs take the wide kernels against the oracle).  Every other pass runs the narrow instantiations.
-bool seedpass_wide(int64_t total_windows)
+// sorted-mer-list export: hand the sorted pairs to the host
+template <typename KeyT, typename ValT>
+static int export_sorted_list(SeedPass<KeyT, ValT> &ps)
 {
-    static const bool force = [] { const char *e = getenv("MAUVE_WIDE_INDEX"); return e && e[0] == '1' && e[1] == 0; }();
-    return force || total_windows >= (1LL << 31);
+    constexpr bool WIDEV = sizeof(ValT) == 8;
+    mauve_ctx *ctx = ps.ctx; const uint32_t sorted_n = ps.ns;
+    std::vector<uint64_t> *out_keys = ps.rq.out_keys; std::vector<uint32_t> *out_vals = ps.rq.out_vals;
+    std::vector<KeyT> hk(sorted_n);
+    out_vals->resize(sorted_n);
+    std::vector<ValT> hv(WIDEV ? sorted_n : 0);
+    HIPCHK(ctx, hipMemcpyAsync(hk.data(), ps.keys, (size_t)sorted_n * sizeof(KeyT), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(WIDEV ? (void *)hv.data() : (void *)out_vals->data(), ps.vals, (size_t)sorted_n * sizeof(ValT), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    out_keys->resize(sorted_n);
+    for (uint32_t i = 0; i < sorted_n; i++) (*out_keys)[i] = (uint64_t)hk[i];
+    if (WIDEV) {                                // wide: local to the genome already (index | strand << 31), as the narrow caller makes them
+        const uint32_t g0 = ps.tab.gpos_off[ps.rq.only_seq];
+        for (uint32_t i = 0; i < sorted_n; i++) (*out_vals)[i] = ((uint32_t)hv[i] - g0) | ((uint32_t)((uint64_t)hv[i] >> 63) << 31);
+    }
+    return MAUVE_OK;
 }
 
-// the seedpass_impl instantiation of a pass: key width by the seed weight (and SEG), value width by seedpass_wide
-#define SEEDPASS_DISPATCH(KEY, SEGV, ...) \
-    (seedpass_wide(total) ? seedpass_impl<KEY, SEGV, uint64_t>(__VA_ARGS__) : seedpass_impl<KEY, SEGV, uint32_t>(__VA_ARGS__))
+// ---- launchers and checks the finder stages share ----
+// Capacities of the compacted lists are handed to the kernels that fill them (a store past the end is skipped, the counter still counts)
+// and checked against the counts that come back.
+static bool cand_overflow(SeedState &st, uint32_t nc)
+{
+    if (nc > st.cand_cap) st.ctx->err = "seed pass: " + std::to_string(nc) + " candidates for a list of " + std::to_string(st.cand_cap);
+    return nc > st.cand_cap;
+}
+
+// extension phase A: run starts from the whole hit table
+template <bool SEG>
+static int launch_runs(SeedState &st)
+{
+    mauve_ctx *ctx = st.ctx; const uint32_t P = st.P;
+    { KernelTimer t(ctx, MAUVE_K_RUNS, P);
+      hipLaunchKernelGGL((mum_runs<SEG>), dim3((P + RUNS_TILE - 1) / RUNS_TILE), dim3(256), 0, ctx->stream, st.tab,
+                         st.sh.span, st.tmask, st.tpos, P, st.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), st.rq.seg,
+                         st.rq.nseg, st.cand_cap, 0u); }
+    HIPCHK(ctx, hipGetLastError());
+    return MAUVE_OK;
+}
+
+// extension phase B over the first ncand entries of the candidate list (ncand_dev / counters_out: see mum_extend)
+template <bool SEG, bool WIDEV>
+static int launch_extend(SeedState &st, uint32_t blocks, uint32_t ncand, int32_t *o_len, int32_t *o_start, const uint32_t *ncand_dev = nullptr,
+                         uint32_t *counters_out = nullptr)
+{
+    mauve_ctx *ctx = st.ctx;
+    KernelTimer t(ctx, MAUVE_K_EXTEND, ncand);
+    hipLaunchKernelGGL((mum_extend<SEG, WIDEV>), dim3(blocks), dim3(256), 0, ctx->stream, st.packed, st.tab, st.sh, st.tmask, st.tpos, st.P,
+                       ctx->cand.as<uint32_t>(), ncand, st.rq.extend, o_len, o_start, st.rq.seg, st.rq.nseg, st.vmask, st.cmask, ncand_dev, counters_out);
+    HIPCHK(ctx, hipGetLastError());
+#ifdef MAUVE_EXT_STATS
+    if (seed_trace_on()) {
+        unsigned long long h[8]; hipStreamSynchronize(ctx->stream);
+        hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ext_stats), sizeof h); unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_ext_stats), z, sizeof z);
+        fprintf(stderr, "[trace]   extend stats: %llu rounds, %llu waves, wave time mean %.1f us max %.1f us (setup %.1f, left walk %.1f, right walk %.1f), most rounds of a wave %llu\n", h[0], h[4],
+                h[4] ? h[2] / (double)h[4] / 100.0 : 0.0, h[3] / 100.0, h[4] ? h[1] / (double)h[4] / 100.0 : 0.0, h[4] ? h[6] / (double)h[4] / 100.0 : 0.0,
+                h[4] ? h[7] / (double)h[4] / 100.0 : 0.0, h[5]);
+    }
+#endif
+    return MAUVE_OK;
+}
+
+// the records of all passes accumulate on the device: nc more behind the cand_total there are
+template <bool SEG, bool WIDEV>
+static int extend_candidates(SeedState &st, uint32_t nc, uint32_t max_blocks)
+{
+    mauve_ctx *ctx = st.ctx; const int N = st.tab.nseq;
+    HIPCHK(ctx, ctx->mlen.ensure_keep((size_t)(st.cand_total + nc) * 4 + 4, (size_t)st.cand_total * 4, ctx->stream));
+    HIPCHK(ctx, ctx->mstart.ensure_keep((size_t)(st.cand_total + nc) * 4 * N + 4, (size_t)st.cand_total * 4 * N, ctx->stream));
+    if (int rc = launch_extend<SEG, WIDEV>(st, std::min<uint32_t>((nc + 3) / 4, max_blocks), nc, ctx->mlen.as<int32_t>() + st.cand_total,
+                                           ctx->mstart.as<int32_t>() + (size_t)st.cand_total * N)) return rc;
+    st.cand_total += nc;
+    seed_trace(ctx, "extend", st.trace_t0);
+    return MAUVE_OK;
+}
+
+// PairwiseMatchFinder over several pairs.  The runs that can matter to any pair are listed once (see run_summary); then the passes run
+// in groups: pairs with different lower genomes write disjoint slices of the hit table, so up to
+// N - 1 of them share one join launch (the run list is read once per group instead of once per pair), one run-detection launch
+// (blockIdx.y = pair), one candidate list, one round trip and one extension launch: 28 passes of an 8-genome guide tree are 7 groups.
+template <typename KeyT, typename ValT>
+static int pairwise_passes(SeedPass<KeyT, ValT> &ps)
+{
+    constexpr bool WIDEV = sizeof(ValT) == 8;
+    mauve_ctx *ctx = ps.ctx; const GenomeTab &tab = ps.tab; const uint32_t P = ps.P, ns = ps.ns, list_cap = list_cap_env();
+    const std::vector<FinderPass> &passes = ps.passes;
+    const size_t cap = (size_t)ns / 2 + 1;
+    const uint32_t run_cap = list_cap ? std::min<uint32_t>((uint32_t)cap, list_cap) : (uint32_t)cap;
+    HIPCHK(ctx, ctx->run_sum.ensure(3 * cap * 4));
+    uint32_t *rstart = ctx->run_sum.as<uint32_t>(), *rlen = rstart + cap, *runiq = rlen + cap;
+    HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    { KernelTimer t(ctx, MAUVE_K_JOIN, ns);
+      hipLaunchKernelGGL((run_summary<KeyT, ValT>), dim3((ns + 1023) / 1024), dim3(256), 0, ctx->stream, ps.keys, ps.vals, ns, tab,
+                         (int)ps.pl.has_invalid, rstart, rlen, runiq, ctx->counters.as<uint32_t>() + 2, run_cap); }
+    HIPCHK(ctx, hipGetLastError());
+    const uint32_t *cw;
+    if (int rc = seed_counters(ctx, 16, &cw)) return rc;
+    const uint32_t nruns = cw[2];
+    if (nruns > run_cap) { ctx->err = "seed pass: " + std::to_string(nruns) + " runs for a list of " + std::to_string(run_cap); return MAUVE_ERR_LIMIT; }
+    seed_trace(ctx, "run summary", ps.trace_t0);
+    if (!nruns) return MAUVE_OK;                               // no run that matters to any pair: no candidate
+    // one candidate list per group: a pair has at most one hit per window of its lower genome, the lower genomes of a group are
+    // different, so a group has at most P candidates (a single pass: P / 2, "a hit needs two entries" -- not enough here)
+    HIPCHK(ctx, ctx->cand.ensure(((size_t)P + 1) * 4));
+    ps.cand_cap = list_cap ? std::min<uint32_t>(P + 1, list_cap) : P + 1;
+    std::vector<char> used(passes.size(), 0);
+    for (size_t left = passes.size(); left;) {
+        PairGroup grp; memset(&grp, 0, sizeof grp);
+        uint32_t amask = 0, maxslice = 0, slices = 0;
+        for (size_t q = 0; q < passes.size(); q++) {
+            if (used[q]) continue;
+            const int ga = __builtin_ctz(passes[q].consider), gb = 31 - __builtin_clz(passes[q].consider);
+            if (amask >> ga & 1u) continue;
+            used[q] = 1; left--;
+            // the hit table is indexed by the anchor's window = a window of the lowest genome of the pass: a pass over one genome pair
+            // (the guide tree runs N (N - 1) / 2 of them) clears and scans that genome's slice only
+            const uint32_t lo = tab.gpos_off[ga], hi = std::min<uint32_t>(tab.gpos_off[ga + 1], P);
+            if (hi <= lo) continue;                            // (a genome shorter than the seed has no window: nothing can be anchored in it)
+            grp.ga[grp.n] = ga; grp.gb[grp.n] = gb; grp.lo[grp.n] = lo; grp.hi[grp.n] = hi; grp.n++;
+            amask |= 1u << ga; maxslice = std::max(maxslice, hi - lo); slices += hi - lo;
+        }
+        if (!grp.n) continue;
+        for (int y = 0; y < grp.n; y++) HIPCHK(ctx, hipMemsetAsync(ps.tmask + grp.lo[y], 0, (size_t)(grp.hi[y] - grp.lo[y]) * 4, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+        { KernelTimer t(ctx, MAUVE_K_JOIN, nruns);
+          hipLaunchKernelGGL(join_pair_group<ValT>, dim3((nruns + 255) / 256), dim3(256), 0, ctx->stream, ps.vals, tab, rstart, rlen, runiq, nruns, grp, ps.tmask, ps.tpos); }
+        HIPCHK(ctx, hipGetLastError());
+        seed_trace(ctx, "join", ps.trace_t0);
+        { KernelTimer t(ctx, MAUVE_K_RUNS, slices);
+          hipLaunchKernelGGL(mum_runs_group, dim3((maxslice + RUNS_TILE - 1) / RUNS_TILE, (uint32_t)grp.n), dim3(256), 0, ctx->stream, tab, ps.sh.span, ps.tmask, ps.tpos, grp,
+                             ps.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), ps.cand_cap); }
+        HIPCHK(ctx, hipGetLastError());
+        if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }
+        if (int rc = seed_counters(ctx, 16, &cw)) return rc;
+        const uint32_t nc = cw[1];
+        if (cand_overflow(ps, nc)) return MAUVE_ERR_LIMIT;
+        seed_trace(ctx, "runs", ps.trace_t0);
+        if (seed_trace_on()) fprintf(stderr, "[trace]   %u candidates of %u windows (%d pairs at once)\n", nc, slices, grp.n);
+        if (nc == 0) continue;
+        if (int rc = extend_candidates<false, WIDEV>(ps, nc, 256 * 8)) return rc;
+    }
+    return MAUVE_OK;
+}
+
+// A tiny pass (a round of the LCB extension, a small guide-tree node, a small recursion batch) is a handful of 5-10 us kernels: the round
+// trip that fetched the candidate count before the extension kernel could be launched cost as much as the pass.  Its candidate list has
+// at most a few thousand entries, so the extension is launched for the CAPACITY of the list with the count left on the device, and the
+// counters come back together with the records: one synchronisation per pass instead of two.
+// The records and the counters go straight into page-locked host memory (the device writes it in place: a handful of candidates), so the
+// round trip is one synchronisation and no copy kernel.  (Not when the canonical order is to be made on the device -- a test setting for
+// lists this small: then the records stay in device memory and are copied as well.)
+// (A tiny pass is the only finder pass of its call -- seed_plan: no host hits, not pairwise -- and tiny_join clears the hit table for itself.)
+static_assert(TJ_MAX / 2 + 1 <= 8192, "a tiny pass's candidate list: extension launched for its capacity");
+template <bool SEG, bool WIDEV>
+static int tiny_pass(SeedState &st, const FinderPass &fp)
+{
+    mauve_ctx *ctx = st.ctx; const uint32_t P = st.P, cand_cap = st.cand_cap; const int N = st.tab.nseq;
+    // (tiny_join needs more LDS than a launch gets by default.  A static of every instantiation: asked for at least once for each of the two kernels)
+    static const bool tj_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(tiny_join<WIDEV>), hipFuncAttributeMaxDynamicSharedMemorySize, TJ_SLOTS * 8) == hipSuccess;
+    if (!tj_attr) { ctx->err = "tiny_join: cannot reserve its LDS"; return MAUVE_ERR_HIP; }
+    { KernelTimer t(ctx, MAUVE_K_JOIN, P);
+      hipLaunchKernelGGL(tiny_join<WIDEV>, dim3(1), dim3(1024), TJ_SLOTS * 8, ctx->stream, st.packed, st.tab, st.sh, P, st.vmask, st.cmask, fp.rule, fp.want, st.tmask, st.tpos,
+                         ctx->counters.as<uint32_t>() + 9, SEG ? st.rq.seg : (const uint32_t *)nullptr, st.rq.nseg, ctx->counters.as<uint32_t>(), 0u, P); }
+    HIPCHK(ctx, hipGetLastError());
+    seed_trace(ctx, "join", st.trace_t0);
+    if (int rc = launch_runs<SEG>(st)) return rc;
+    if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // host work that does not depend on the pass: the kernels above are still running
+    const size_t lbytes = ((size_t)cand_cap * 4 + 63) & ~(size_t)63, sbytes = (size_t)cand_cap * 4 * N;
+    HIPCHK(ctx, ctx->pin_seed.ensure(64 + lbytes + sbytes));
+    char *pin = ctx->pin_seed.as<char>();
+    const bool host_out = cand_cap < canon_device_min();
+    if (!host_out) { HIPCHK(ctx, ctx->mlen.ensure((size_t)cand_cap * 4 + 4)); HIPCHK(ctx, ctx->mstart.ensure((size_t)cand_cap * 4 * N + 4)); }
+    int32_t *o_len = host_out ? reinterpret_cast<int32_t *>(pin + 64) : ctx->mlen.as<int32_t>();
+    int32_t *o_st = host_out ? reinterpret_cast<int32_t *>(pin + 64 + lbytes) : ctx->mstart.as<int32_t>();
+    if (int rc = launch_extend<SEG, WIDEV>(st, std::min<uint32_t>((cand_cap + 3) / 4, 512), cand_cap, o_len, o_st, ctx->counters.as<uint32_t>() + 1,
+                                           reinterpret_cast<uint32_t *>(pin))) return rc;
+    if (!host_out) {
+        HIPCHK(ctx, hipMemcpyAsync(pin + 64, ctx->mlen.p, (size_t)cand_cap * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(pin + 64 + lbytes, ctx->mstart.p, sbytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t nc = reinterpret_cast<const uint32_t *>(pin)[1];
+    if (reinterpret_cast<const uint32_t *>(pin)[9]) { ctx->err = "tiny_join: anchor out of range (internal error)"; return MAUVE_ERR_HIP; }
+    if (cand_overflow(st, nc)) return MAUVE_ERR_LIMIT;
+    seed_trace(ctx, "runs + extend (one round trip)", st.trace_t0);
+    if (seed_trace_on()) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
+    ctx->sdh.hl.assign(reinterpret_cast<const int32_t *>(pin + 64), reinterpret_cast<const int32_t *>(pin + 64) + nc);
+    ctx->sdh.hs.assign(reinterpret_cast<const int32_t *>(pin + 64 + lbytes), reinterpret_cast<const int32_t *>(pin + 64 + lbytes) + (size_t)nc * N);
+    st.cand_total = nc; st.records_on_host = true;
+    return MAUVE_OK;
+}
+
+// Ranges join_hash declined (a bucket beyond its LDS table): full sort + serial join of each slice, or of the whole list when there
+// are more of them than the list holds; then the run detection again.  *nc: the candidates after it.
+template <typename KeyT, bool SEG, typename ValT>
+static int join_overflow_slices(SeedPass<KeyT, ValT> &ps, const FinderPass &fp, uint32_t novf, uint32_t *nc)
+{
+    mauve_ctx *ctx = ps.ctx; KeyT *keys = ps.keys; ValT *vals = ps.vals;
+    std::vector<uint32_t> rng;
+    if (novf > (uint32_t)HJ_OVF_CAP) rng = {0u, ps.ns};
+    else {
+        rng.resize(2 * (size_t)novf);
+        HIPCHK(ctx, hipMemcpy(rng.data(), ctx->join_ovf.as<uint32_t>() + 2, rng.size() * 4, hipMemcpyDeviceToHost));
+    }
+    KeyT *alt_k = keys == ctx->keysA.as<KeyT>() ? ctx->keysB.as<KeyT>() : ctx->keysA.as<KeyT>();
+    ValT *alt_v = vals == ctx->valsA.as<ValT>() ? ctx->valsB.as<ValT>() : ctx->valsA.as<ValT>();
+    // each slice sorted in full where it lies (the sorted pairs end up in this buffer or the other one), then ONE join over all slices
+    const size_t nsl = rng.size() / 2;
+    std::vector<uint32_t> sl_lo(nsl), sl_pre(nsl + 1, 0);
+    uint64_t tot_sl = 0;
+    for (size_t q = 0; q < nsl; q++) {
+        const uint32_t s0 = rng[2 * q], cnt = rng[2 * q + 1] - rng[2 * q];
+        KeyT *kp = keys + s0; ValT *vp = vals + s0;
+        if (int rc = sort_pairs<KeyT, ValT>(ctx, cnt, ps.pl.full_bits, &kp, &vp, alt_k + s0, alt_v + s0, false, MAUVE_K_JOIN)) return rc;
+        if (kp != keys + s0) {           // an odd number of passes: the slice now lies in the other buffer -- copy it back
+            HIPCHK(ctx, hipMemcpyAsync(keys + s0, kp, (size_t)cnt * sizeof(KeyT), hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(vals + s0, vp, (size_t)cnt * sizeof(ValT), hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        sl_lo[q] = s0; tot_sl += cnt; sl_pre[q + 1] = (uint32_t)tot_sl;
+    }
+    if (tot_sl) {
+        HIPCHK(ctx, ctx->join_bound.ensure((2 * nsl + 1) * 4));
+        HIPCHK(ctx, ctx->pin_seed.ensure(64 + (2 * nsl + 1) * 4));
+        uint32_t *hp = reinterpret_cast<uint32_t *>(ctx->pin_seed.as<char>() + 64);
+        memcpy(hp, sl_lo.data(), nsl * 4); memcpy(hp + nsl, sl_pre.data(), (nsl + 1) * 4);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->join_bound.p, hp, (2 * nsl + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        KernelTimer t(ctx, MAUVE_K_JOIN, (uint32_t)tot_sl);
+        hipLaunchKernelGGL((mum_join_slices<KeyT, SEG, ValT>), dim3((uint32_t)((tot_sl + 255) / 256)), dim3(256), 0, ctx->stream, (const KeyT *)keys, (const ValT *)vals,
+                           ctx->join_bound.as<uint32_t>(), ctx->join_bound.as<uint32_t>() + nsl, (uint32_t)nsl, ps.tab, fp.rule, fp.want,
+                           fp.consider, ps.tmask, ps.tpos, (int)ps.pl.has_invalid);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));     // the page-locked slice table is reused by the counter copy below
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    if (int rc = launch_runs<SEG>(ps)) return rc;
+    const uint32_t *cw;
+    if (int rc = seed_counters(ctx, 16, &cw)) return rc;
+    *nc = cw[1];
+    if (seed_trace_on()) fprintf(stderr, "[trace]   join_hash handed back %u range(s)\n", novf);
+    return MAUVE_OK;
+}
+
+// One finder pass that is neither tiny nor part of a pair group: clear the hit table, fill it (host hits, join_hash or mum_join:
+// seed_plan), run detection, extension.
+template <typename KeyT, bool SEG, typename ValT>
+static int finder_pass(SeedPass<KeyT, ValT> &ps, const FinderPass &fp)
+{
+    constexpr bool WIDEV = sizeof(ValT) == 8;
+    mauve_ctx *ctx = ps.ctx; const uint32_t P = ps.P, ns = ps.ns; const int N = ps.tab.nseq;
+    const HostHits *hh = ps.rq.hits;
+    HIPCHK(ctx, hipMemsetAsync(ps.tmask, 0, (size_t)P * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    if (hh) {
+        HIPCHK(ctx, ctx->run_sum.ensure((size_t)hh->n * (N + 1) * 4 + 64));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->run_sum.p, hh->rec, (size_t)hh->n * (N + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (hh->n) hipLaunchKernelGGL(hits_scatter<WIDEV>, dim3((hh->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->run_sum.as<uint32_t>(), hh->n, N, P, ps.tmask, ps.tpos, ps.tab);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the host records must outlive the copy
+    } else if (ps.pl.hash_path) {
+        const uint32_t nchunk = (ns + HJ_T - 1) / HJ_T;
+        HIPCHK(ctx, ctx->join_ovf.ensure((2 + 2 * (size_t)HJ_OVF_CAP) * 4));        // the ranges; their count sits in the counter block (words 8, 9)
+        KernelTimer t(ctx, MAUVE_K_JOIN, ns);
+        HIPCHK(ctx, ctx->join_bound.ensure(((size_t)nchunk + 2) * 4));
+        hipLaunchKernelGGL((join_bounds<KeyT>), dim3((nchunk + 1 + 3) / 4), dim3(256), 0, ctx->stream, ps.keys, ns, ps.L, nchunk,
+                           ctx->join_bound.as<uint32_t>());
+#define JH_LAUNCH(W) hipLaunchKernelGGL((join_hash<KeyT, W, ValT>), dim3(nchunk), dim3(256), 0, ctx->stream, ps.keys, ps.vals, ns, \
+                                           ctx->join_bound.as<uint32_t>(), ps.tab, fp.rule, fp.want, ps.tmask, ps.tpos, ctx->counters.as<uint32_t>() + 8, ctx->join_ovf.as<uint32_t>(), P)
+        if (N > 16) JH_LAUNCH(true);
+        else JH_LAUNCH(false);
+#undef JH_LAUNCH
+    } else
+    { KernelTimer t(ctx, MAUVE_K_JOIN, ns);
+      hipLaunchKernelGGL((mum_join<KeyT, SEG, ValT>), dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ps.keys, ps.vals, ns, ps.tab, fp.rule,
+                         fp.want, fp.consider, ps.tmask, ps.tpos, P, (int)ps.pl.has_invalid); }
+    HIPCHK(ctx, hipGetLastError());
+    seed_trace(ctx, "join", ps.trace_t0);
+    if (int rc = launch_runs<SEG>(ps)) return rc;
+    if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // host work that does not depend on the pass: the kernels above are still running
+    const uint32_t *cw;
+    if (int rc = seed_counters(ctx, 48, &cw)) return rc;     // run counters + join_hash's overflow count
+    uint32_t nc = cw[1];
+    const uint32_t novf = ps.pl.hash_path ? cw[8] : 0u;
+    if (ps.pl.hash_path && cw[9]) { ctx->err = "join_hash: anchor out of range (internal error)"; return MAUVE_ERR_HIP; }
+    if (novf) if (int rc = join_overflow_slices<KeyT, SEG, ValT>(ps, fp, novf, &nc)) return rc;
+    if (cand_overflow(ps, nc)) return MAUVE_ERR_LIMIT;
+    seed_trace(ctx, "runs", ps.trace_t0);
+    if (seed_trace_on()) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
+    if (nc == 0) return MAUVE_OK;
+    // six waves per SIMD fit (77 registers); two rounds of workgroups even out the candidates' different lengths (measured: 5 .. 8 per compute unit
+    // within 5 % of each other, 12 .. 14 another 10 % faster)
+    constexpr int EXT_BLOCKS_PER_CU = 12;
+    return extend_candidates<SEG, WIDEV>(ps, nc, (uint32_t)(ctx->cus * EXT_BLOCKS_PER_CU));
+}
+
+// One seed pass over a genome set: extraction, sort, then an export or the finder passes and the common finish (seed_finish.hip).
+// SEG: the set is segmented (recursive anchoring).  Results land in ctx->match_len / match_start (canonical order).
+template <typename KeyT, bool SEG, typename ValT>
+static int seedpass_stages(const SeedState &st0)
+{
+    constexpr bool WIDEV = sizeof(ValT) == 8;
+    SeedPass<KeyT, ValT> ps(st0);
+    mauve_ctx *ctx = ps.ctx; const SeedRequest &rq = ps.rq; const uint32_t P = ps.P; const int N = ps.tab.nseq;
+    if (seed_trace_on()) fprintf(stderr, "[trace] seed pass: %u windows, %d-bit keys, %s window index (%d-bit values)\n", P, (int)sizeof(KeyT) * 8,
+                                  WIDEV ? "wide" : "narrow", (int)sizeof(ValT) * 8);
+    if (int rc = seed_plan(ctx, ps.sh, ps.tab, rq, P, ps.vmask || ps.cmask, SEG, (int)sizeof(KeyT) * 8, &ps.pl, &ps.passes)) return rc;
+    if (int rc = extract<KeyT, SEG, ValT>(ps)) return rc;
+    if (ps.ns == 0) { if (rq.n_matches) *rq.n_matches = 0; return MAUVE_OK; }
+    ps.L = ps.pl.low_bits(ps.ns);
+    if (!rq.hits && !ps.pl.tiny)
+        if (int rc = sort_pairs<KeyT, ValT>(ctx, ps.ns, ps.pl.full_bits, &ps.keys, &ps.vals, ctx->keysB.as<KeyT>(), ctx->valsB.as<ValT>(), ps.have_hist0, -1, ps.L)) return rc;
+    seed_trace(ctx, "sort", ps.trace_t0);
+    if (rq.enumerate) return export_enumerator(ps);
+    if (rq.out_keys) return export_sorted_list(ps);
+
+    // ---- join + extension, once per finder pass ----
+    HIPCHK(ctx, ctx->posmask.ensure((size_t)P * 4));             // tmask
+    HIPCHK(ctx, ctx->hit_pos.ensure((size_t)P * 4 * N));         // tpos [P][N]
+    ps.tmask = ctx->posmask.as<uint32_t>(); ps.tpos = ctx->hit_pos.as<uint32_t>();
+    ps.cand_cap = P / 2 + 1;                                     // a hit needs >= 2 entries
+    HIPCHK(ctx, ctx->cand.ensure((size_t)ps.cand_cap * 4));
+    if (list_cap_env()) ps.cand_cap = std::min(ps.cand_cap, list_cap_env());
+    ctx->sdh.hl.clear(); ctx->sdh.hs.clear();                    // (host scratch kept across calls)
+    if (ps.pl.tiny) {
+        if (int rc = tiny_pass<SEG, WIDEV>(ps, ps.passes[0])) return rc;
+    } else if (ps.pl.use_summary) {
+        if (int rc = pairwise_passes(ps)) return rc;
+    } else {
+        for (const FinderPass &fp : ps.passes)
+            if (int rc = finder_pass<KeyT, SEG, ValT>(ps, fp)) return rc;
+    }
+    return seed_finish(ctx, ps.gs, rq, ps.cand_total, ps.records_on_host, ps.trace_t0);
+}
+
+// what every entry point starts with: the seed's shape, the genomes the request is about (seq: one sequence; nullptr: all of them), the window table
+static int seedpass_prologue(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, const int *seq, SeedShape *sh, GenomeTab *tab, int64_t *total)
+{
+    if (!make_seed_shape(pattern, sh)) { ctx->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
+    if (!seq && gs.nseq < 1) { ctx->err = "no genomes set"; return MAUVE_ERR_STATE; }
+    if (seq && (*seq < 0 || *seq >= gs.nseq)) { ctx->err = "sequence index out of range"; return MAUVE_ERR_ARG; }
+    return build_tab(ctx, gs, sh->span, tab, total);
+}
+
+static void reset_match_list(mauve_ctx *ctx, int64_t *n_matches)
+{
+    ctx->n_matches = 0; ctx->match_len.clear(); ctx->match_start.clear(); ctx->matches_pending = false;
+    ctx->dev_rec_n = -1;
+    if (n_matches) *n_matches = 0;
+}
+
+// the instantiation of a pass: key width by the seed weight (64 bits when segmented), value width by seedpass_wide
+static int seedpass_dispatch(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, int64_t total, const SeedRequest &rq)
+{
+    SeedState st{ctx, gs, sh, tab, rq, (uint32_t)total, gs.buf->as<uint64_t>(), gs.vmask ? gs.vmask->as<uint64_t>() : nullptr,
+                 gs.cmask ? gs.cmask->as<uint64_t>() : nullptr};
+    st.trace_t0 = now_ms();
+    const bool wide = seedpass_wide(total);
+    if (rq.seg) return wide ? seedpass_stages<uint64_t, true, uint64_t>(st) : seedpass_stages<uint64_t, true, uint32_t>(st);
+    if (2 * sh.weight <= 32) return wide ? seedpass_stages<uint32_t, false, uint64_t>(st) : seedpass_stages<uint32_t, false, uint32_t>(st);
+    return wide ? seedpass_stages<uint64_t, false, uint64_t>(st) : seedpass_stages<uint64_t, false, uint32_t>(st);
+}
 
 int seedpass_run(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, int mode, uint64_t mask, int extend,
                  const uint32_t *seg_dev, uint32_t nseg, int64_t *n_matches)
 {
-    SeedShape sh;
-    if (!make_seed_shape(pattern, &sh)) { ctx->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
-    if (gs.nseq < 1) { ctx->err = "no genomes set"; return MAUVE_ERR_STATE; }
-    GenomeTab tab; int64_t total = 0;
-    int rc = build_tab(ctx, gs, sh.span, &tab, &total);
-    if (rc) return rc;
-    ctx->n_matches = 0; ctx->match_len.clear(); ctx->match_start.clear(); ctx->matches_pending = false;
-    ctx->dev_rec_n = -1;
-    if (n_matches) *n_matches = 0;
+    SeedShape sh; GenomeTab tab; int64_t total = 0;
+    if (int rc = seedpass_prologue(ctx, gs, pattern, nullptr, &sh, &tab, &total)) return rc;
+    reset_match_list(ctx, n_matches);
     if (total == 0) return MAUVE_OK;
-    if (seg_dev) return SEEDPASS_DISPATCH(uint64_t, true, ctx, gs, sh, tab, total, mode, mask, extend, -1, seg_dev, nseg, n_matches, nullptr, nullptr);
-    if (2 * sh.weight <= 32) return SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, mode, mask, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
-    return SEEDPASS_DISPATCH(uint64_t, false, ctx, gs, sh, tab, total, mode, mask, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
+    SeedRequest rq;
+    rq.mode = mode; rq.mask = mask; rq.extend = extend; rq.n_matches = n_matches;
+    if (seg_dev) { rq.seg = seg_dev; rq.nseg = nseg; }
+    return seedpass_dispatch(ctx, gs, sh, tab, total, rq);
 }
 
 // extension + canonical order of hits a host-side finder supplies (records of 1 + nseq words: component set, values -- global window
 // index | strand << 31, or local to the genome when seedpass_wide says so for the genome set: api.cpp builds them by the same rule)
 int seedpass_from_hits(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, const HostHits &hits, int extend, int64_t *n_matches)
 {
-    SeedShape sh;
-    if (!make_seed_shape(pattern, &sh)) { ctx->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
-    if (gs.nseq < 1) { ctx->err = "no genomes set"; return MAUVE_ERR_STATE; }
-    GenomeTab tab; int64_t total = 0;
-    int rc = build_tab(ctx, gs, sh.span, &tab, &total);
-    if (rc) return rc;
-    ctx->n_matches = 0; ctx->match_len.clear(); ctx->match_start.clear(); ctx->matches_pending = false;
-    ctx->dev_rec_n = -1;
-    if (n_matches) *n_matches = 0;
+    SeedShape sh; GenomeTab tab; int64_t total = 0;
+    if (int rc = seedpass_prologue(ctx, gs, pattern, nullptr, &sh, &tab, &total)) return rc;
+    reset_match_list(ctx, n_matches);
     if (total == 0 || hits.n == 0) return MAUVE_OK;
-    ctx->host_hits = &hits;
-    rc = SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, MAUVE_MODE_MEM, 0, extend, -1, nullptr, 0, n_matches, nullptr, nullptr);
-    ctx->host_hits = nullptr;
-    return rc;
+    SeedRequest rq;
+    rq.mode = MAUVE_MODE_MEM; rq.extend = extend; rq.hits = &hits; rq.n_matches = n_matches;
+    return seedpass_dispatch(ctx, gs, sh, tab, total, rq);
 }
 
 // SeedMatchEnumerator::FindMatches of sequence `seq` on the device; q carries the rule in and the CSR result out
 int seedpass_enumerate(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t pattern, EnumRequest &q)
 {
-    SeedShape sh;
-    if (!make_seed_shape(pattern, &sh)) { ctx->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
-    if (seq < 0 || seq >= gs.nseq) { ctx->err = "sequence index out of range"; return MAUVE_ERR_ARG; }
-    GenomeTab tab; int64_t total = 0;
-    int rc = build_tab(ctx, gs, sh.span, &tab, &total);
-    if (rc) return rc;
+    SeedShape sh; GenomeTab tab; int64_t total = 0;
+    if (int rc = seedpass_prologue(ctx, gs, pattern, &seq, &sh, &tab, &total)) return rc;
     q.n = 0; q.ns = 0;
     if (tab.nwin[seq] == 0) { if (q.start_off) q.start_off[0] = 0; return MAUVE_OK; }
-    ctx->enum_req = &q;
-    if (2 * sh.weight <= 32) rc = SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, nullptr, nullptr);
-    else rc = SEEDPASS_DISPATCH(uint64_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, nullptr, nullptr);
-    ctx->enum_req = nullptr;
-    return rc;
+    SeedRequest rq;
+    rq.mode = 0; rq.only_seq = seq; rq.enumerate = &q;
+    return seedpass_dispatch(ctx, gs, sh, tab, total, rq);
 }
 
 int seedpass_sorted_list(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t pattern, std::vector<uint64_t> *keys,
                          std::vector<uint32_t> *vals, int *weight)
 {
-    SeedShape sh;
-    if (!make_seed_shape(pattern, &sh)) { ctx->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
-    if (seq < 0 || seq >= gs.nseq) { ctx->err = "sequence index out of range"; return MAUVE_ERR_ARG; }
-    GenomeTab tab; int64_t total = 0;
-    int rc = build_tab(ctx, gs, sh.span, &tab, &total);
-    if (rc) return rc;
+    SeedShape sh; GenomeTab tab; int64_t total = 0;
+    if (int rc = seedpass_prologue(ctx, gs, pattern, &seq, &sh, &tab, &total)) return rc;
     *weight = sh.weight;
     keys->clear(); vals->clear();
     if (tab.nwin[seq] == 0) return MAUVE_OK;
-    if (2 * sh.weight <= 32) rc = SEEDPASS_DISPATCH(uint32_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, keys, vals);
-    else rc = SEEDPASS_DISPATCH(uint64_t, false, ctx, gs, sh, tab, total, 0, 0, 0, seq, nullptr, 0, nullptr, keys, vals);
-    if (rc) return rc;
+    SeedRequest rq;
+    rq.mode = 0; rq.only_seq = seq; rq.out_keys = keys; rq.out_vals = vals;
+    if (int rc = seedpass_dispatch(ctx, gs, sh, tab, total, rq)) return rc;
     // vals carry global window indices; make them local to the genome (a wide pass hands them out local already)
     if (!seedpass_wide(total))
         for (auto &v : *vals) v = ((v & 0x7fffffffu) - tab.gpos_off[seq]) | (v & 0x80000000u);
-    return MAUVE_OK;
-}
-
-// host copy of a match list the seed pass left on the device only (seedpass_impl with lazy_matches_ok)
-int seed_matches_to_host(mauve_ctx *ctx)
-{
-    if (!ctx->matches_pending) return MAUVE_OK;
-    const size_t nm = (size_t)ctx->n_matches; const int N = ctx->match_nseq;
-    const size_t rbytes = nm * (1 + (size_t)N) * 8;
-    HIPCHK(ctx, ctx->pin_seed.ensure(64 + rbytes));
-    char *pin = ctx->pin_seed.as<char>() + 64;
-    HIPCHK(ctx, hipMemcpyAsync(pin, ctx->sorted_rec.p, rbytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->match_len.resize(nm); ctx->match_start.resize(nm * N);
-    memcpy(ctx->match_len.data(), pin, nm * 8);
-    memcpy(ctx->match_start.data(), pin + nm * 8, nm * N * 8);
-    ctx->matches_pending = false;
     return MAUVE_OK;
 }
 
@@ -2517,31 +2206,14 @@ static_assert(RP_TILE == RS_TILE, "the multiplicity pass sorts with the histogra
 template <typename KeyT, typename ValT>
 static int rp_windows(mauve_ctx *c, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, uint32_t n)
 {
-    if (g_trace) fprintf(stderr, "[trace] multiplicity pass: %u windows, %s window index (%d-bit values)\n", n, sizeof(ValT) == 8 ? "wide" : "narrow", (int)sizeof(ValT) * 8);
-    HIPCHK(c, c->keysA.ensure((size_t)n * sizeof(KeyT)));
-    HIPCHK(c, c->keysB.ensure((size_t)n * sizeof(KeyT)));
-    HIPCHK(c, c->valsA.ensure((size_t)n * sizeof(ValT)));
-    HIPCHK(c, c->valsB.ensure((size_t)n * sizeof(ValT)));
-    const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
-    HIPCHK(c, c->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
+    if (seed_trace_on()) fprintf(stderr, "[trace] multiplicity pass: %u windows, %s window index (%d-bit values)\n", n, sizeof(ValT) == 8 ? "wide" : "narrow", (int)sizeof(ValT) * 8);
+    if (int rc = ensure_sort_buffers<KeyT, ValT>(c, n)) return rc;
     KeyT *keys = c->keysA.as<KeyT>(); ValT *vals = c->valsA.as<ValT>();
-    const uint64_t *packed = gs.buf->as<uint64_t>();
-    const uint64_t *vmask = gs.vmask ? gs.vmask->as<uint64_t>() : nullptr;      // ambiguous bases
-    const uint64_t *cmask = gs.cmask ? gs.cmask->as<uint64_t>() : nullptr;      // contig joins
-    {
-        KernelTimer t(c, MAUVE_K_EXTRACT, n);
-        if (sh.span <= 32 && sh.weight <= 15)
-            hipLaunchKernelGGL((seed_extract_all<KeyT, false, true, ValT>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
-                               c->hist.as<uint32_t>(), nblk, vmask, 0, cmask);
-        else
-            hipLaunchKernelGGL((seed_extract_all<KeyT, false, false, ValT>), dim3(nblk), dim3(256), 0, c->stream, packed, tab, sh, keys, vals, n, nullptr, 0u,
-                               c->hist.as<uint32_t>(), nblk, vmask, 0, cmask);
-    }
+    if (int rc = extract_all<KeyT, false, ValT>(c, gs, sh, tab, n, nullptr, 0u, 0, keys, vals)) return rc;
     HIPCHK(c, hipGetLastError());
     // the mer bits only: an invalid window's all-ones key has ones there that no canonical mer has (min(F, R) is never all T),
     // so the invalid windows end the list
-    int rc = sort_pairs<KeyT, ValT>(c, n, 2 * sh.weight, &keys, &vals, c->keysB.as<KeyT>(), c->valsB.as<ValT>(), true);
-    if (rc) return rc;
+    if (int rc = sort_pairs<KeyT, ValT>(c, n, 2 * sh.weight, &keys, &vals, c->keysB.as<KeyT>(), c->valsB.as<ValT>(), true)) return rc;
     hipLaunchKernelGGL((rp_count<KeyT, ValT>), dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->cus * 16)), dim3(256), 0, c->stream, keys, vals, n, tab,
                        c->rp_wcnt.as<uint8_t>());
     HIPCHK(c, hipGetLastError());
@@ -2550,14 +2222,10 @@ static int rp_windows(mauve_ctx *c, const GenomeSet &gs, const SeedShape &sh, co
 
 int repeat_multiplicity(mauve_ctx *c, uint64_t pattern)
 {
-    SeedShape sh;
-    if (!make_seed_shape(pattern, &sh)) { c->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
-    if (c->nseq < 1) { c->err = "no genomes set"; return MAUVE_ERR_STATE; }
-    if (c->rp_gen == c->genome_gen && c->rp_pat == pattern) return MAUVE_OK;
     const GenomeSet gs = main_genome_set(c);
-    GenomeTab tab; int64_t total = 0;
-    int rc = build_tab(c, gs, sh.span, &tab, &total);
-    if (rc) return rc;
+    SeedShape sh; GenomeTab tab; int64_t total = 0;
+    if (int rc = seedpass_prologue(c, gs, pattern, nullptr, &sh, &tab, &total)) return rc;
+    if (c->rp_gen == c->genome_gen && c->rp_pat == pattern) return MAUVE_OK;
     c->rp_gen = 0;                                             // (nothing valid while it is rebuilt)
     RpOut o; memset(&o, 0, sizeof o);
     c->rp_off.assign((size_t)c->nseq, 0);
@@ -2571,6 +2239,7 @@ int repeat_multiplicity(mauve_ctx *c, uint64_t pattern)
     HIPCHK(c, c->rp_wcnt.ensure((size_t)total + 16));
     if (total > 0) {
         const bool wide = seedpass_wide(total);
+        int rc;
         if (2 * sh.weight <= 32) rc = wide ? rp_windows<uint32_t, uint64_t>(c, gs, sh, tab, (uint32_t)total) : rp_windows<uint32_t, uint32_t>(c, gs, sh, tab, (uint32_t)total);
         else rc = wide ? rp_windows<uint64_t, uint64_t>(c, gs, sh, tab, (uint32_t)total) : rp_windows<uint64_t, uint32_t>(c, gs, sh, tab, (uint32_t)total);
         if (rc) return rc;
