@@ -393,6 +393,39 @@ int mauve_apply_homology_alignment(mauve_ctx *ctx, int nseq, int64_t n_iv, const
                                    int64_t *n_moved);
 int mauve_backbone_fetch(mauve_ctx *ctx, int64_t *seg_iv, int64_t *seg_col, int64_t *seg_len, uint32_t *seg_mask,
                          int64_t *seg_left, int64_t *seg_right, int64_t *islands);
+/* ---- coordinate translation through the alignment: Interval::GetColumn as coordinateTranslate uses it (coordinateTranslate.cpp:36-46)
+        and CompactGappedAlignment::SeqPosToColumn (getOrthologList.cpp:219-220, bbBreakOnGenes.cpp:154-155, randomGeneSample.cpp:139-140,
+        scoreProcrastAlignment.cpp:293-303), batched on a rank/select index over the columns.  Frozen form DESIGN.md S14: genome g is
+        present in interval i iff left[i,g] != 0; its residue with ordinal k in column order sits at left + k, at right - k on the
+        reverse strand, and is reported signed (negative = reverse strand).
+        Index: mauve_coord_index takes the alignment the context holds (MAUVE_ERR_STATE without one), mauve_coord_index_alignment the
+        caller's, in the arrays of mauve_align_fetch; the columns must be consistent with the interval ends (as for
+        mauve_backbone_alignment) and every base of a genome may lie in at most one interval, else MAUVE_ERR_ARG (the text names the
+        two intervals).  The index is a snapshot with device buffers of its own: later seed passes, alignments and genome uploads
+        leave it valid, the next index call replaces it, the context's end frees it.  After mauve_apply_homology it still describes
+        the columns it was built from until it is built again.  mauve_coord_index_size tells what the index in force was built from
+        (genomes, intervals, columns: the answer arrays are sized by its nseq); any pointer may be NULL.
+        Queries (MAUVE_ERR_STATE without an index; n = 0 is MAUVE_OK) are host arrays, page-locked ones (mauve_host_alloc) are copied
+        directly; any output pointer may be NULL.
+        mauve_column_positions: for (iv[q], col[q]) pos[q*nseq + g] = 0 for an absent genome, the signed position of the residue in
+          the column where bit g is set (then bit g of defined[q] too); where g is gapped 0, or with nearest != 0 the residue before
+          the column, else the first one after it (the defined bit stays clear).
+        mauve_seqpos_to_column: for (seq[q], pos[q]), pos 1-based and unsigned, the interval that covers the base and the column in it
+          that holds it; (-1, -1) where no interval does (add_unaligned = 0 leaves bases out: a legal question).
+        mauve_translate_positions: the two in turn -- nseq signed positions (entry seq[q] is +-pos[q]), the defined mask, the interval;
+          zeros, 0 and -1 where nothing covers the base.
+        An interval id outside [0, n_iv), a column outside its interval, seq outside [0, nseq) or pos < 1 makes the whole call return
+        MAUVE_ERR_ARG. ---- */
+int mauve_coord_index(mauve_ctx *ctx);
+int mauve_coord_index_alignment(mauve_ctx *ctx, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right,
+                                const int8_t *reverse, const int64_t *col_off, const uint32_t *cols);
+int mauve_coord_index_size(mauve_ctx *ctx, int *nseq, int64_t *n_iv, int64_t *n_cols);
+int mauve_column_positions(mauve_ctx *ctx, int64_t n, const int64_t *iv, const int64_t *col, int nearest,
+                           int64_t *pos /* n*nseq */, uint32_t *defined /* n */);
+int mauve_seqpos_to_column(mauve_ctx *ctx, int64_t n, const int32_t *seq, const int64_t *pos,
+                           int64_t *iv /* n */, int64_t *col /* n */);
+int mauve_translate_positions(mauve_ctx *ctx, int64_t n, const int32_t *seq, const int64_t *pos, int nearest,
+                              int64_t *out /* n*nseq */, uint32_t *defined /* n */, int64_t *iv /* n */);
 /* IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760; format mfa2xmfa.cpp:64-115).
    Two-phase: buf == NULL returns the needed size (including NUL) in *len. */
 int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_t *len);

@@ -32,6 +32,7 @@ EXPORTS = [
     "mauve_backbone", "mauve_backbone_alignment", "mauve_backbone_fetch", "mauve_merge_matches",
     "mauve_write_xmfa", "mauve_profile_enable", "mauve_profile_reset", "mauve_profile_get", "mauve_last_stage_times",
     "mauve_set_repeat_penalty", "mauve_seed_multiplicity", "mauve_match_sp_scores_repeat",
+    "mauve_coord_index", "mauve_coord_index_alignment", "mauve_coord_index_size", "mauve_column_positions", "mauve_seqpos_to_column", "mauve_translate_positions",
 ]
 
 
@@ -740,6 +741,80 @@ class Context:
                                                         _p(cols if len(cols) else np.zeros(1, np.uint32), C.c_uint32), C.byref(h), _p(noff, C.c_int64), _p(ncols, C.c_uint32),
                                                         C.byref(moved)), "mauve_apply_homology_alignment")
         return noff, ncols[:noff[-1]].copy(), int(moved.value)
+
+    # ---- coordinate translation through the alignment ----
+    def coord_index(self):
+        """mauve_coord_index: the rank/select index of the alignment this context holds (a snapshot: it outlives later passes)"""
+        self._chk(self.L.mauve_coord_index(self.h), "mauve_coord_index")
+
+    def coord_index_alignment(self, left, right, reverse, col_off, cols):
+        """... of the caller's alignment (mauve_coord_index_alignment): left/right/reverse [n_iv, nseq], col_off [n_iv+1], cols."""
+        left = np.ascontiguousarray(left, np.int64)
+        right = np.ascontiguousarray(right, np.int64)
+        reverse = np.ascontiguousarray(reverse, np.int8)
+        col_off = np.ascontiguousarray(col_off, np.int64)
+        cols = np.ascontiguousarray(cols, np.uint32)
+        n_iv, N = left.shape
+        self._chk(self.L.mauve_coord_index_alignment(self.h, N, C.c_int64(n_iv), _p(left, C.c_int64), _p(right, C.c_int64), _p(reverse, C.c_int8),
+                                                     _p(col_off, C.c_int64), _p(cols if len(cols) else np.zeros(1, np.uint32), C.c_uint32)),
+                  "mauve_coord_index_alignment")
+
+    def coord_index_size(self):
+        """mauve_coord_index_size: (nseq, n_iv, n_cols) the index in force was built from; the answer arrays are sized by its nseq"""
+        n, k, c = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.mauve_coord_index_size(self.h, C.byref(n), C.byref(k), C.byref(c)), "mauve_coord_index_size")
+        return n.value, k.value, c.value
+
+    @staticmethod
+    def _co_out(out, k, shape, dtype):
+        """the k-th result array of a coordinate query: the caller's (out=..., e.g. from pinned_empty) or a fresh one"""
+        if out is None:
+            return np.zeros(shape, dtype)
+        a = out[k]
+        if a.dtype != np.dtype(dtype) or a.shape != tuple(shape) or not a.flags.c_contiguous:
+            raise ValueError("coordinate query: out[%d] must be a contiguous %s array of shape %s" % (k, np.dtype(dtype).name, tuple(shape)))
+        return a
+
+    def column_positions(self, iv, col, nearest=False, out=None):
+        """mauve_column_positions: (interval, column) -> (pos[n, nseq] signed, defined[n] genome masks).  Arrays from pinned_empty (queries
+        and out=(pos, defined)) are copied without staging."""
+        iv = np.ascontiguousarray(iv, np.int64)
+        col = np.ascontiguousarray(col, np.int64)
+        n, N = len(iv), self.coord_index_size()[0]
+        if len(col) != n:
+            raise ValueError("column_positions: iv and col differ in length")
+        pos = self._co_out(out, 0, (n, N), np.int64)
+        dfn = self._co_out(out, 1, (n,), np.uint32)
+        self._chk(self.L.mauve_column_positions(self.h, C.c_int64(n), _p(iv, C.c_int64), _p(col, C.c_int64), int(bool(nearest)),
+                                                _p(pos, C.c_int64), _p(dfn, C.c_uint32)), "mauve_column_positions")
+        return pos, dfn
+
+    def seqpos_to_column(self, seq, pos, out=None):
+        """mauve_seqpos_to_column: (genome, 1-based position) -> (interval, column in it); (-1, -1) where no interval covers the base"""
+        seq = np.ascontiguousarray(seq, np.int32)
+        pos = np.ascontiguousarray(pos, np.int64)
+        n = len(seq)
+        if len(pos) != n:
+            raise ValueError("seqpos_to_column: seq and pos differ in length")
+        iv = self._co_out(out, 0, (n,), np.int64)
+        col = self._co_out(out, 1, (n,), np.int64)
+        self._chk(self.L.mauve_seqpos_to_column(self.h, C.c_int64(n), _p(seq, C.c_int32), _p(pos, C.c_int64), _p(iv, C.c_int64), _p(col, C.c_int64)),
+                  "mauve_seqpos_to_column")
+        return iv, col
+
+    def translate_positions(self, seq, pos, nearest=False, out=None):
+        """mauve_translate_positions: (genome, position) -> (out[n, nseq] signed positions in every genome, defined[n], interval[n])"""
+        seq = np.ascontiguousarray(seq, np.int32)
+        pos = np.ascontiguousarray(pos, np.int64)
+        n, N = len(seq), self.coord_index_size()[0]
+        if len(pos) != n:
+            raise ValueError("translate_positions: seq and pos differ in length")
+        res = self._co_out(out, 0, (n, N), np.int64)
+        dfn = self._co_out(out, 1, (n,), np.uint32)
+        iv = self._co_out(out, 2, (n,), np.int64)
+        self._chk(self.L.mauve_translate_positions(self.h, C.c_int64(n), _p(seq, C.c_int32), _p(pos, C.c_int64), int(bool(nearest)),
+                                                   _p(res, C.c_int64), _p(dfn, C.c_uint32), _p(iv, C.c_int64)), "mauve_translate_positions")
+        return res, dfn, iv
 
     def stage_times(self):
         t = StageTimes()

@@ -757,7 +757,7 @@ int backbone_run(mauve_ctx *c, int N, int64_t n_iv, const int64_t *left, const i
 // A caller's alignment (the _alignment entry points; the mirror hands over iv.Columns() of user Intervals): every genome's residue count
 // in an interval's columns must be what its ends say -- right - left + 1, none for an absent genome -- and no column may carry a bit at or
 // above nseq.  The homology pass turns these counts into base addresses (hom_column), so an inconsistent array would read outside the genomes.
-static int check_columns(mauve_ctx *c, const char *who, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int64_t *col_off, const uint32_t *d_cols)
+int check_columns(mauve_ctx *c, const char *who, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int64_t *col_off, const uint32_t *d_cols)
 {
     const int64_t n_cols = col_off[n_iv];
     auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };

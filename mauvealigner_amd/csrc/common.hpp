@@ -212,6 +212,7 @@ struct AlignState {
     }
 };
 
+struct CoordDev;                         // coord_dev.hip
 struct mauve_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -281,6 +282,11 @@ struct mauve_ctx {
     PinnedBuf pin_bb;                    // rank queries and their answers
     DevBuf bb_cols, bb_work, bb_query;   // a caller's / a host-assembled column array; interval table + records; rank queries
     size_t bb_rec_cap = 0;
+    // coordinate translation (coord_dev.hip): the rank/select index is a snapshot with buffers of its own -- it reads neither the
+    // genomes nor res_cols once built, so later passes leave it alone; replaced by the next mauve_coord_index*, freed with the context
+    struct CoordIndex { bool valid = false; int N = 0; int64_t n_iv = 0, n_cols = 0; struct ::CoordDev *dev = nullptr; } co;     // dev: the kernels' view of the index, owned by coord_dev.hip (coord_index_release)
+    DevBuf co_index, co_q;               // the index; one chunk of queries and their answers
+    PinnedBuf pin_coord;                 // ... on their way from / to pageable caller arrays, and the error flag
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them
     DevBuf rec_genomes, rec_seg;         // recursive anchoring: gap sub-sequences + segment table
@@ -502,6 +508,11 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na, const int32_t *h_len,
                         int64_t max_gapped_len, const mauve_scoring *scoring, int32_t *gapcode, int64_t *n_dp_out, int64_t *code_total_out,
                         PinnedBuf *dcols, std::vector<int64_t> &dcol_off, std::vector<int64_t> &dscore, int64_t *cells, int stay = 0);
 int assemble_device(mauve_ctx *c, int64_t na, int64_t cells, mauve_align_sizes *sizes, bool host_chains = false);
+// a caller's column array against its interval table: right - left + 1 residues of every present genome, none of an absent one, no bit at
+// or above nseq -- else MAUVE_ERR_ARG with `who` in the text (backbone_dev.hip; the _alignment entry points of the backbone, the homology
+// pass and the coordinate index)
+int check_columns(mauve_ctx *c, const char *who, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int64_t *col_off, const uint32_t *d_cols);
+void coord_index_release(mauve_ctx *c);  // coord_dev.hip: the host side of the coordinate index (its device buffers go with the context's DevBufs)
 int materialize_result(mauve_ctx *c);
 int materialize_tables(mauve_ctx *c);
 int fetch_columns(mauve_ctx *c, uint32_t *dst);
