@@ -49,6 +49,7 @@ public:
     }
 
     uint SeqCount() const { return n_; }
+    HipContext &context() const { return *hc_; }          // the context the index lives in (AlignmentExtractor.h works on it)
 
     // Interval::GetColumn for a batch: query q asks for column cols[q] of interval blocks[q].  pos[q * SeqCount() + g] is the signed
     // position of sequence g's residue there (negative = reverse strand), 0 where g is absent or gapped; defined[q]: bit g set = a

@@ -426,6 +426,32 @@ int mauve_seqpos_to_column(mauve_ctx *ctx, int64_t n, const int32_t *seq, const 
                            int64_t *iv /* n */, int64_t *col /* n */);
 int mauve_translate_positions(mauve_ctx *ctx, int64_t n, const int32_t *seq, const int64_t *pos, int nearest,
                               int64_t *out /* n*nseq */, uint32_t *defined /* n */, int64_t *iv /* n */);
+/* ---- alignment columns as a base matrix: the GetAlignment loops of stripGapColumns (stripGapColumns.cpp:32-64), projectAndStrip
+        (projectAndStrip.cpp:75-101), stripSubsetLCBs (stripSubsetLCBs.cpp:125-142), createBackboneMFA (createBackboneMFA.cpp:28-37) and
+        alignmentProjector (alignmentProjector.cpp:58-77) -- choose columns, choose rows, write the letters -- on the coordinate index in
+        force and the resident genomes.  Frozen form DESIGN.md S15.  The cell of a column and a genome is '-' where the genome is absent
+        from the interval or gapped in the column, else the base at the signed position of S14 ("ACGT", complemented on the reverse
+        strand, N where the ambiguity bitmap is set): the letter mauve_write_xmfa prints there.
+        Request: keep[0..n_keep) distinct genome ids = the rows, in that order (the projection list); require: genome mask, a column is
+        selected only if all of them have a residue (require = the keep set: the core columns); drop_empty: ... and only if a kept genome
+        has one; polymorphic: ... and only if the kept genomes' ACGT cells show two different letters (N and '-' do not count).
+        Ranges (range_iv, range_col, range_len)[n_range]: the form of seg_iv / seg_col / seg_len of mauve_backbone_fetch; range_iv == NULL:
+        one range per interval, all its columns (n_range is then not read).  Selected columns come in range order, ascending inside a
+        range; overlapping ranges repeat columns; empty ranges and n_range = 0 are legal.
+        mauve_extract_select makes the selection (*n_sel columns) and keeps it in the context; mauve_extract_fetch writes
+        rows[k*row_stride + j] = the cell of keep[k] and selected column j (row_stride >= n_sel; the bytes between n_sel and row_stride
+        are not written), sel_iv / sel_col [n_sel] in the form mauve_column_positions takes, range_off [n_range+1] = every range's slice
+        of the selection.  Any output pointer may be NULL; page-locked ones (mauve_host_alloc) are copied directly.
+        MAUVE_ERR_ARG: an interval id outside [0, n_iv), col < 0, len < 0, col + len past the interval, n_keep outside [1, nseq], a keep
+        id outside [0, nseq) or repeated, a require bit at or above nseq, an interval of the index that ends beyond the resident genome.
+        MAUVE_ERR_STATE: no index, an index of another nseq than the context's, an index built before the last mauve_set_genomes*;
+        a fetch without a selection -- a later mauve_coord_index*, mauve_set_genomes* or select ends the one before. ---- */
+typedef struct { int32_t n_keep; int32_t keep[MAUVE_MAX_SEQ]; uint32_t require; int32_t drop_empty; int32_t polymorphic; } mauve_extract_params;
+void mauve_default_extract_params(int nseq, mauve_extract_params *p);        /* every genome in order, no condition */
+int mauve_extract_select(mauve_ctx *ctx, const mauve_extract_params *p, int64_t n_range, const int64_t *range_iv,
+                         const int64_t *range_col, const int64_t *range_len, int64_t *n_sel);
+int mauve_extract_fetch(mauve_ctx *ctx, char *rows, int64_t row_stride,       /* rows[k*row_stride + j], row_stride >= n_sel */
+                        int64_t *sel_iv, int64_t *sel_col, int64_t *range_off); /* [n_sel], [n_sel], [n_range+1]; any may be NULL */
 /* IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760; format mfa2xmfa.cpp:64-115).
    Two-phase: buf == NULL returns the needed size (including NUL) in *len. */
 int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_t *len);

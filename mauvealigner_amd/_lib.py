@@ -33,6 +33,7 @@ EXPORTS = [
     "mauve_write_xmfa", "mauve_profile_enable", "mauve_profile_reset", "mauve_profile_get", "mauve_last_stage_times",
     "mauve_set_repeat_penalty", "mauve_seed_multiplicity", "mauve_match_sp_scores_repeat",
     "mauve_coord_index", "mauve_coord_index_alignment", "mauve_coord_index_size", "mauve_column_positions", "mauve_seqpos_to_column", "mauve_translate_positions",
+    "mauve_default_extract_params", "mauve_extract_select", "mauve_extract_fetch",
 ]
 
 
@@ -53,6 +54,10 @@ class Params(C.Structure):
 
 class HmmParams(C.Structure):
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32), ("go_homologous", C.c_int32), ("go_unrelated", C.c_int32)]
+
+
+class ExtractParams(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("keep", C.c_int32 * 32), ("require", C.c_uint32), ("drop_empty", C.c_int32), ("polymorphic", C.c_int32)]
 
 
 class AlignSizes(C.Structure):
@@ -815,6 +820,65 @@ class Context:
         self._chk(self.L.mauve_translate_positions(self.h, C.c_int64(n), _p(seq, C.c_int32), _p(pos, C.c_int64), int(bool(nearest)),
                                                    _p(res, C.c_int64), _p(dfn, C.c_uint32), _p(iv, C.c_int64)), "mauve_translate_positions")
         return res, dfn, iv
+
+    # ---- alignment columns as a base matrix ----
+    def extract_select(self, keep=None, require=0, drop_empty=False, polymorphic=False, ranges=None):
+        """mauve_extract_select: choose the columns (ranges = (iv, col, len) arrays as backbone()'s seg_iv / seg_col / seg_len, None = every
+        interval whole) that satisfy the request, and the rows (keep, None = every genome in order).  -> n_sel"""
+        p = ExtractParams()
+        self.L.mauve_default_extract_params.restype = None
+        self.L.mauve_default_extract_params(C.c_int(self.nseq), C.byref(p))
+        if keep is not None:
+            keep = [int(g) for g in keep]
+            if len(keep) > 32:
+                raise ValueError("extract: at most 32 rows")
+            p.n_keep = len(keep)
+            for k, g in enumerate(keep):
+                p.keep[k] = g
+        p.require, p.drop_empty, p.polymorphic = int(require), int(bool(drop_empty)), int(bool(polymorphic))
+        n = C.c_int64(0)
+        if ranges is None:
+            rc = self.L.mauve_extract_select(self.h, C.byref(p), C.c_int64(0), None, None, None, C.byref(n))
+        else:
+            iv, col, ln = (np.ascontiguousarray(x, np.int64) for x in ranges)
+            if not (len(iv) == len(col) == len(ln)):
+                raise ValueError("extract: the range arrays differ in length")
+            z = np.zeros(1, np.int64)
+            rc = self.L.mauve_extract_select(self.h, C.byref(p), C.c_int64(len(iv)), _p(iv if len(iv) else z, C.c_int64), _p(col if len(iv) else z, C.c_int64),
+                                             _p(ln if len(iv) else z, C.c_int64), C.byref(n))
+        self._chk(rc, "mauve_extract_select")
+        self._ex_shape = (p.n_keep, n.value, self.coord_index_size()[1] if ranges is None else len(iv))
+        return n.value
+
+    def extract_fetch(self, out=None, lists=True):
+        """mauve_extract_fetch of the selection in force -> (rows uint8 [n_keep, n_sel], sel_iv, sel_col, range_off); out = the four arrays
+        (e.g. from pinned_empty: copied without staging), rows may be a view of a wider matrix (its row stride is passed on);
+        lists=False: the matrix alone (the three lists are not copied: None)"""
+        nk, ns, nr = self._ex_shape
+        if out is None:
+            rows = np.zeros((nk, ns), np.uint8)
+        else:
+            rows = out[0]
+            if rows.dtype != np.uint8 or rows.shape != (nk, ns) or (ns > 1 and rows.strides[1] != 1) or (nk > 1 and rows.strides[0] < ns):
+                raise ValueError("extract: out[0] must be a uint8 array of shape %s with contiguous rows" % ((nk, ns),))
+        stride = rows.strides[0] if nk > 1 and ns > 0 else max(ns, 1)
+        if not lists:
+            self._chk(self.L.mauve_extract_fetch(self.h, C.c_void_p(rows.ctypes.data), C.c_int64(stride), None, None, None), "mauve_extract_fetch")
+            return rows, None, None, None
+        siv = self._co_out(out, 1, (ns,), np.int64)
+        scol = self._co_out(out, 2, (ns,), np.int64)
+        roff = self._co_out(out, 3, (nr + 1,), np.int64)
+        self._chk(self.L.mauve_extract_fetch(self.h, C.c_void_p(rows.ctypes.data), C.c_int64(stride), _p(siv, C.c_int64), _p(scol, C.c_int64), _p(roff, C.c_int64)),
+                  "mauve_extract_fetch")
+        return rows, siv, scol, roff
+
+    def extract_columns(self, keep=None, require=0, drop_empty=False, polymorphic=False, ranges=None, out=None):
+        """select + fetch: the letters of the chosen columns in the chosen genomes, row-major per genome (the projection / core-column /
+        SNP matrix of stripGapColumns, projectAndStrip, alignmentProjector).  require: genome mask (int) or a list of genome ids."""
+        if not isinstance(require, (int, np.integer)):
+            require = sum(1 << int(g) for g in require)
+        self.extract_select(keep, require, drop_empty, polymorphic, ranges)
+        return self.extract_fetch(out)
 
     def stage_times(self):
         t = StageTimes()

@@ -284,9 +284,18 @@ struct mauve_ctx {
     size_t bb_rec_cap = 0;
     // coordinate translation (coord_dev.hip): the rank/select index is a snapshot with buffers of its own -- it reads neither the
     // genomes nor res_cols once built, so later passes leave it alone; replaced by the next mauve_coord_index*, freed with the context
-    struct CoordIndex { bool valid = false; int N = 0; int64_t n_iv = 0, n_cols = 0; struct ::CoordDev *dev = nullptr; } co;     // dev: the kernels' view of the index, owned by coord_dev.hip (coord_index_release)
+    struct CoordIndex { bool valid = false; int N = 0; int64_t n_iv = 0, n_cols = 0; uint64_t genome_gen = 0; struct ::CoordDev *dev = nullptr; } co;     // dev: the kernels' view of the index, owned by coord_dev.hip (coord_index_release)
     DevBuf co_index, co_q;               // the index; one chunk of queries and their answers
     PinnedBuf pin_coord;                 // ... on their way from / to pageable caller arrays, and the error flag
+    // column extraction (extract_dev.hip): the selection a fetch turns into letters -- the selected columns as (interval, column)
+    // in ex_sel, with the request; it belongs to the index and the genomes it was made on (an index call clears `valid`, genome_gen tells an upload)
+    struct ExtractSel {
+        bool valid = false; uint64_t genome_gen = 0;
+        int64_t n_sel = 0, n_range = 0;
+        int n_keep = 0; int32_t keep[MAUVE_MAX_SEQ] = {0};
+    } ex;
+    DevBuf ex_work, ex_bits, ex_sel, ex_mat;   // ranges and their scan; flag words and their scan; sel_iv | sel_col | range_off; the matrix (padded pitch)
+    PinnedBuf pin_ex;                    // ranges on their way in, counts and the error flag coming back, staging of pageable outputs
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them
     DevBuf rec_genomes, rec_seg;         // recursive anchoring: gap sub-sequences + segment table

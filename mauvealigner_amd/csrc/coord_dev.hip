@@ -14,37 +14,18 @@
 //   coord_finish   ranks from the scanned block counts (dev_scan.hpp), the samples;  coord_iv_rows  the interval rows
 //   coord_positions / coord_select   the queries: a thread per (query, genome) resp. per query; every index they form is checked first
 #include "common.hpp"
+#include "coord_index.hpp"
 #include "dev_scan.hpp"
 #include <algorithm>
 #include <cstring>
 
-constexpr int CO_WORDS = 7;                       // 64-column words per block record (with the rank: 64 bytes)
-constexpr int CO_BLOCK = CO_WORDS * 64;           // columns per block
 constexpr int CO_SAMPLE = 512;                    // residues between two samples; more than a block holds, so a block carries at most one
-constexpr uint32_t CO_BAD_ARG = 1u, CO_BAD_INDEX = 2u;      // the error flag: a query out of range; columns that disagree with the interval ends
-
-struct alignas(64) CoordRec { int64_t rank; uint64_t w[CO_WORDS]; };
-struct alignas(32) CoordIv { int64_t left, right, base, col0_rev; };      // base: rank at the interval's first column; col0_rev: that column << 1 | reverse
-
-// the index as the kernels see it (by value); the context keeps the host copy (mauve_ctx::CoordIndex::dev, coord_index_release)
-struct CoordDev {
-    const CoordRec *rec;                          // [(nb1) * N], block-major
-    const CoordIv *ivt;                           // [n_iv * N]
-    const int64_t *col_off;                       // [n_iv + 1]
-    const int64_t *tleft, *tright, *tiv;          // genome tables, genome after genome (tab_off)
-    const uint32_t *samp;                         // samples, genome after genome (samp_off)
-    int64_t n_iv, nb1;                            // nb1: blocks, the one that holds column n_cols included
-    int N;
-    uint32_t tab_off[MAUVE_MAX_SEQ + 1], samp_off[MAUVE_MAX_SEQ + 1];
-};
 
 void coord_index_release(mauve_ctx *c) { delete c->co.dev; c->co.dev = nullptr; c->co.valid = false; }
 
 namespace {
 
 struct CoordTotals { int64_t v[MAUVE_MAX_SEQ]; };  // residues of every genome by the interval ends
-
-__device__ __forceinline__ uint64_t co_below(int p) { return p >= 64 ? ~0ull : (1ull << p) - 1; }
 
 // position of the k-th (0-based) set bit of x; x holds more than k
 __device__ __forceinline__ int co_select64(uint64_t x, int k)
@@ -56,21 +37,6 @@ __device__ __forceinline__ int co_select64(uint64_t x, int k)
         if (k >= c) { k -= c; pos += s; }
     }
     return pos;
-}
-
-// residues in front of column `off` of the record's block (whole array); *present: the bit of that column
-__device__ __forceinline__ int64_t co_rank(const CoordRec &r, int off, bool *present)
-{
-    const int wi = off >> 6, bit = off & 63;
-    int64_t n = r.rank; bool p = false;
-#pragma unroll
-    for (int k = 0; k < CO_WORDS; k++) {
-        const uint64_t m = k < wi ? ~0ull : (k == wi ? co_below(bit) : 0ull);
-        n += __popcll(r.w[k] & m);
-        if (k == wi) p = r.w[k] >> bit & 1;
-    }
-    *present = p;
-    return n;
 }
 
 __global__ void __launch_bounds__(256) coord_build(const uint32_t *__restrict__ cols, int64_t n_cols, int N, int64_t nb1, CoordRec *__restrict__ rec, uint32_t *__restrict__ cnt)
@@ -311,7 +277,7 @@ int coord_build_index(mauve_ctx *c, int N, int64_t n_iv, const int64_t *left, co
     if (flag) { c->err = "coord_index: the columns do not hold the residues the interval ends announce"; return MAUVE_ERR_ARG; }
     if (!X.dev) X.dev = new CoordDev;
     *X.dev = D;
-    X.N = N; X.n_iv = n_iv; X.n_cols = n_cols; X.valid = true;
+    X.N = N; X.n_iv = n_iv; X.n_cols = n_cols; X.genome_gen = c->genome_gen; X.valid = true;
     return MAUVE_OK;
 }
 
@@ -403,7 +369,7 @@ extern "C" {
 int mauve_coord_index(mauve_ctx *c)
 {
     if (!c) return MAUVE_ERR_ARG;
-    c->co.valid = false;
+    c->co.valid = false; c->ex.valid = false;               // (a selection, DESIGN.md S15, belongs to the index it was made on)
     AlignResult &R = c->res;
     if (R.stale) { c->err = "coord_index: the genomes were replaced after this alignment was made"; return MAUVE_ERR_STATE; }
     const int64_t n_iv = R.sz.n_iv;
@@ -425,7 +391,7 @@ int mauve_coord_index(mauve_ctx *c)
 int mauve_coord_index_alignment(mauve_ctx *c, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)
 {
     if (!c) return MAUVE_ERR_ARG;
-    c->co.valid = false;
+    c->co.valid = false; c->ex.valid = false;               // (a selection, DESIGN.md S15, belongs to the index it was made on)
     if (nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !col_off || (n_iv && (!left || !right || !reverse)) || (n_iv && col_off[n_iv] > 0 && !cols)) {
         c->err = "coord_index: bad arguments"; return MAUVE_ERR_ARG;
     }
