@@ -41,6 +41,16 @@ struct DpMeta {
 
 struct DpScoring { int32_t go, ge; int32_t s[4][4]; };
 
+// what every DP kernel takes behind its list: the bases, the per-interval records, both profile buffers, traceback, parked rows, reversed ops, scores.
+// The kernels take them as __restrict__ pointer parameters and put them into this record on entry; the interval functions take the record.  (As
+// the kernel argument itself the record would carry no __restrict__: dp_step_wide then needs 17 more registers and loses a wave per SIMD.)
+struct DpBufs {
+    const uint8_t *codes; const int64_t *seq_off; DpMeta *meta;
+    uint32_t *cntA, *maskA, *cntB, *maskB;
+    uint8_t *tb; const int64_t *tb_off; int32_t *rows; const int64_t *rows_off; uint8_t *ops;
+    DpScoring sc;
+};
+
 // ---- banded steps: intervals whose longest sequence exceeds max_gapped_len run every progressive step
 // inside the band |j - c(i)| <= W around the scaled diagonal c(i) = floor(i * n / m), W = 128 + |n - m| + (m + n) / 64:
 // cells outside are minus infinity.  Only the band is swept and only its traceback is stored: stripe s covers the
@@ -113,18 +123,163 @@ __device__ __forceinline__ void max3(int32_t a, int32_t b, int32_t c, int32_t &b
     if (c > best) { best = c; p = 2; }
 }
 
-// One 64-row stripe of a DP step as a wave sees it: the lane's row constants, the rolling cell state and the two
-// 64-column chunks (current, next) of what lane 0 consumes -- the sequence bases and the boundary row above the
-// stripe.  Chunks are fetched by the whole wave one round (64 steps) ahead, from clamped addresses so the load is
-// unconditional and its wait lands a round later, and handed to lane 0 with v_readlane.
-struct DpStripe {
-    int32_t s, i, m, n, steps, gyo, gye, gxo, gxe, sub0, sub1, sub2, sub3;
-    int32_t j0, blo, bhi, plo, phi;          // first column of the stripe's sweep; this row's band; the band of the row above the stripe
-    bool active, park;
-    const uint8_t *seq; const int32_t *rin; int32_t *rout; uint8_t *tbs;
-    int32_t Mc, Xc, Yc, Md, Xd, Yd;
-    uint32_t bcur, sq_cur, sq_nxt;
+// ---- the frame of a progressive step: what every schedule below does around its sweep --------------------------------------
+// An interval function goes over the interval's sequences with a DpMeta of its own: the first non-empty one becomes the profile
+// (dp_first_profile), every later one is a step -- pointers (dp_step_ptrs), the schedule's sweep, the state at (m, n)
+// (dp_pick_state), the schedule's walk, the new profile (dp_rebuild), the record (dp_step_done).  The fences and barriers between
+// these parts are the caller's: they depend on who takes part (a sub-wave group, a wave, a workgroup, a cluster).
+struct DpStep { uint32_t *Pc, *Pm, *Qc, *Qm; };          // the current profile (counts, masks) and the one the step builds
+
+__device__ __forceinline__ DpMeta dp_meta_zero() { DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0; return mt; }
+
+// the two profile buffers change roles with every step (mt.cur); base: the interval's first column in them
+__device__ __forceinline__ DpStep dp_step_ptrs(const DpBufs &B, const DpMeta &mt, int64_t base)
+{
+    DpStep P;
+    P.Pc = (mt.cur ? B.cntB : B.cntA) + base; P.Pm = (mt.cur ? B.maskB : B.maskA) + base;
+    P.Qc = (mt.cur ? B.cntA : B.cntB) + base; P.Qm = (mt.cur ? B.maskA : B.maskB) + base;
+    return P;
+}
+
+// the first non-empty sequence becomes the profile: STRIDE threads take part, this one is number idx of them
+template <int STRIDE>
+__device__ __forceinline__ void dp_first_profile(const DpStep &P, const uint8_t *seq, int32_t n, int g, int idx)
+{
+    for (int32_t c = idx; c < n; c += STRIDE) { P.Pc[c] = 1u << (8 * seq[c]); P.Pm[c] = 1u << g; }
+}
+
+// the state the traceback starts in at (m, n): the first of M, X, Y that attains the maximum; returns the maximum (the step's score)
+__device__ __forceinline__ int32_t dp_pick_state(int32_t fM, int32_t fX, int32_t fY, int &state)
+{
+    int32_t best = fM; state = 0;
+    if (fX > best) { best = fX; state = 1; }
+    if (fY > best) { best = fY; state = 2; }
+    return best;
+}
+
+// the new profile in forward order from the len reversed ops at opr: ballot prefix counts give each column its sources.  By W waves
+// together: every wave keeps the running source counts, chunk k is written by wave k mod W.
+template <int W>
+__device__ __forceinline__ void dp_rebuild(const DpStep &P, const uint8_t *opr, int32_t len, const uint8_t *seq, int g, int lane, int wv)
+{
+    const uint64_t lt = lane ? (~0ULL >> (64 - lane)) : 0ULL;
+    int32_t carry_p = 0, carry_s = 0;
+    for (int32_t c0i = 0, k = 0; c0i < len; c0i += 64, k++) {
+        const int32_t c = c0i + lane;
+        const bool ok = c < len;
+        const uint32_t op = ok ? opr[len - 1 - c] : 0u;
+        const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
+        if (ok && (W == 1 || (k % W) == wv)) {
+            const int32_t pi = carry_p + (int32_t)__popcll(bp & lt), sj = carry_s + (int32_t)__popcll(bs & lt);
+            uint32_t cv = 0, mv = 0;
+            if (op & 1) { cv = P.Pc[pi]; mv = P.Pm[pi]; }
+            if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
+            P.Qc[c] = cv; P.Qm[c] = mv;
+        }
+        carry_p += (int32_t)__popcll(bp); carry_s += (int32_t)__popcll(bs);
+    }
+}
+
+__device__ __forceinline__ void dp_step_done(DpMeta &mt, int64_t cells, int32_t best, int32_t len)
+{
+    mt.cells += cells; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1;
+}
+
+// What lane 0 of a stripe's systolic sweep consumes, as the wave feeds it: the sequence bases and the boundary row above the
+// stripe, in two 64-column chunks (current, next).  Chunks are fetched by the whole wave one round (64 steps) ahead, from clamped
+// addresses so the load is unconditional and its wait lands a round later, and handed to lane 0 with v_readlane.
+struct DpFeed {
+    const uint8_t *seq; const int32_t *rin;
+    int32_t n, s, gyo, gye;
+    int32_t j0, plo, phi;                    // banded: first column of the stripe's sweep; the band of the row above the stripe
+    uint32_t sq_cur, sq_nxt;
     int32_t bM_cur, bX_cur, bY_cur, bM_nxt, bX_nxt, bY_nxt;
+    // chunk k: base t-1 and boundary column t for t = 64k + lane
+    template <bool BANDED>
+    __device__ __forceinline__ void chunk(int32_t k, int lane, uint32_t &sq, int32_t &bM, int32_t &bX, int32_t &bY) const
+    {
+        const int32_t col = (BANDED ? j0 : 0) + 64 * k + lane;
+        sq = (uint32_t)seq[min(max(col - 1, 0), n - 1)];
+        const bool inr = !BANDED || (col >= plo && col <= phi);                   // inside the band of the row above (always, unbanded)
+        if (s == 0) {
+            bM = col == 0 ? 0 : DP_NEG_INF; bX = DP_NEG_INF;
+            bY = (col == 0 || !inr) ? DP_NEG_INF : gyo + (col - 1) * gye;
+        } else {
+            const int32_t cc = min(col, n);
+            bM = inr ? rin[cc] : DP_NEG_INF; bX = inr ? rin[(n + 1) + cc] : DP_NEG_INF; bY = inr ? rin[2 * (n + 1) + cc] : DP_NEG_INF;
+        }
+    }
+    // before round c (steps 64c .. 64c + 63): chunk c becomes the current one, chunk c + 1 is fetched
+    template <bool BANDED>
+    __device__ __forceinline__ void advance(int32_t c, int lane)
+    {
+        if (c == 0) chunk<BANDED>(0, lane, sq_cur, bM_cur, bX_cur, bY_cur);
+        else { sq_cur = sq_nxt; bM_cur = bM_nxt; bX_cur = bX_nxt; bY_cur = bY_nxt; }
+        chunk<BANDED>(c + 1, lane, sq_nxt, bM_nxt, bX_nxt, bY_nxt);
+    }
+    // step t: lane 0's inputs arrive by v_readlane from the chunk registers and are put in place by v_writelane
+    __device__ __forceinline__ void take(int32_t t, int32_t &Mu, int32_t &Xu, int32_t &Yu, int32_t &bn) const
+    {
+        const int sel = t & 63;
+        Mu = lane0_set(Mu, __builtin_amdgcn_readlane(bM_cur, sel));
+        Xu = lane0_set(Xu, __builtin_amdgcn_readlane(bX_cur, sel));
+        Yu = lane0_set(Yu, __builtin_amdgcn_readlane(bY_cur, sel));
+        bn = lane0_set(bn, __builtin_amdgcn_readlane((int32_t)sq_cur, sel));
+    }
+};
+
+// Traceback walk of the anti-diagonal sweeps, from (m, n) in `state` to (0, 0), through a window of the last CAP / rowbytes steps
+// of a stripe in LDS.  Layout: stripes of 64 R rows, R rows per lane; stripe s, step t at tbp + (s * T + t) * rowbytes, the byte of
+// row r of lane l at l * R + r; step t of lane l is column j = j0(s) + t - l.  WAVES waves walk the same path (uniform control flow)
+// and refill the window together: a workgroup between two barriers, a wave on its own behind a fence.  Thread 0 records the
+// reversed ops at opr; returns their number.
+template <int R, int WAVES, int CAP>
+__device__ __forceinline__ int32_t dp_window_walk(const uint8_t *tbp, int32_t T, int32_t rowbytes, uint8_t *win, int32_t m, int32_t n, bool banded,
+                                                  int state, uint8_t *opr)
+{
+    const int tid = WAVES == 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+    const int32_t wsteps = CAP / rowbytes;
+    int32_t ti = m, tj = n, len = 0, ws = -1, wj0 = 0, wlo = 0;
+    while (ti > 0 || tj > 0) {
+        uint32_t op, nstate;
+        if (ti == 0) { op = 2; nstate = (tj == 1) ? 0 : 2; }
+        else {
+            const uint32_t i0 = (uint32_t)(ti - 1);
+            const int32_t s = (int32_t)(i0 / (64 * R)), l = (int32_t)((i0 % (64 * R)) / R), r = (int32_t)(i0 % R);
+            if (s != ws) wj0 = dp_j0(s, m, n, banded);
+            const int32_t t = tj - wj0 + l;
+            if (s != ws || t < wlo) {                  // the same for every wave: the barriers are uniform
+                ws = s; wlo = max(0, t - (wsteps - 1));
+                const uint8_t *src = tbp + ((size_t)s * T + wlo) * rowbytes;
+                const int32_t nbytes = (t - wlo + 1) * rowbytes;
+                if (WAVES > 1) __syncthreads();        // nobody still reads the old window
+                for (int32_t o = tid * 16; o < nbytes; o += 64 * WAVES * 16)
+                    *reinterpret_cast<uint4 *>(win + o) = *reinterpret_cast<const uint4 *>(src + o);
+                if (WAVES > 1) __syncthreads(); else __threadfence_block();     // the window is read by every lane
+            }
+            const uint8_t bt = win[(size_t)(t - wlo) * rowbytes + l * R + r];
+            if (state == 0) { op = 3; nstate = bt & 3; }
+            else if (state == 1) { op = 1; nstate = (bt >> 2) & 3; }
+            else { op = 2; nstate = (bt >> 4) & 3; }
+        }
+        if (tid == 0) opr[len] = (uint8_t)op;
+        len++;
+        if (op & 1) ti--;
+        if (op & 2) tj--;
+        state = (int)nstate;
+    }
+    return len;
+}
+
+// One 64-row stripe of a DP step as a wave sees it: the lane's row constants, the rolling cell state and lane 0's feed.
+struct DpStripe {
+    DpFeed F;
+    int32_t i, m, steps, gxo, gxe, sub0, sub1, sub2, sub3;
+    int32_t blo, bhi;                        // this row's band
+    bool active, park;
+    int32_t *rout; uint8_t *tbs;
+    int32_t Mc, Xc, Yc, Md, Xd, Yd;
+    uint32_t bcur;
 };
 
 template <bool BANDED>
@@ -132,7 +287,8 @@ __device__ __forceinline__ void dp_stripe_begin(DpStripe &S, int32_t s, int lane
                                                 const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows,
                                                 int32_t *rowbuf, uint8_t *tbp, int32_t T)
 {
-    S.s = s; S.m = m; S.n = n; S.seq = seq;
+    DpFeed &F = S.F;
+    F.s = s; S.m = m; F.n = n; F.seq = seq;
     S.i = s * 64 + lane + 1;
     S.active = S.i <= m;
     const uint32_t cn = S.active ? Pc[S.i - 1] : 0u;
@@ -145,8 +301,8 @@ __device__ __forceinline__ void dp_stripe_begin(DpStripe &S, int32_t s, int lane
     S.sub2 = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
     S.sub3 = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
     S.gxo = sc.go * r; S.gxe = sc.ge * r;
-    S.gyo = sc.go * krows; S.gye = sc.ge * krows;
-    S.rin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (n + 1);      // written by stripe s-1
+    F.gyo = sc.go * krows; F.gye = sc.ge * krows;
+    F.rin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (n + 1);      // written by stripe s-1
     S.rout = rowbuf + (size_t)(s & 1) * 3 * (n + 1);
     S.park = s + 1 < nstripes;
     const int32_t rows_here = min(64, m - s * 64);
@@ -155,33 +311,17 @@ __device__ __forceinline__ void dp_stripe_begin(DpStripe &S, int32_t s, int lane
         const int64_t ci = dp_diag(S.active ? S.i : m, m, n);
         S.blo = (int32_t)max((int64_t)0, ci - W); S.bhi = (int32_t)min((int64_t)n, ci + W);
         const int64_t cp = dp_diag((int64_t)s * 64, m, n);
-        S.plo = (int32_t)max((int64_t)0, cp - W); S.phi = (int32_t)min((int64_t)n, cp + W);
-        S.j0 = dp_j0(s, m, n, true);
+        F.plo = (int32_t)max((int64_t)0, cp - W); F.phi = (int32_t)min((int64_t)n, cp + W);
+        F.j0 = dp_j0(s, m, n, true);
         const int32_t j1 = (int32_t)min((int64_t)n, dp_diag((int64_t)s * 64 + rows_here, m, n) + W);
-        S.steps = (j1 - S.j0 + 1) + rows_here - 1;
+        S.steps = (j1 - F.j0 + 1) + rows_here - 1;
     } else {
-        S.blo = 0; S.bhi = n; S.plo = 0; S.phi = n; S.j0 = 0;
+        S.blo = 0; S.bhi = n; F.plo = 0; F.phi = n; F.j0 = 0;
         S.steps = n + rows_here;                                // t = 0 .. n + rows_here - 1
     }
     S.tbs = tbp + (size_t)s * T * 64 + lane;
     S.Mc = S.Xc = S.Yc = S.Md = S.Xd = S.Yd = DP_NEG_INF;
     S.bcur = 0;
-}
-
-// chunk k of lane 0's inputs: base t-1 and boundary column t for t = 64k + lane
-template <bool BANDED>
-__device__ __forceinline__ void dp_stripe_chunk(const DpStripe &S, int32_t k, int lane, uint32_t &sq, int32_t &bM, int32_t &bX, int32_t &bY)
-{
-    const int32_t col = (BANDED ? S.j0 : 0) + 64 * k + lane;
-    sq = (uint32_t)S.seq[min(max(col - 1, 0), S.n - 1)];
-    const bool inr = !BANDED || (col >= S.plo && col <= S.phi);               // inside the band of the row above (always, unbanded)
-    if (S.s == 0) {
-        bM = col == 0 ? 0 : DP_NEG_INF; bX = DP_NEG_INF;
-        bY = (col == 0 || !inr) ? DP_NEG_INF : S.gyo + (col - 1) * S.gye;
-    } else {
-        const int32_t cc = min(col, S.n);
-        bM = inr ? S.rin[cc] : DP_NEG_INF; bX = inr ? S.rin[(S.n + 1) + cc] : DP_NEG_INF; bY = inr ? S.rin[2 * (S.n + 1) + cc] : DP_NEG_INF;
-    }
 }
 
 // round c: steps t = 64c .. min(64c + 63, steps - 1).  The cell update is straight-line code: the state moves only where
@@ -192,38 +332,33 @@ __device__ __forceinline__ void dp_stripe_chunk(const DpStripe &S, int32_t k, in
 template <bool BANDED>
 __device__ __forceinline__ void dp_stripe_round(DpStripe &S, int32_t c, int lane)
 {
-    if (c == 0) dp_stripe_chunk<BANDED>(S, 0, lane, S.sq_cur, S.bM_cur, S.bX_cur, S.bY_cur);
-    else { S.sq_cur = S.sq_nxt; S.bM_cur = S.bM_nxt; S.bX_cur = S.bX_nxt; S.bY_cur = S.bY_nxt; }
-    dp_stripe_chunk<BANDED>(S, c + 1, lane, S.sq_nxt, S.bM_nxt, S.bX_nxt, S.bY_nxt);
+    S.F.template advance<BANDED>(c, lane);
     const int32_t t0 = __builtin_amdgcn_readfirstlane(64 * c), t_end = __builtin_amdgcn_readfirstlane(min(64 * c + 64, S.steps));
     const bool park = __builtin_amdgcn_readfirstlane((int)S.park) != 0;
-    const int32_t jbase = (BANDED ? S.j0 : 0) - lane;
+    const int32_t n = S.F.n, gyo = S.F.gyo, gye = S.F.gye;
+    const int32_t jbase = (BANDED ? S.F.j0 : 0) - lane;
     uint8_t *tbw = S.tbs + (size_t)t0 * 64;
     for (int32_t t = t0; t < t_end; t++, tbw += 64) {
         const int32_t j = jbase + t;
         // (i-1, j): lane-1's newest values (DPP wave shift); lane 0 takes the stripe's upper boundary row
         int32_t Mu = wave_shr1z(S.Mc), Xu = wave_shr1z(S.Xc), Yu = wave_shr1z(S.Yc);
         int32_t bn = wave_shr1z((int32_t)S.bcur);
-        const int sel = t & 63;
-        Mu = lane0_set(Mu, __builtin_amdgcn_readlane(S.bM_cur, sel));
-        Xu = lane0_set(Xu, __builtin_amdgcn_readlane(S.bX_cur, sel));
-        Yu = lane0_set(Yu, __builtin_amdgcn_readlane(S.bY_cur, sel));
-        bn = lane0_set(bn, __builtin_amdgcn_readlane((int32_t)S.sq_cur, sel));
+        S.F.take(t, Mu, Xu, Yu, bn);
         const uint32_t bnext = (uint32_t)bn;
         S.bcur = bnext;
-        const bool on = S.active && (uint32_t)j <= (uint32_t)S.n, j1 = j >= 1;
+        const bool on = S.active && (uint32_t)j <= (uint32_t)n, j1 = j >= 1;
         int32_t best; uint32_t pm, px, py;
         max3(S.Md, S.Xd, S.Yd, best, pm);
         const int32_t sa = (bnext & 1) ? S.sub1 : S.sub0, sb = (bnext & 1) ? S.sub3 : S.sub2;
         int32_t Mn = max(best + ((bnext & 2) ? sb : sa), DP_NEG_INF);
         max3(Mu + S.gxo, Xu + S.gxe, Yu + S.gxo, best, px);
         const int32_t Xn = max(best, DP_NEG_INF);
-        max3(S.Mc + S.gyo, S.Xc + S.gyo, S.Yc + S.gye, best, py);    // (i, j-1): own previous column
+        max3(S.Mc + gyo, S.Xc + gyo, S.Yc + gye, best, py);          // (i, j-1): own previous column
         int32_t Yn = max(best, DP_NEG_INF);
         Mn = j1 ? Mn : DP_NEG_INF; Yn = j1 ? Yn : DP_NEG_INF; pm = j1 ? pm : 0u; py = j1 ? py : 0u;
         *tbw = (uint8_t)(pm | (px << 2) | (py << 4));
         const bool upd = on && (!BANDED || (j >= S.blo && j <= S.bhi));
-        if (park) { if (upd && lane == 63) { S.rout[j] = Mn; S.rout[(S.n + 1) + j] = Xn; S.rout[2 * (S.n + 1) + j] = Yn; } }
+        if (park) { if (upd && lane == 63) { S.rout[j] = Mn; S.rout[(n + 1) + j] = Xn; S.rout[2 * (n + 1) + j] = Yn; } }
         if (BANDED) {                                                  // outside the band: minus infinity for whoever reads it
             S.Mc = upd ? Mn : (on ? DP_NEG_INF : S.Mc); S.Xc = upd ? Xn : (on ? DP_NEG_INF : S.Xc); S.Yc = upd ? Yn : (on ? DP_NEG_INF : S.Yc);
         } else { S.Mc = upd ? Mn : S.Mc; S.Xc = upd ? Xn : S.Xc; S.Yc = upd ? Yn : S.Yc; }
@@ -287,18 +422,15 @@ __device__ __forceinline__ void dp_mw_sweep(int32_t *s_stripe, int32_t *s_round,
     }
 }
 
-__device__ void dp_interval_mw(int nseq, int64_t iv, const uint8_t *__restrict__ codes, const int64_t *__restrict__ seq_off,
-                               DpMeta *__restrict__ meta, uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA,
-                               uint32_t *__restrict__ cntB, uint32_t *__restrict__ maskB, uint8_t *__restrict__ tb,
-                               const int64_t *__restrict__ tb_off, int32_t *__restrict__ rows,
-                               const int64_t *__restrict__ rows_off, uint8_t *__restrict__ ops, const DpScoring &sc, int64_t band_from)
+__device__ void dp_interval_mw(int nseq, int64_t iv, const DpBufs &B, int64_t band_from)
 {
     __shared__ int32_t s_stripe[DP_MW_WAVES], s_round[DP_MW_WAVES], s_fin[3];
     __shared__ __attribute__((aligned(16))) uint8_t s_win[DP_MW_WIN * 64];     // traceback window of the walk
     constexpr int W = DP_MW_WAVES;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t lt = lane ? (~0ULL >> (64 - lane)) : 0ULL;
-    DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
+    const int64_t *seq_off = B.seq_off;
+    const DpScoring &sc = B.sc;
+    DpMeta mt = dp_meta_zero();
     const int64_t base = seq_off[iv * nseq];
     int64_t longest = 0;
     for (int g = 0; g < nseq; g++) longest = max(longest, seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g]);
@@ -307,11 +439,10 @@ __device__ void dp_interval_mw(int nseq, int64_t iv, const uint8_t *__restrict__
         const int64_t so = seq_off[iv * nseq + g];
         const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
         if (n == 0) continue;
-        const uint8_t *seq = codes + so;
-        uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-        uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
+        const uint8_t *seq = B.codes + so;
+        const DpStep P = dp_step_ptrs(B, mt, base);
         if (mt.krows == 0) {
-            for (int32_t c = threadIdx.x; c < n; c += 64 * W) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
+            dp_first_profile<64 * W>(P, seq, n, g, threadIdx.x);
             mt.m = n; mt.krows = 1;
             __threadfence_block();
             __syncthreads();
@@ -319,73 +450,25 @@ __device__ void dp_interval_mw(int nseq, int64_t iv, const uint8_t *__restrict__
         }
         const int32_t m = mt.m;
         const int32_t T = (int32_t)dp_stride(m, n, banded);
-        auto j0_of = [&](int32_t st) -> int32_t { return dp_j0(st, m, n, banded); };
-        uint8_t *tbp = tb + tb_off[iv];
-        int32_t *rowbuf = rows + rows_off[iv];
+        uint8_t *tbp = B.tb + B.tb_off[iv];
+        int32_t *rowbuf = B.rows + B.rows_off[iv];
         const int32_t nstripes = (m + 63) / 64;
 
-        if (banded) dp_mw_sweep<true>(s_stripe, s_round, s_fin, lane, wv, m, n, nstripes, Pc, seq, sc, mt.krows, rowbuf, tbp, T);
-        else dp_mw_sweep<false>(s_stripe, s_round, s_fin, lane, wv, m, n, nstripes, Pc, seq, sc, mt.krows, rowbuf, tbp, T);
-        int32_t fM, fX, fY;
-        fM = s_fin[0]; fX = s_fin[1]; fY = s_fin[2];
-        int32_t best = fM; int state = 0;
-        if (fX > best) { best = fX; state = 1; }
-        if (fY > best) { best = fY; state = 2; }
-
-        // ---- traceback: every wave walks the same path (uniform control flow), wave 0 records it ----
-        uint8_t *opr = ops + base;
-        // through a window in LDS that the whole workgroup refills (as the one-wave walker of dp2_interval does)
-        int32_t ti = m, tj = n, len = 0, ws = -1, wj0 = 0, wlo = 0;
-        while (ti > 0 || tj > 0) {
-            uint32_t op, nstate;
-            if (ti == 0) { op = 2; nstate = (tj == 1) ? 0 : 2; }
-            else {
-                const int32_t s = (ti - 1) >> 6, l = (ti - 1) & 63;
-                if (s != ws) wj0 = j0_of(s);
-                const int32_t t = tj - wj0 + l;
-                if (s != ws || t < wlo) {                  // the same for every wave: the barriers are uniform
-                    ws = s; wlo = max(0, t - (DP_MW_WIN - 1));
-                    const uint8_t *src = tbp + ((size_t)s * T + wlo) * 64;
-                    const int32_t nbytes = (t - wlo + 1) * 64;
-                    __syncthreads();                       // nobody still reads the old window
-                    for (int32_t o = threadIdx.x * 16; o < nbytes; o += 64 * W * 16)
-                        *reinterpret_cast<uint4 *>(s_win + o) = *reinterpret_cast<const uint4 *>(src + o);
-                    __syncthreads();
-                }
-                const uint8_t bt = s_win[(size_t)(t - wlo) * 64 + l];
-                if (state == 0) { op = 3; nstate = bt & 3; }
-                else if (state == 1) { op = 1; nstate = (bt >> 2) & 3; }
-                else { op = 2; nstate = (bt >> 4) & 3; }
-            }
-            if (threadIdx.x == 0) opr[len] = (uint8_t)op;
-            len++;
-            if (op & 1) ti--;
-            if (op & 2) tj--;
-            state = (int)nstate;
-        }
+        if (banded) dp_mw_sweep<true>(s_stripe, s_round, s_fin, lane, wv, m, n, nstripes, P.Pc, seq, sc, mt.krows, rowbuf, tbp, T);
+        else dp_mw_sweep<false>(s_stripe, s_round, s_fin, lane, wv, m, n, nstripes, P.Pc, seq, sc, mt.krows, rowbuf, tbp, T);
+        int state;
+        const int32_t best = dp_pick_state(s_fin[0], s_fin[1], s_fin[2], state);
+        // ---- traceback: every wave walks the same path, the whole workgroup refills the window, thread 0 records ----
+        uint8_t *opr = B.ops + base;
+        const int32_t len = dp_window_walk<1, W, DP_MW_WIN * 64>(tbp, T, 64, s_win, m, n, banded, state, opr);
         __threadfence_block();
         __syncthreads();
-        // ---- new profile: every wave keeps the running source counts, chunk k is written by wave k mod W ----
-        int32_t carry_p = 0, carry_s = 0;
-        for (int32_t c0i = 0, k = 0; c0i < len; c0i += 64, k++) {
-            const int32_t c = c0i + lane;
-            const bool ok = c < len;
-            const uint32_t op = ok ? opr[len - 1 - c] : 0u;
-            const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
-            if (ok && (k % W) == wv) {
-                const int32_t pi = carry_p + (int32_t)__popcll(bp & lt), sj = carry_s + (int32_t)__popcll(bs & lt);
-                uint32_t cv = 0, mv = 0;
-                if (op & 1) { cv = Pc[pi]; mv = Pm[pi]; }
-                if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
-                Qc[c] = cv; Qm[c] = mv;
-            }
-            carry_p += (int32_t)__popcll(bp); carry_s += (int32_t)__popcll(bs);
-        }
-        mt.cells += dp_step_cells(m, n, banded, lane); mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1;
+        dp_rebuild<W>(P, opr, len, seq, g, lane, wv);
+        dp_step_done(mt, dp_step_cells(m, n, banded, lane), best, len);
         __threadfence_block();
         __syncthreads();
     }
-    if (threadIdx.x == 0) meta[iv] = mt;
+    if (threadIdx.x == 0) B.meta[iv] = mt;
 }
 
 // ================================================================================================================
@@ -466,11 +549,11 @@ struct Dp2Rows {
 // ---- sub-wave groups: 64 / G intervals per wave, G lanes x R rows each, everything of a step in LDS ----
 template <int G>
 __device__ void dp2_groups(int nseq, const int64_t *__restrict__ list, int64_t first, int64_t count, int64_t wave_index, int64_t nwaves,
-                           const uint8_t *__restrict__ codes, const int64_t *__restrict__ seq_off, DpMeta *__restrict__ meta,
-                           uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA, uint32_t *__restrict__ cntB,
-                           uint32_t *__restrict__ maskB, uint32_t *s_tb_wave, uint16_t *s_rec_wave, uint8_t *s_seq_wave, const DpScoring &sc)
+                           const DpBufs &B, uint32_t *s_tb_wave, uint16_t *s_rec_wave, uint8_t *s_seq_wave)
 {
     constexpr int R = DP2_R, GROUPS = 64 / G, ROWS = G * R;
+    const int64_t *seq_off = B.seq_off;
+    const DpScoring &sc = B.sc;
     const int lane = threadIdx.x & 63, ql = lane & (G - 1), q = lane / G, gbase = lane & ~(G - 1);
     const bool leader = ql == 0;
     uint32_t *tbq = s_tb_wave + q * (DP2_T * G);                       // one dword per (step, lane of the group)
@@ -480,7 +563,7 @@ __device__ void dp2_groups(int nseq, const int64_t *__restrict__ list, int64_t f
     for (int64_t li0 = wave_index * GROUPS; li0 < count; li0 += nwaves * GROUPS) {
         const bool have = li0 + q < count;
         const int64_t iv = have ? list[first + li0 + q] : 0;
-        DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
+        DpMeta mt = dp_meta_zero();
         const int64_t base = have ? seq_off[iv * nseq] : 0;
         // The class comes from an ESTIMATE of the profile lengths (DpClassEst): a group whose profile outgrows its rows, or
         // whose step outgrows the LDS slice, gives the interval up (mt.m = -1); the wave runs it alone afterwards.
@@ -489,16 +572,15 @@ __device__ void dp2_groups(int nseq, const int64_t *__restrict__ list, int64_t f
             int64_t so = 0; int32_t n = 0;
             if (have && !dead) { so = seq_off[iv * nseq + g]; n = (int32_t)(seq_off[iv * nseq + g + 1] - so); }
             if (n > 0 && mt.krows > 0 && (mt.m > ROWS || n + G > DP2_T)) { dead = true; n = 0; }
-            const uint8_t *seq = codes + so;
-            uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-            uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
+            const uint8_t *seq = B.codes + so;
+            const DpStep P = dp_step_ptrs(B, mt, base);
             const bool init = n > 0 && mt.krows == 0, step = n > 0 && mt.krows > 0;
-            if (init) for (int32_t c = ql; c < n; c += G) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
+            if (init) dp_first_profile<G>(P, seq, n, g, ql);
             if (__ballot(step)) {
                 const int32_t m = step ? mt.m : 0, nn = step ? n : 0;
                 for (int32_t c = ql; c < nn; c += G) seqq[G + c] = seq[c];       // base j at seqq[G + j - 1]
                 Dp2Rows<R> L;
-                L.constants(Pc, ql * R, m, sc);
+                L.constants(P.Pc, ql * R, m, sc);
                 const int32_t gyo = sc.go * mt.krows, gye = sc.ge * mt.krows;
                 const int32_t La = (m + R - 1) / R;                               // lanes of the group that hold rows
                 const bool has = ql < La;
@@ -527,9 +609,8 @@ __device__ void dp2_groups(int nseq, const int64_t *__restrict__ list, int64_t f
                 int32_t fM, fX, fY;
                 L.row((max(m, 1) - 1) % R, fM, fX, fY);       // the lane of row m holds (m, n) in that row: its state stopped at column n
                 fM = lane_read(fM, owner); fX = lane_read(fX, owner); fY = lane_read(fY, owner);
-                int32_t best = fM; int state = 0;
-                if (fX > best) { best = fX; state = 1; }
-                if (fY > best) { best = fY; state = 2; }
+                int state;
+                const int32_t best = dp_pick_state(fM, fX, fY, state);
                 // ---- traceback: the group leaders walk side by side; an op is recorded with the profile column / base it consumes ----
                 int32_t len = 0;
                 if (leader && step) {
@@ -561,18 +642,18 @@ __device__ void dp2_groups(int nseq, const int64_t *__restrict__ list, int64_t f
                     if (step && c < len) {
                         const uint32_t rec = recq[len - 1 - c];
                         uint32_t cv = 0, mv = 0;
-                        if (rec & 1u) { const uint32_t pi = (rec >> 2) & 127u; cv = Pc[pi]; mv = Pm[pi]; }
+                        if (rec & 1u) { const uint32_t pi = (rec >> 2) & 127u; cv = P.Pc[pi]; mv = P.Pm[pi]; }
                         if (rec & 2u) { cv += 1u << (8 * seqq[G + ((rec >> 9) & 127u)]); mv |= 1u << g; }
-                        Qc[c] = cv; Qm[c] = mv;
+                        P.Qc[c] = cv; P.Qm[c] = mv;
                     }
                 }
-                if (step) { mt.cells += (int64_t)m * nn; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1; }
+                if (step) dp_step_done(mt, (int64_t)m * nn, best, len);
             }
             if (init) { mt.m = n; mt.krows = 1; }
             __threadfence_block();       // profiles written by some lanes are read by others in the next step
         }
         if (dead) mt.m = -1;
-        if (have && leader) meta[iv] = mt;
+        if (have && leader) B.meta[iv] = mt;
     }
 }
 
@@ -589,12 +670,12 @@ __host__ __device__ __forceinline__ int64_t dp2_tb_need(int64_t m, int64_t n)
 template <int R>
 struct Dp2Stripe {
     Dp2Rows<R> L;
-    int32_t s, n, steps, gyo, gye, La;
+    DpFeed F;                                // never banded
+    int32_t steps, La;
     bool has, park;
-    const uint8_t *seq; const int32_t *rin; int32_t *rout; uint8_t *tbs; int32_t rowbytes;
+    int32_t *rout; uint8_t *tbs; int32_t rowbytes;
     int32_t Md, Xd, Yd;
-    uint32_t bcur, sq_cur, sq_nxt;
-    int32_t bM_cur, bX_cur, bY_cur, bM_nxt, bX_nxt, bY_nxt;
+    uint32_t bcur;
 };
 
 template <int R>
@@ -602,13 +683,14 @@ __device__ __forceinline__ void dp2_stripe_begin(Dp2Stripe<R> &S, int32_t s, int
                                                  const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows, int32_t *rowbuf,
                                                  uint8_t *tbp)
 {
-    S.s = s; S.n = n; S.seq = seq;
+    DpFeed &F = S.F;
+    F.s = s; F.n = n; F.seq = seq; F.j0 = 0; F.plo = 0; F.phi = n;
     const int32_t rows_here = min(64 * R, m - s * 64 * R);
     S.La = (rows_here + R - 1) / R;
     S.has = lane < S.La;
     S.L.constants(Pc, s * 64 * R + lane * R, m, sc);
-    S.gyo = sc.go * krows; S.gye = sc.ge * krows;
-    S.rin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (n + 1);      // written by stripe s-1
+    F.gyo = sc.go * krows; F.gye = sc.ge * krows;
+    F.rin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (n + 1);      // written by stripe s-1
     S.rout = rowbuf + (size_t)(s & 1) * 3 * (n + 1);
     S.park = s + 1 < nstripes;
     S.steps = n + S.La;                                         // t = 0 .. n + La - 1
@@ -618,27 +700,11 @@ __device__ __forceinline__ void dp2_stripe_begin(Dp2Stripe<R> &S, int32_t s, int
     S.bcur = 0;
 }
 
-// chunk k of lane 0's inputs: base t-1 and the row above the stripe at column t, for t = 64k + lane
-template <int R>
-__device__ __forceinline__ void dp2_stripe_chunk(const Dp2Stripe<R> &S, int32_t k, int lane, uint32_t &sq, int32_t &bM, int32_t &bX, int32_t &bY)
-{
-    const int32_t col = 64 * k + lane;
-    sq = (uint32_t)S.seq[min(max(col - 1, 0), S.n - 1)];
-    if (S.s == 0) {
-        bM = col == 0 ? 0 : DP_NEG_INF; bX = DP_NEG_INF;
-        bY = col == 0 ? DP_NEG_INF : S.gyo + (col - 1) * S.gye;
-    } else {
-        const int32_t cc = min(col, S.n);
-        bM = S.rin[cc]; bX = S.rin[(S.n + 1) + cc]; bY = S.rin[2 * (S.n + 1) + cc];
-    }
-}
-
 template <int R>
 __device__ __forceinline__ void dp2_stripe_round(Dp2Stripe<R> &S, int32_t c, int lane)
 {
-    if (c == 0) dp2_stripe_chunk<R>(S, 0, lane, S.sq_cur, S.bM_cur, S.bX_cur, S.bY_cur);
-    else { S.sq_cur = S.sq_nxt; S.bM_cur = S.bM_nxt; S.bX_cur = S.bX_nxt; S.bY_cur = S.bY_nxt; }
-    dp2_stripe_chunk<R>(S, c + 1, lane, S.sq_nxt, S.bM_nxt, S.bX_nxt, S.bY_nxt);
+    S.F.template advance<false>(c, lane);
+    const int32_t n = S.F.n;
     const int32_t t0 = __builtin_amdgcn_readfirstlane(64 * c), t_end = __builtin_amdgcn_readfirstlane(min(64 * c + 64, S.steps));
     const bool park = __builtin_amdgcn_readfirstlane((int)S.park) != 0;
     uint8_t *tbw = S.tbs + (size_t)t0 * S.rowbytes;
@@ -646,54 +712,46 @@ __device__ __forceinline__ void dp2_stripe_round(Dp2Stripe<R> &S, int32_t c, int
         const int32_t j = t - lane;
         int32_t Mu = wave_shr1z(S.L.M[R - 1]), Xu = wave_shr1z(S.L.X[R - 1]), Yu = wave_shr1z(S.L.Y[R - 1]);
         int32_t bn = wave_shr1z((int32_t)S.bcur);
-        const int sel = t & 63;
-        Mu = lane0_set(Mu, __builtin_amdgcn_readlane(S.bM_cur, sel));
-        Xu = lane0_set(Xu, __builtin_amdgcn_readlane(S.bX_cur, sel));
-        Yu = lane0_set(Yu, __builtin_amdgcn_readlane(S.bY_cur, sel));
-        bn = lane0_set(bn, __builtin_amdgcn_readlane((int32_t)S.sq_cur, sel));
+        S.F.take(t, Mu, Xu, Yu, bn);
         S.bcur = (uint32_t)bn;
-        if (S.has && (uint32_t)j <= (uint32_t)S.n) {
-            const uint32_t tb = S.L.step(Mu, Xu, Yu, S.Md, S.Xd, S.Yd, (uint32_t)bn, S.gyo, S.gye, j >= 1);
+        if (S.has && (uint32_t)j <= (uint32_t)n) {
+            const uint32_t tb = S.L.step(Mu, Xu, Yu, S.Md, S.Xd, S.Yd, (uint32_t)bn, S.F.gyo, S.F.gye, j >= 1);
             *reinterpret_cast<uint32_t *>(tbw) = tb;
-            if (park && lane == 63) { S.rout[j] = S.L.M[R - 1]; S.rout[(S.n + 1) + j] = S.L.X[R - 1]; S.rout[2 * (S.n + 1) + j] = S.L.Y[R - 1]; }
+            if (park && lane == 63) { S.rout[j] = S.L.M[R - 1]; S.rout[(n + 1) + j] = S.L.X[R - 1]; S.rout[2 * (n + 1) + j] = S.L.Y[R - 1]; }
         }
         S.Md = Mu; S.Xd = Xu; S.Yd = Yu;
     }
 }
 
 // all progressive steps of interval iv, by one wave; win: the wave's LDS slice (DP2_TB_DW dwords) for the traceback walk
-__device__ void dp2_interval(int nseq, int64_t iv, const uint8_t *__restrict__ codes, const int64_t *__restrict__ seq_off, DpMeta *__restrict__ meta,
-                             uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA, uint32_t *__restrict__ cntB, uint32_t *__restrict__ maskB,
-                             uint8_t *__restrict__ tb, const int64_t *__restrict__ tb_off, int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
-                             uint8_t *__restrict__ ops, uint8_t *win, const DpScoring &sc)
+__device__ void dp2_interval(int nseq, int64_t iv, const DpBufs &B, uint8_t *win)
 {
     constexpr int R = DP2_R;
     const int lane = threadIdx.x & 63;
-    const uint64_t lt = lane ? (~0ULL >> (64 - lane)) : 0ULL;
-    DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
+    const int64_t *seq_off = B.seq_off;
+    DpMeta mt = dp_meta_zero();
     const int64_t base = seq_off[iv * nseq];
     for (int g = 0; g < nseq; g++) {
         const int64_t so = seq_off[iv * nseq + g];
         const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
         if (n == 0) continue;
-        const uint8_t *seq = codes + so;
-        uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-        uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
-        if (mt.krows == 0) {           // first non-empty sequence becomes the profile
-            for (int32_t c = lane; c < n; c += 64) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
+        const uint8_t *seq = B.codes + so;
+        const DpStep P = dp_step_ptrs(B, mt, base);
+        if (mt.krows == 0) {
+            dp_first_profile<64>(P, seq, n, g, lane);
             mt.m = n; mt.krows = 1;
             __threadfence_block();      // the next step's lanes read what other lanes just wrote
             continue;
         }
         const int32_t m = mt.m;
         const int32_t W = (int32_t)dp2_lanes(m), T = n + W, rowbytes = W * R;
-        uint8_t *tbp = tb + tb_off[iv];
-        int32_t *rowbuf = rows + rows_off[iv];             // 2 x 3 x (n+1)
+        uint8_t *tbp = B.tb + B.tb_off[iv];
+        int32_t *rowbuf = B.rows + B.rows_off[iv];         // 2 x 3 x (n+1)
         const int32_t nstripes = (m + 64 * R - 1) / (64 * R);
         int32_t fM = DP_NEG_INF, fX = DP_NEG_INF, fY = DP_NEG_INF;   // values at (m, n)
         for (int32_t s = 0; s < nstripes; s++) {
             Dp2Stripe<R> S;
-            dp2_stripe_begin<R>(S, s, lane, m, n, nstripes, W, Pc, seq, sc, mt.krows, rowbuf, tbp);
+            dp2_stripe_begin<R>(S, s, lane, m, n, nstripes, W, P.Pc, seq, B.sc, mt.krows, rowbuf, tbp);
             const int32_t nrounds = (S.steps + 63) / 64;
             for (int32_t c = 0; c < nrounds; c++) dp2_stripe_round<R>(S, c, lane);
             __threadfence_block();   // the parked row / traceback bytes are read back by this wave
@@ -701,59 +759,17 @@ __device__ void dp2_interval(int nseq, int64_t iv, const uint8_t *__restrict__ c
         }
         const int owner = ((m - 1) % (64 * R)) / R;
         fM = __shfl(fM, owner); fX = __shfl(fX, owner); fY = __shfl(fY, owner);
-        int32_t best = fM; int state = 0;
-        if (fX > best) { best = fX; state = 1; }
-        if (fY > best) { best = fY; state = 2; }
-        // ---- traceback (wave-uniform walk) through a window of the last DP2_TB_DW * 4 / rowbytes steps in LDS ----
-        uint8_t *opr = ops + base;                         // reversed ops, capacity m + n
-        const int32_t wsteps = (DP2_TB_DW * 4) / rowbytes;
-        int32_t ti = m, tj = n, len = 0, ws = -1, wlo = 0;
-        while (ti > 0 || tj > 0) {
-            uint32_t op, nstate;
-            if (ti == 0) { op = 2; nstate = (tj == 1) ? 0 : 2; }
-            else {
-                const int32_t i0 = ti - 1, s = i0 / (64 * R), l = (i0 % (64 * R)) / R, r = i0 % R;
-                const int32_t t = tj + l;
-                if (s != ws || t < wlo) {
-                    ws = s; wlo = max(0, t - (wsteps - 1));
-                    const uint8_t *src = tbp + ((size_t)s * T + wlo) * rowbytes;
-                    const int32_t nbytes = (t - wlo + 1) * rowbytes;
-                    for (int32_t o = lane * 16; o < nbytes; o += 1024)
-                        *reinterpret_cast<uint4 *>(win + o) = *reinterpret_cast<const uint4 *>(src + o);
-                    __threadfence_block();             // the window is read by every lane
-                }
-                const uint8_t bt = win[(size_t)(t - wlo) * rowbytes + l * R + r];
-                if (state == 0) { op = 3; nstate = bt & 3; }
-                else if (state == 1) { op = 1; nstate = (bt >> 2) & 3; }
-                else { op = 2; nstate = (bt >> 4) & 3; }
-            }
-            if (lane == 0) opr[len] = (uint8_t)op;
-            len++;
-            if (op & 1) ti--;
-            if (op & 2) tj--;
-            state = (int)nstate;
-        }
+        int state;
+        const int32_t best = dp_pick_state(fM, fX, fY, state);
+        // ---- traceback (wave-uniform walk) through a window of the last DP2_TB_DW * 4 / rowbytes steps in the wave's LDS slice ----
+        uint8_t *opr = B.ops + base;                       // reversed ops, capacity m + n
+        const int32_t len = dp_window_walk<R, 1, DP2_TB_DW * 4>(tbp, T, rowbytes, win, m, n, false, state, opr);
         __threadfence_block();
-        // ---- new profile in forward order: ballot prefix counts give each column its sources ----
-        int32_t carry_p = 0, carry_s = 0;
-        for (int32_t c0i = 0; c0i < len; c0i += 64) {
-            const int32_t c = c0i + lane;
-            const bool ok = c < len;
-            const uint32_t op = ok ? opr[len - 1 - c] : 0u;
-            const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
-            if (ok) {
-                const int32_t pi = carry_p + (int32_t)__popcll(bp & lt), sj = carry_s + (int32_t)__popcll(bs & lt);
-                uint32_t cv = 0, mv = 0;
-                if (op & 1) { cv = Pc[pi]; mv = Pm[pi]; }
-                if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
-                Qc[c] = cv; Qm[c] = mv;
-            }
-            carry_p += (int32_t)__popcll(bp); carry_s += (int32_t)__popcll(bs);
-        }
-        mt.cells += (int64_t)m * n; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1;
+        dp_rebuild<1>(P, opr, len, seq, g, lane, 0);
+        dp_step_done(mt, (int64_t)m * n, best, len);
         __threadfence_block();
     }
-    if (lane == 0) meta[iv] = mt;
+    if (lane == 0) B.meta[iv] = mt;
 }
 
 struct DpClasses { int64_t first_med, n_med, first_c, n_c, first_s32, n_s32, first_s16, n_s16; uint32_t blocks_med, blocks_c, blocks_s32; int32_t scan; };   // list = [big | one wave | G = 16 | s32 (G = 8) | s16 (G = 4)]
@@ -977,18 +993,9 @@ struct Dp3Walk {
         if (nl < 64 && t - tmin + 1 > nl) { pw = min(pend, 128); nl = min(t - tmin + 1, cap / pw); }     // square-ish: look further back along the lines
         PW = pw; p_lo = pend - pw; p_hi = pend - 1; s_hi = t; s_lo = t - nl + 1;
         const int32_t per = pw / 16, total = per * nl;
-        for (int32_t u0 = lane; u0 < total; u0 += 256) {         // four 16-byte loads in flight per lane
-            uint4 v[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int32_t u = min(u0 + 64 * q, total - 1), cl = u / per, seg = u % per;
-                v[q] = *reinterpret_cast<const uint4 *>(tb + (size_t)(s_lo + cl) * stride + p_lo + seg * 16);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int32_t u = u0 + 64 * q, cl = u / per, seg = u % per;
-                if (u < total) *reinterpret_cast<uint4 *>(win + (size_t)cl * pw + seg * 16) = v[q];
-            }
+        for (int32_t u = lane; u < total; u += 64) {
+            const int32_t cl = u / per, seg = u % per;
+            *reinterpret_cast<uint4 *>(win + (size_t)cl * pw + seg * 16) = *reinterpret_cast<const uint4 *>(tb + (size_t)(s_lo + cl) * stride + p_lo + seg * 16);
         }
         __threadfence_block();
     }
@@ -1173,72 +1180,64 @@ __device__ __forceinline__ void dp3_sweep_b(int lane, int32_t m, int32_t n, cons
     }
 }
 
-__device__ void dp3_interval(int nseq, int64_t iv, const uint8_t *__restrict__ codes, const int64_t *__restrict__ seq_off, DpMeta *__restrict__ meta,
-                             uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA, uint32_t *__restrict__ cntB, uint32_t *__restrict__ maskB,
-                             uint8_t *__restrict__ tb, const int64_t *__restrict__ tb_off, int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
-                             uint8_t *__restrict__ ops, uint8_t *win, const DpScoring &sc)
+// The layout of one step on one wave: the orientation by cost, as few rows (A) / columns (B) per lane as cover the dimension with the 64 lanes, at most 4
+// (then bands).  A: line j at tbp + j * stride; B: line i - 1 at tbp + (i - 1) * stride.
+__device__ __forceinline__ void dp3_layout(Dp3Walk &W, const uint8_t *tbp, int32_t m, int32_t n)
+{
+    W.tb = tbp; W.orient_b = dp3_orient_b(m, n);
+    const int32_t ldim = W.orient_b ? n : m;
+    W.R = dp3_rows_per_lane(ldim); W.stride = dp3_pad(ldim);
+}
+// ... and the sweep in that layout, by one wave.  Leaves (m, n) in fM / fX / fY.
+__device__ __forceinline__ void dp3_sweep(const Dp3Walk &W, int lane, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows,
+                                          int32_t *rowbuf, uint8_t *tbp, int32_t &fM, int32_t &fX, int32_t &fY)
+{
+    const int32_t pad = (int32_t)W.stride;
+    if (!W.orient_b) {
+        if (W.R == 1) dp3_sweep_a<1>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
+        else if (W.R == 2) dp3_sweep_a<2>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
+        else dp3_sweep_a<4>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
+    } else {
+        if (W.R == 1) dp3_sweep_b<1>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
+        else if (W.R == 2) dp3_sweep_b<2>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
+        else dp3_sweep_b<4>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
+    }
+}
+
+__device__ void dp3_interval(int nseq, int64_t iv, const DpBufs &B, uint8_t *win)
 {
     const int lane = threadIdx.x & 63;
-    const uint64_t lt = lane ? (~0ULL >> (64 - lane)) : 0ULL;
-    DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
+    const int64_t *seq_off = B.seq_off;
+    DpMeta mt = dp_meta_zero();
     const int64_t base = seq_off[iv * nseq];
     for (int g = 0; g < nseq; g++) {
         const int64_t so = seq_off[iv * nseq + g];
         const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
         if (n == 0) continue;
-        const uint8_t *seq = codes + so;
-        uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-        uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
-        if (mt.krows == 0) {           // first non-empty sequence becomes the profile
-            for (int32_t c = lane; c < n; c += 64) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
+        const uint8_t *seq = B.codes + so;
+        const DpStep P = dp_step_ptrs(B, mt, base);
+        if (mt.krows == 0) {
+            dp_first_profile<64>(P, seq, n, g, lane);
             mt.m = n; mt.krows = 1;
             __threadfence_block();
             continue;
         }
         const int32_t m = mt.m;
-        uint8_t *tbp = tb + tb_off[iv];
-        int32_t *rowbuf = rows + rows_off[iv];
-        const bool ob = dp3_orient_b(m, n);
         int32_t fM = DP_NEG_INF, fX = DP_NEG_INF, fY = DP_NEG_INF;   // values at (m, n)
-        // rows (A) / columns (B) per lane: as few as cover the dimension with the 64 lanes, at most 4 (then bands)
-        const int32_t ldim = ob ? n : m, R = dp3_rows_per_lane(ldim), pad = (int32_t)dp3_pad(ldim);
-        Dp3Walk W; W.win = win; W.cap = DP2_TB_DW * 4; W.orient_b = ob; W.R = R; W.stride = pad;
-        W.tb = ob ? tbp : tbp;                             // A: line j at tbp + j * pad; B: line i - 1 at tbp + (i - 1) * pad
-        if (!ob) {
-            if (R == 1) dp3_sweep_a<1>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-            else if (R == 2) dp3_sweep_a<2>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-            else dp3_sweep_a<4>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-        } else {
-            if (R == 1) dp3_sweep_b<1>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-            else if (R == 2) dp3_sweep_b<2>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-            else dp3_sweep_b<4>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-        }
-        int32_t best = fM; int state = 0;
-        if (fX > best) { best = fX; state = 1; }
-        if (fY > best) { best = fY; state = 2; }
-        uint8_t *opr = ops + base;                         // reversed ops, capacity m + n
+        uint8_t *tbp = B.tb + B.tb_off[iv];
+        Dp3Walk W; W.win = win; W.cap = DP2_TB_DW * 4;
+        dp3_layout(W, tbp, m, n);
+        dp3_sweep(W, lane, m, n, P.Pc, seq, B.sc, mt.krows, B.rows + B.rows_off[iv], tbp, fM, fX, fY);
+        int state;
+        const int32_t best = dp_pick_state(fM, fX, fY, state);
+        uint8_t *opr = B.ops + base;                       // reversed ops, capacity m + n
         const int32_t len = dp3_walk(W, m, n, state, opr, lane);
         __threadfence_block();
-        // ---- new profile in forward order: ballot prefix counts give each column its sources ----
-        int32_t carry_p = 0, carry_s = 0;
-        for (int32_t c0i = 0; c0i < len; c0i += 64) {
-            const int32_t c = c0i + lane;
-            const bool ok = c < len;
-            const uint32_t op = ok ? opr[len - 1 - c] : 0u;
-            const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
-            if (ok) {
-                const int32_t pi = carry_p + (int32_t)__popcll(bp & lt), sj = carry_s + (int32_t)__popcll(bs & lt);
-                uint32_t cv = 0, mv = 0;
-                if (op & 1) { cv = Pc[pi]; mv = Pm[pi]; }
-                if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
-                Qc[c] = cv; Qm[c] = mv;
-            }
-            carry_p += (int32_t)__popcll(bp); carry_s += (int32_t)__popcll(bs);
-        }
-        mt.cells += (int64_t)m * n; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1;
+        dp_rebuild<1>(P, opr, len, seq, g, lane, 0);
+        dp_step_done(mt, (int64_t)m * n, best, len);
         __threadfence_block();
     }
-    if (lane == 0) meta[iv] = mt;
+    if (lane == 0) B.meta[iv] = mt;
 }
 
 
@@ -1256,7 +1255,7 @@ __device__ void dp3_interval(int nseq, int64_t iv, const uint8_t *__restrict__ c
 // tie rules; E stays far from the clamp for every interval dp3_admissible lets in), the traceback layout is dp3's with R = 4
 // (wave w of super-band q is band 16 q + w), so dp3_walk reads it; steps small in both dimensions run the one-wave sweep.
 // ================================================================================================================
-constexpr int DPW_MAXW = 16;                      // waves of a workgroup (two shapes are built: 8 waves x 4 rows per lane, 16 x 2; both super-bands hold 2048 rows)
+constexpr int DPW_MAXW = 8;                       // waves of a workgroup (one shape is built: 8 waves x 4 rows per lane, a super-band of 2048 rows)
 constexpr int DPW_SB = 2048;
 struct DpwShared {
     int32_t botM[DPW_MAXW], botE[DPW_MAXW];      // last cell of every wave in the current line: M and the element-wise gap state (A: Y, B: X)
@@ -1660,17 +1659,16 @@ __device__ __forceinline__ void dpw_sweep_b(DpwShared &S, int lane, int wv, int3
 // cluster of K workgroups (CL): they all go through the steps together, the sweeps of steps with several super-bands are shared, workgroup 0 walks and
 // rebuilds and tells the others the outcome of every step
 template <int R, int W>
-__device__ void dp_interval_wide(int nseq, int64_t iv, const uint8_t *__restrict__ codes, const int64_t *__restrict__ seq_off, DpMeta *__restrict__ meta,
-                                 uint32_t *__restrict__ cntA, uint32_t *__restrict__ maskA, uint32_t *__restrict__ cntB, uint32_t *__restrict__ maskB,
-                                 uint8_t *__restrict__ tb, const int64_t *__restrict__ tb_off, int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
-                                 uint8_t *__restrict__ ops, const DpScoring &sc, DpwCluster CL)
+__device__ void dp_interval_wide(int nseq, int64_t iv, const DpBufs &B, DpwCluster CL)
 {
+    static_assert(W <= DPW_MAXW, "DpwShared holds a slot per wave");
     __shared__ DpwShared S;
     __shared__ __attribute__((aligned(16))) uint8_t s_wwin[DP2_TB_DW * 4];       // traceback window of the walk (wave 0)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t lt = lane ? (~0ULL >> (64 - lane)) : 0ULL;
+    const int64_t *seq_off = B.seq_off;
+    const DpScoring &sc = B.sc;
     const bool lead = !CL.on() || CL.c == 0;                 // the workgroup that walks, rebuilds and writes the result
-    DpMeta mt; mt.m = 0; mt.krows = 0; mt.cur = 0; mt.pad = 0; mt.score = 0; mt.cells = 0;
+    DpMeta mt = dp_meta_zero();
     const int64_t base = seq_off[iv * nseq];
     bool good = true;
     CL.step = 0;
@@ -1692,11 +1690,10 @@ __device__ void dp_interval_wide(int nseq, int64_t iv, const uint8_t *__restrict
         const int64_t so = seq_off[iv * nseq + g];
         const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
         if (n == 0) continue;
-        const uint8_t *seq = codes + so;
-        uint32_t *Pc = (mt.cur ? cntB : cntA) + base, *Pm = (mt.cur ? maskB : maskA) + base;
-        uint32_t *Qc = (mt.cur ? cntA : cntB) + base, *Qm = (mt.cur ? maskA : maskB) + base;
+        const uint8_t *seq = B.codes + so;
+        const DpStep P = dp_step_ptrs(B, mt, base);
         if (mt.krows == 0) {
-            if (lead) for (int32_t c = threadIdx.x; c < n; c += 64 * W) { Pc[c] = 1u << (8 * seq[c]); Pm[c] = 1u << g; }
+            if (lead) dp_first_profile<64 * W>(P, seq, n, g, threadIdx.x);
             mt.m = n; mt.krows = 1;
             __threadfence_block();
             __syncthreads();
@@ -1704,8 +1701,8 @@ __device__ void dp_interval_wide(int nseq, int64_t iv, const uint8_t *__restrict
             continue;
         }
         const int32_t m = mt.m;
-        uint8_t *tbp = tb + tb_off[iv];
-        int32_t *rowbuf = rows + rows_off[iv];
+        uint8_t *tbp = B.tb + B.tb_off[iv];
+        int32_t *rowbuf = B.rows + B.rows_off[iv];
         Dp3Walk Wk; Wk.win = s_wwin; Wk.cap = DP2_TB_DW * 4; Wk.tb = tbp;
         const bool wide_b = dpw_orient_b(m, n);
         const int32_t ldim = wide_b ? n : m;
@@ -1717,8 +1714,8 @@ __device__ void dp_interval_wide(int nseq, int64_t iv, const uint8_t *__restrict
             Wk.orient_b = wide_b; Wk.R = 4; Wk.stride = pad;              // (a byte per row / column: the walk's R = 4 layout whatever R the sweep ran with)
             DpwCluster C1 = CL; if (nsb < 2) C1.K = 1;                    // one super-band: nothing to share (the lead runs it as if alone)
             if (C1.on() || lead) {
-                if (!wide_b) dpw_sweep_a<R, W>(S, lane, wv, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1);
-                else dpw_sweep_b<R, W>(S, lane, wv, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1);
+                if (!wide_b) dpw_sweep_a<R, W>(S, lane, wv, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1);
+                else dpw_sweep_b<R, W>(S, lane, wv, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1);
             }
             if (C1.on()) {
                 // the traceback bytes (and, from whoever ran the last super-band, the final cell) to the lead
@@ -1740,30 +1737,19 @@ __device__ void dp_interval_wide(int nseq, int64_t iv, const uint8_t *__restrict
             }
         } else if (lead) {
             // small in the dimension the cost rule picks: the one-wave sweep, by wave 0 (dp3_interval's choice of orientation and of R)
-            const bool ob = dp3_orient_b(m, n);
-            const int32_t ld1 = ob ? n : m, R1 = dp3_rows_per_lane(ld1), pad = (int32_t)dp3_pad(ld1);
-            Wk.orient_b = ob; Wk.R = R1; Wk.stride = pad;
+            dp3_layout(Wk, tbp, m, n);
             if (wv == 0) {
                 int32_t fM = DP_NEG_INF, fX = DP_NEG_INF, fY = DP_NEG_INF;
-                if (!ob) {
-                    if (R1 == 1) dp3_sweep_a<1>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-                    else if (R1 == 2) dp3_sweep_a<2>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-                    else dp3_sweep_a<4>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-                } else {
-                    if (R1 == 1) dp3_sweep_b<1>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-                    else if (R1 == 2) dp3_sweep_b<2>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-                    else dp3_sweep_b<4>(lane, m, n, Pc, seq, sc, mt.krows, rowbuf, tbp, pad, fM, fX, fY);
-                }
+                dp3_sweep(Wk, lane, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, fM, fX, fY);
                 if (lane == 0) { S.fin[0] = fM; S.fin[1] = fX; S.fin[2] = fY; }
             }
             __threadfence_block();
             __syncthreads();
         }
-        int32_t len = 0;
+        int32_t len = 0, best; int state;
         if (lead) {
-            const int32_t fM = S.fin[0], fX = S.fin[1], fY = S.fin[2];
-            int state = 0; { int32_t best = fM; if (fX > best) { best = fX; state = 1; } if (fY > best) { best = fY; state = 2; } }
-            uint8_t *opr = ops + base;                         // reversed ops, capacity m + n
+            best = dp_pick_state(S.fin[0], S.fin[1], S.fin[2], state);
+            uint8_t *opr = B.ops + base;                       // reversed ops, capacity m + n
             if (wv == 0) {
                 const int32_t l0 = dp3_walk(Wk, m, n, state, opr, lane);
                 if (lane == 0) S.len = l0;
@@ -1771,36 +1757,17 @@ __device__ void dp_interval_wide(int nseq, int64_t iv, const uint8_t *__restrict
             __threadfence_block();
             __syncthreads();
             len = S.len;
-            // ---- new profile: every wave keeps the running source counts, chunk k is written by wave k mod W ----
-            int32_t carry_p = 0, carry_s = 0;
-            for (int32_t c0i = 0, k = 0; c0i < len; c0i += 64, k++) {
-                const int32_t c = c0i + lane;
-                const bool ok = c < len;
-                const uint32_t op = ok ? opr[len - 1 - c] : 0u;
-                const uint64_t bp = __ballot(ok && (op & 1)), bs = __ballot(ok && (op & 2));
-                if (ok && (k % W) == wv) {
-                    const int32_t pi = carry_p + (int32_t)__popcll(bp & lt), sj = carry_s + (int32_t)__popcll(bs & lt);
-                    uint32_t cv = 0, mv = 0;
-                    if (op & 1) { cv = Pc[pi]; mv = Pm[pi]; }
-                    if (op & 2) { cv += 1u << (8 * seq[sj]); mv |= 1u << g; }
-                    Qc[c] = cv; Qm[c] = mv;
-                }
-                carry_p += (int32_t)__popcll(bp); carry_s += (int32_t)__popcll(bs);
-            }
+            dp_rebuild<W>(P, opr, len, seq, g, lane, wv);
             tell(len);
-        } else hear(len);
-        {
-            const int32_t fM = S.fin[0], fX = S.fin[1], fY = S.fin[2];
-            int32_t best = fM; if (fX > best) best = fX; if (fY > best) best = fY;
-            mt.cells += (int64_t)m * n; mt.score += best; mt.m = len; mt.krows += 1; mt.cur ^= 1;
-        }
+        } else { hear(len); best = dp_pick_state(S.fin[0], S.fin[1], S.fin[2], state); }
+        dp_step_done(mt, (int64_t)m * n, best, len);
         CL.step++;
         __threadfence_block();
         __syncthreads();
     }
     if (lead && threadIdx.x == 0) {
         if (CL.on() && (!good || __hip_atomic_load(CL.failed(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ULL)) mt.pad = 1;     // a wait of the cluster ran out: the host refuses the batch
-        meta[iv] = mt;
+        B.meta[iv] = mt;
     }
 }
 
@@ -1821,9 +1788,10 @@ __global__ void __launch_bounds__(64 * DP_MW_WAVES) dp_step_big(int nseq, const 
                                                int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
                                                uint8_t *__restrict__ ops, DpScoring sc, int64_t band_from, int wide)
 {
+    const DpBufs B = { codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, sc };
     const int64_t iv = list[blockIdx.x];
     if (dp_takes_wide(nseq, iv, seq_off, sc, band_from, wide)) return;
-    dp_interval_mw(nseq, iv, codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, sc, band_from);
+    dp_interval_mw(nseq, iv, B, band_from);
 }
 template <int R, int W>
 __global__ void __launch_bounds__(64 * W) dp_step_wide(int nseq, const int64_t *__restrict__ list, const uint8_t *__restrict__ codes,
@@ -1834,6 +1802,7 @@ __global__ void __launch_bounds__(64 * W) dp_step_wide(int nseq, const int64_t *
                                                int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
                                                uint8_t *__restrict__ ops, DpScoring sc, int64_t band_from, int K, unsigned long long *__restrict__ flags)
 {
+    const DpBufs B = { codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, sc };
     // K > 1: K consecutive workgroups share list entry blockIdx.x / K (a cluster); a workgroup that can never hold a super-band of this interval -- no
     // profile and no sequence of it can be longer than all its sequences together -- leaves at once
     const uint32_t entry = K > 1 ? blockIdx.x / (uint32_t)K : blockIdx.x;
@@ -1847,7 +1816,7 @@ __global__ void __launch_bounds__(64 * W) dp_step_wide(int nseq, const int64_t *
         if (c >= kk) return;
         CL.K = kk; CL.c = c; CL.flags = flags + (size_t)entry * DPW_FLAGS;
     }
-    dp_interval_wide<R, W>(nseq, iv, codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, sc, CL);
+    dp_interval_wide<R, W>(nseq, iv, B, CL);
 }
 
 // The register-blocked launch: block ranges [one wave per interval | G = 16 | G = 8 | G = 4], the long ones first.
@@ -1859,6 +1828,7 @@ __global__ void __launch_bounds__(64 * DP2_WAVES) dp_step2(int nseq, const int64
                                                int32_t *__restrict__ rows, const int64_t *__restrict__ rows_off,
                                                uint8_t *__restrict__ ops, DpScoring sc)
 {
+    const DpBufs B = { codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, sc };
     __shared__ __attribute__((aligned(16))) uint32_t s_tb[DP2_WAVES][DP2_TB_DW];
     __shared__ uint16_t s_rec[DP2_WAVES][DP2_REC];
     __shared__ uint8_t s_seq[DP2_WAVES][DP2_SEQ];
@@ -1871,9 +1841,9 @@ __global__ void __launch_bounds__(64 * DP2_WAVES) dp_step2(int nseq, const int64
         else if (b < cl.blocks_c + cl.blocks_s32) { k = 1; b -= cl.blocks_c; nb = cl.blocks_s32; first = cl.first_s32; count = cl.n_s32; }
         else { k = 2; b -= cl.blocks_c + cl.blocks_s32; nb = gridDim.x - cl.blocks_med - cl.blocks_c - cl.blocks_s32; first = cl.first_s16; count = cl.n_s16; }
         const int64_t widx = (int64_t)b * DP2_WAVES + wv, nw = (int64_t)nb * DP2_WAVES;
-        if (k == 0) dp2_groups<16>(nseq, list, first, count, widx, nw, codes, seq_off, meta, cntA, maskA, cntB, maskB, s_tb[wv], s_rec[wv], s_seq[wv], sc);
-        else if (k == 1) dp2_groups<8>(nseq, list, first, count, widx, nw, codes, seq_off, meta, cntA, maskA, cntB, maskB, s_tb[wv], s_rec[wv], s_seq[wv], sc);
-        else dp2_groups<4>(nseq, list, first, count, widx, nw, codes, seq_off, meta, cntA, maskA, cntB, maskB, s_tb[wv], s_rec[wv], s_seq[wv], sc);
+        if (k == 0) dp2_groups<16>(nseq, list, first, count, widx, nw, B, s_tb[wv], s_rec[wv], s_seq[wv]);
+        else if (k == 1) dp2_groups<8>(nseq, list, first, count, widx, nw, B, s_tb[wv], s_rec[wv], s_seq[wv]);
+        else dp2_groups<4>(nseq, list, first, count, widx, nw, B, s_tb[wv], s_rec[wv], s_seq[wv]);
         // second look at this wave's own list positions: what a group gave up is aligned below, one interval per wave
         per = k == 0 ? 4 : (k == 1 ? 8 : 16); only_failed = true;
         pos0 = first + widx * per; pstep = nw * per; pend = first + count;
@@ -1888,8 +1858,8 @@ __global__ void __launch_bounds__(64 * DP2_WAVES) dp_step2(int nseq, const int64
             if (only_failed && meta[iv].m != -1) continue;
             // column / row scans where 32-bit prefix sums are exact (always, for real scoring schemes); else the anti-diagonal sweep
             const bool scan = cl.scan && dp3_admissible(seq_off[(iv + 1) * nseq] - seq_off[iv * nseq], nseq, sc.ge, sc.go);
-            if (scan) dp3_interval(nseq, iv, codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, reinterpret_cast<uint8_t *>(s_tb[wv]), sc);
-            else dp2_interval(nseq, iv, codes, seq_off, meta, cntA, maskA, cntB, maskB, tb, tb_off, rows, rows_off, ops, reinterpret_cast<uint8_t *>(s_tb[wv]), sc);
+            if (scan) dp3_interval(nseq, iv, B, reinterpret_cast<uint8_t *>(s_tb[wv]));
+            else dp2_interval(nseq, iv, B, reinterpret_cast<uint8_t *>(s_tb[wv]));
         }
 }
 
@@ -2072,7 +2042,7 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
     const uint32_t blocks = cl.blocks_med + cl.blocks_c + cl.blocks_s32 + (uint32_t)std::min<int64_t>((cl.n_s16 + 16 * wpb - 1) / (16 * wpb), cap);
     uint8_t *tb = ctx->dp_tb.as<uint8_t>() - tb_base;                   // only offsets >= tb_base are used in this round
     KernelTimer t(ctx, MAUVE_K_DP, b - a);                              // (the profile calls this timer "dp_step": it names the stage, all launches below)
-    // what every DP kernel takes behind its list: the bases, the per-interval records, both profile buffers, traceback, parked rows, reversed ops, scores
+    // what every DP kernel takes behind its list (DpBufs, in its order)
 #define DP_STEP_ARGS ctx->dp_codes.as<uint8_t>(), d_seq_off, ctx->dp_meta.as<DpMeta>(), ctx->dp_prof_cnt.as<uint32_t>(), ctx->dp_prof_mask.as<uint32_t>(), \
                      ctx->dp_prof2_cnt.as<uint32_t>(), ctx->dp_prof2_mask.as<uint32_t>(), tb, d_tb_off, ctx->dp_rows.as<int32_t>(), d_rows_off, \
                      ctx->dp_score.as<uint8_t>(), sc
@@ -2086,9 +2056,8 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
         HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
         const bool wide = dp_wide_on();
-        // 8 waves x 4 rows per lane; MAUVE_DP_WIDE_R2: 16 waves x 2 rows per lane (A/B: the same time per line -- the sweep is bound by vector issue, not by the
-        // number of waves -- and the 128-register budget of a 1024-thread workgroup makes it spill)
-        static const bool r4 = getenv("MAUVE_DP_WIDE_R2") == nullptr;
+        // the wide sweep runs 8 waves x 4 rows per lane (16 waves x 2 rows took the same time per line -- the sweep is bound by vector issue, not by the
+        // number of waves -- and the 128-register budget of a 1024-thread workgroup made it spill: it is no longer built)
         // the first entries of the list (the largest intervals) get a CLUSTER of up to DPW_KMAX workgroups each (dp_interval_wide); few enough that all
         // of them are resident at once beside the rest.  MAUVE_DP_CLUSTER=0: off (A/B), =n: that many entries
         static const int64_t cl_max = getenv("MAUVE_DP_CLUSTER") ? atoll(getenv("MAUVE_DP_CLUSTER")) : 32;
@@ -2099,10 +2068,9 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
             HIPCHK(ctx, hipMemsetAsync(ctx->dp_wflags.p, 0, (size_t)n_cl * DPW_FLAGS * 8, ctx->stream));
             flags = ctx->dp_wflags.as<unsigned long long>();
         }
-#define DPW_LAUNCH(RR, WW, first, count, K) hipLaunchKernelGGL((dp_step_wide<RR, WW>), dim3((uint32_t)((count) * (K))), dim3(64 * WW), 0, ctx->stream, nseq, \
+#define DPW_LAUNCH(first, count, K) hipLaunchKernelGGL((dp_step_wide<4, 8>), dim3((uint32_t)((count) * (K))), dim3(64 * 8), 0, ctx->stream, nseq, \
                                ctx->dp_list.as<int64_t>() + bf + (first), DP_STEP_ARGS, band_from, (int)(K), flags)
-        if (wide && r4) { if (n_cl) DPW_LAUNCH(4, 8, 0, n_cl, DPW_KMAX); if (bn > n_cl) DPW_LAUNCH(4, 8, n_cl, bn - n_cl, 1); }
-        else if (wide) { if (n_cl) DPW_LAUNCH(2, 16, 0, n_cl, DPW_KMAX); if (bn > n_cl) DPW_LAUNCH(2, 16, n_cl, bn - n_cl, 1); }
+        if (wide) { if (n_cl) DPW_LAUNCH(0, n_cl, DPW_KMAX); if (bn > n_cl) DPW_LAUNCH(n_cl, bn - n_cl, 1); }
 #undef DPW_LAUNCH
         // (the stripe pipeline: every entry without the wide sweep; with it, only where banded intervals or an inadmissible scoring scheme can occur)
         if (!wide || band_from != INT64_MAX || !dp3_admissible(1, nseq, sc.ge, sc.go))
