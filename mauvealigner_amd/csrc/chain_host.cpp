@@ -620,3 +620,53 @@ int mauve_lcb_chain(int nseq, int64_t n, const int64_t *length, const int64_t *s
 }
 
 }  // extern "C"
+
+// ---- steps the align path (pipeline.cpp) and the progressive path (progressive.cpp) share ----
+int resolve_seed(mauve_ctx *c, const mauve_params *p, int64_t avg_len, const char *who, int *w, uint64_t *pat)
+{
+    const int w0 = p->seed_weight > 0 ? p->seed_weight : mauve_default_seed_weight(avg_len);
+    if (!pat) { *w = p->seed_pattern ? mauve_seed_weight(p->seed_pattern) : w0; return MAUVE_OK; }
+    *pat = p->seed_pattern ? p->seed_pattern : mauve_get_seed(w0, p->seed_rank);
+    if (!*pat) { c->err = std::string(who) + ": no seed pattern for this weight/rank"; return MAUVE_ERR_ARG; }
+    *w = mauve_seed_weight(*pat);
+    return MAUVE_OK;
+}
+
+void seed_matches_to_vec(const mauve_ctx *c, int n, int64_t nm, MatchVec &m)
+{
+    m.N = n; m.resize((size_t)nm);
+    for (int64_t i = 0; i < nm; i++) {
+        m.len((size_t)i) = c->match_len[(size_t)i];
+        std::copy(&c->match_start[(size_t)i * n], &c->match_start[(size_t)i * n] + n, m.st((size_t)i));
+    }
+}
+
+int host_chain_lcbs(mauve_ctx *c, const mauve_params *p, MatchVec &m, const int *gmap, int64_t lcbw, int64_t minw_sp, std::vector<int64_t> &match_lcb,
+                    int64_t &nl, std::vector<int64_t> *match_weight, bool compact, double *t_elim)
+{
+    ChainOrders orders;
+    host_eliminate_overlaps(m, &orders, compact);
+    if (t_elim) *t_elim = now_ms();
+    const bool sp = p->lcb_scoring == MAUVE_LCB_SCORE_SP;    // LCB weight = sum-of-pairs score of its anchors
+    std::vector<int64_t> mw;
+    if (sp) { const int rc = match_sp_scores(c, m, gmap, &p->scoring, mw); if (rc) return rc; }
+    host_lcb_chain(m, sp ? minw_sp : lcbw, p->collinear != 0, match_lcb, nl, &orders, sp ? mw.data() : nullptr);
+    if (match_weight) match_weight->swap(mw);
+    return MAUVE_OK;
+}
+
+void result_reset(AlignResult &R)
+{
+    R.sz = mauve_align_sizes();
+    R.mum_length.clear(); R.mum_start.clear(); R.lcb_left.clear(); R.lcb_right.clear(); R.lcb_weight.clear();
+    R.anchor_length.clear(); R.anchor_start.clear(); R.anchor_lcb.clear(); R.iv_left.clear(); R.iv_right.clear();
+    R.iv_reverse.clear(); R.col_off.clear(); R.n_cols = 0; R.dp_score.clear();
+    R.dev_pending = false; R.cols_pending = false; R.stale = false; R.genomes_replaced = false; R.dev_na = 0; R.dev_nm = 0; R.cols_ext = nullptr;
+}
+
+void restore_cols(AlignResult &R, uint32_t full, SpinPool *pool)
+{
+    auto run = [&](int64_t b, int64_t e) { for (int64_t i = b; i < e; i++) std::fill_n(R.cols.begin() + R.cols_dirty[(size_t)i].first, R.cols_dirty[(size_t)i].second, full); };
+    if (pool) pool->parallel_for((int64_t)R.cols_dirty.size(), 1024, run); else run(0, (int64_t)R.cols_dirty.size());
+    R.cols_dirty.clear();
+}

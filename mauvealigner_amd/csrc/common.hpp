@@ -8,6 +8,7 @@
 #include <vector>
 #include <functional>
 #include "workers.hpp"
+#include "host_chain.hpp"
 #include <chrono>
 #include <algorithm>
 
@@ -157,30 +158,9 @@ struct AlignResult {
     const uint32_t *cols_data() const { return cols_ext ? cols_ext : cols.data(); }
 };
 
-// N-way match list in flat records of (1 + N) int64: length, signed 1-based starts (libMems Match layout).
-struct MatchVec {
-    int N = 0;
-    std::vector<int64_t> d;
-    explicit MatchVec(int n = 0) : N(n) {}
-    size_t size() const { return d.size() / (size_t)(1 + N); }
-    bool empty() const { return d.empty(); }
-    int64_t &len(size_t i) { return d[i * (1 + N)]; }
-    int64_t len(size_t i) const { return d[i * (1 + N)]; }
-    int64_t *st(size_t i) { return &d[i * (1 + N) + 1]; }
-    const int64_t *st(size_t i) const { return &d[i * (1 + N) + 1]; }
-    const int64_t *rec(size_t i) const { return &d[i * (1 + N)]; }
-    void push(const int64_t *r) { d.insert(d.end(), r, r + 1 + N); }
-    void push(int64_t l, const int64_t *starts) { d.push_back(l); d.insert(d.end(), starts, starts + N); }
-    void resize(size_t n) { d.resize(n * (1 + N)); }
-    void move(size_t dst, size_t src) { if (dst != src) std::copy(d.begin() + src * (1 + N), d.begin() + (src + 1) * (1 + N), d.begin() + dst * (1 + N)); }
-    void reserve(size_t n) { d.reserve(n * (1 + N)); }
-    void sort_by_start0();
-};
-struct DpSeqDesc { int32_t genome; int32_t rev; int64_t lo0; int64_t len; };   // lo0: 0-based left end in the genome
-
 // state of an alignment between its begin and finish phases (pipeline.cpp)
 struct AlignState {
-    struct GapRef { int64_t lcb, idx; bool dp; int64_t dp_slot; int64_t tot; };
+    typedef ::GapRef GapRef;
     struct Item { int64_t lcb; uint32_t idx; int64_t col0; int64_t gap; };
     bool open = false;
     bool anchor_table_done = false;     // anchor_length/start/lcb already filled (in the DP kernel's shadow)
@@ -202,6 +182,7 @@ struct AlignState {
     std::vector<int64_t> match_lcb;
     std::vector<int64_t> match_weight;  // sum-of-pairs scores of the matches (lcb_scoring = SP), else empty
     std::vector<Item> items;
+    void count_anchors() { for (const MatchVec &ch : chains) { n_anchor += (int64_t)ch.size(); for (size_t i = 0; i < ch.size(); i++) anchor_cols += ch.len(i); } }
     // start a new alignment: scalars to zero, vectors emptied but not released
     void reset()
     {
@@ -497,6 +478,16 @@ int repeat_multiplicity(mauve_ctx *c, uint64_t pattern);
 // under sum-of-pairs LCB scoring (pipeline.cpp)
 int repeat_begin(mauve_ctx *c, const mauve_params *p, int w, uint64_t pat);
 int64_t sp_default_min_weight(int w, int n, const mauve_scoring *sc);
+// the steps the align path and the progressive path share (chain_host.cpp; the pure ones: host_chain.hpp)
+// seed weight and pattern of a call over genomes of average length avg_len; pat == nullptr: the weight alone, which never fails
+int resolve_seed(mauve_ctx *c, const mauve_params *p, int64_t avg_len, const char *who, int *w, uint64_t *pat);
+void seed_matches_to_vec(const mauve_ctx *c, int n, int64_t nm, MatchVec &m);      // the seed pass's host list (match_len / match_start) as records
+// host chain of a list: overlap elimination, sum-of-pairs scores when p->lcb_scoring asks for them (minimum weight minw_sp, the scores
+// left in *match_weight when given), LCBs; lcbw: the minimum weight of length-weighted LCBs; *t_elim: when the elimination was done
+int host_chain_lcbs(mauve_ctx *c, const mauve_params *p, MatchVec &m, const int *gmap, int64_t lcbw, int64_t minw_sp, std::vector<int64_t> &match_lcb,
+                    int64_t &nl, std::vector<int64_t> *match_weight, bool compact, double *t_elim = nullptr);
+void result_reset(AlignResult &R);       // a new result: tables emptied, the column buffer and its fill state kept
+void restore_cols(AlignResult &R, uint32_t full, SpinPool *pool = nullptr);        // the gap ranges of the last result back to `full`
 
 void lcb_greedy(int N, int32_t K, int64_t *weight, const uint32_t *orient_bits, int32_t *prevv, int32_t *nextv, int64_t min_weight,
                 bool collinear, std::vector<int64_t> &final_id, int64_t &n_lcb);

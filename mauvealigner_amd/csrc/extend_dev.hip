@@ -175,7 +175,7 @@ int extend_lcbs_device(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
     const double t0 = now_ms();
     const uint32_t na = (uint32_t)*na_io; const int64_t nl0 = *nl_io;
     const int32_t *alen = *alen_io, *ast = *ast_io, *alcb = *alcb_io;
-    const uint32_t full = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
+    const uint32_t full = full_mask(N);
     // ---- the LCB table: extents from the first / last anchor of every LCB, weights as chain_order_device summed them ----
     LcbTab T; T.N = N; T.n = nl0;
     {
@@ -298,19 +298,7 @@ int extend_lcbs_device(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
                 ext.st((size_t)i)[g] = s < 0 ? -real : real;
             }
         }
-        {   // canonical order (N-way records: |start 0|, starts, length), then the elimination among the new matches
-            std::vector<size_t> idx(ext.size());
-            for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
-            std::sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-                const int64_t *a = ext.rec(x), *b = ext.rec(y);
-                const int64_t sa = std::llabs(a[1]), sb = std::llabs(b[1]);
-                if (sa != sb) return sa < sb;
-                for (int g = 0; g < N; g++) if (a[1 + g] != b[1 + g]) return a[1 + g] < b[1 + g];
-                return a[0] < b[0];
-            });
-            MatchVec t(N); for (size_t i : idx) t.push(ext.rec(i));
-            ext.d.swap(t.d);
-        }
+        canon_sort(ext);                   // canonical order (N-way records: |start 0|, starts, length), then the elimination among the new matches
         host_eliminate_overlaps(ext);
         // ---- re-chain the units: old LCBs (weights as match weights) + new matches ----
         const size_t nu = (size_t)T.n + ext.size();

@@ -15,16 +15,6 @@ namespace {
 
 inline uint8_t base_at(const uint64_t *w, int64_t i) { return (uint8_t)((w[(size_t)(i >> 5)] >> (2 * (i & 31))) & 3); }
 
-// inter-anchor interval of genome g between anchors a (left in genome-0 order) and b, LCB orientation
-inline void gap_of(const int64_t *a, const int64_t *b, int g, int64_t &lo, int64_t &len, bool &rev)
-{
-    const int64_t sa = a[1 + g], sb = b[1 + g];
-    int64_t hi;
-    if (sa > 0) { lo = sa + a[0]; hi = sb - 1; rev = false; }
-    else { lo = -sb + b[0]; hi = -sa - 1; rev = true; }
-    len = hi - lo + 1; if (len < 0) len = 0;
-}
-
 }  // namespace
 
 int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector<MatchVec> &chains, int N, const int *gmap);
@@ -38,7 +28,7 @@ static int extend_lcbs(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
                        int64_t &nl)
 {
     const int N = m.N;
-    const uint32_t full = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
+    const uint32_t full = full_mask(N);
     int w_e = w;
     MatchVec base(N); ChainOrders base_ord; bool have_base = false;         // the surviving anchors and their per-genome orders
     for (int iter = 0; iter < p->max_extension_iters; iter++) {
@@ -81,12 +71,7 @@ static int extend_lcbs(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
                 const int64_t vlo = cur, vhi = l < nl ? sp[(size_t)l].first - 1 : c->lens[g];
                 if (vhi - vlo + 1 >= span_e) {
                     any = true;
-                    for (int64_t b = vlo - 1; b < vhi;) {               // clear [vlo-1, vhi) word-wise
-                        const int64_t wd = b >> 6, e = std::min<int64_t>(vhi, (wd + 1) << 6);
-                        const int n = (int)(e - b), sh = (int)(b & 63);
-                        M[wd] &= ~((n == 64 ? ~0ULL : ((1ULL << n) - 1ULL)) << sh);
-                        b = e;
-                    }
+                    clear_bits(M, vlo, vhi);
                 }
                 if (l < nl && sp[(size_t)l].second + 1 > cur) cur = sp[(size_t)l].second + 1;
             }
@@ -105,17 +90,9 @@ static int extend_lcbs(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
         if (nx == 0) continue;
         const double tr2 = now_ms();
         // survivors + new matches, canonical order (both lists already are: merge)
-        auto less = [N](const int64_t *a, const int64_t *b) {                // N-way records: |start0|, starts, length
-            const int64_t sa = std::llabs(a[1]), sb = std::llabs(b[1]);
-            if (sa != sb) return sa < sb;
-            for (int g = 0; g < N; g++) if (a[1 + g] != b[1 + g]) return a[1 + g] < b[1 + g];
-            return a[0] < b[0];
-        };
-        MatchVec ext(N); ext.resize((size_t)nx);
-        for (int64_t i = 0; i < nx; i++) {
-            ext.len((size_t)i) = c->match_len[(size_t)i];
-            std::copy(&c->match_start[(size_t)i * N], &c->match_start[(size_t)i * N] + N, ext.st((size_t)i));
-        }
+        const auto less = canon_less(N);
+        MatchVec ext(N);
+        seed_matches_to_vec(c, N, nx, ext);
         // The new matches lie outside every LCB extent in every genome, the surviving anchors inside: a new match can
         // only overlap another new one.  Overlap elimination of the merged list is therefore the elimination among the
         // new matches alone (a handful) next to the untouched anchors, and the per-genome orders of the merged list
@@ -125,17 +102,7 @@ static int extend_lcbs(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
             for (size_t i = 0; i < m.size(); i++) if (match_lcb[i] >= 0) base.push(m.rec(i));
             // Crops of the overlap elimination can carry a match past a neighbour (dense, overlapping lists: seed families):
             // the merged list of a round is in canonical order of the CURRENT records, so the anchors are put in that order first
-            {
-                std::vector<size_t> idx(base.size());
-                for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
-                auto by = [&](size_t x, size_t y) { return less(base.rec(x), base.rec(y)); };
-                if (!std::is_sorted(idx.begin(), idx.end(), by)) {
-                    std::stable_sort(idx.begin(), idx.end(), by);
-                    MatchVec t(N); t.reserve(base.size());
-                    for (size_t i : idx) t.push(base.rec(i));
-                    base.d.swap(t.d);
-                }
-            }
+            canon_sort(base);
             host_left_orders(base, base_ord);
             have_base = true;
         }
@@ -232,11 +199,8 @@ int seed_family_matches(mauve_ctx *c, const GenomeSet &gs, int w, int mode, uint
         const int rc = seedpass_run(c, gs, pat, mode, mask, 1, nullptr, 0, &nm);
         if (rc) return rc;
         static thread_local MatchVec cur_keep(1);                  // (kept from call to call: no fresh megabytes and their page faults per search)
-        MatchVec &cur = cur_keep; cur.N = n; cur.d.clear(); cur.resize((size_t)nm);
-        for (int64_t i = 0; i < nm; i++) {
-            cur.len((size_t)i) = c->match_len[(size_t)i];
-            std::copy(&c->match_start[(size_t)i * n], &c->match_start[(size_t)i * n] + n, cur.st((size_t)i));
-        }
+        MatchVec &cur = cur_keep; cur.d.clear();
+        seed_matches_to_vec(c, n, nm, cur);
         const double tm0 = now_ms();
         if (k == 0) out.d.swap(cur.d); else host_merge_matches(out, cur);
         static const bool trace = getenv("MAUVE_TRACE") != nullptr;
@@ -280,20 +244,14 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     AlignResult &R = c->res;
     // keep the capacity of the result vectors across calls (a fresh 20 MB column buffer per call costs more in
     // page faults than the whole seed pass)
-    R.sz = mauve_align_sizes();
-    R.mum_length.clear(); R.mum_start.clear(); R.lcb_left.clear(); R.lcb_right.clear(); R.lcb_weight.clear();
-    R.anchor_length.clear(); R.anchor_start.clear(); R.anchor_lcb.clear(); R.iv_left.clear(); R.iv_right.clear();
-    R.iv_reverse.clear(); R.col_off.clear(); R.n_cols = 0; R.dp_score.clear();
-    R.dev_pending = false; R.cols_pending = false; R.stale = false; R.genomes_replaced = false; R.dev_na = 0; R.dev_nm = 0; R.cols_ext = nullptr;
+    result_reset(R);
     memset(&c->stage, 0, sizeof c->stage);
 
     int64_t sum = 0; for (int g = 0; g < N; g++) sum += c->lens[g];
     S.sum = sum;
-    int w = p->seed_weight > 0 ? p->seed_weight : mauve_default_seed_weight(sum / N);
-    uint64_t pat = p->seed_pattern ? p->seed_pattern : mauve_get_seed(w, p->seed_rank);
-    if (!pat) { c->err = "align: no seed pattern for this weight/rank"; return MAUVE_ERR_ARG; }
-    w = mauve_seed_weight(pat);
-    const uint32_t full = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
+    int w; uint64_t pat;
+    { const int rs = resolve_seed(c, p, sum / N, "align", &w, &pat); if (rs) return rs; }
+    const uint32_t full = full_mask(N);
     S.full = full;
     RepeatScope rp_scope(c);                         // the anchor scores of this call's LCBs
     { const int rr = repeat_begin(c, p, w, pat); if (rr) return rr; }
@@ -303,11 +261,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     // "all anchors" state, i.e. undo the gap ranges the previous call wrote (see align_finish).
     static const bool no_shadow = getenv("MAUVE_NO_SHADOW") != nullptr;        // A/B switch
     if (R.cols_fill == full && !R.cols_dirty.empty() && !no_shadow)
-        c->shadow = [c, full]() {
-            AlignResult &Rr = c->res;
-            for (const auto &d : Rr.cols_dirty) std::fill(Rr.cols.begin() + d.first, Rr.cols.begin() + d.first + d.second, full);
-            Rr.cols_dirty.clear();
-        };
+        c->shadow = [c, full]() { restore_cols(c->res, full); };
     int64_t nm = 0;
     int rc = MAUVE_OK;
     // LCB extension without taking the chains off the device (extend_dev.hip): plain genomes, length-weighted LCBs.  MAUVE_HOST_EXTEND: A/B switch
@@ -331,23 +285,17 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     if (given) {
         // the caller's list: its N-way matches in canonical order (|start 0|, starts, length) stand where the seed pass's stood
         c->shadow = nullptr;
-        if (R.cols_fill == full && !R.cols_dirty.empty()) {
-            for (const auto &d : R.cols_dirty) std::fill(R.cols.begin() + d.first, R.cols.begin() + d.first + d.second, full);
-            R.cols_dirty.clear();
-        }
+        if (R.cols_fill == full && !R.cols_dirty.empty()) restore_cols(R, full);
         std::vector<size_t> keep;
         for (size_t i = 0; i < given->size(); i++) {
             bool nway = given->len(i) > 0;
             for (int g = 0; g < N && nway; g++) nway = given->st(i)[g] != 0;
             if (nway) keep.push_back(i);
         }
-        auto canon = [&](size_t a, size_t b) {
+        const auto less = canon_less(N);
+        auto canon = [&](size_t a, size_t b) {                   // (std::sort is not stable: the index decides equal records)
             const int64_t *x = given->rec(a), *y = given->rec(b);
-            const int64_t sa = std::llabs(x[1]), sb = std::llabs(y[1]);
-            if (sa != sb) return sa < sb;
-            for (int g = 0; g < N; g++) if (x[1 + g] != y[1 + g]) return x[1 + g] < y[1 + g];
-            if (x[0] != y[0]) return x[0] < y[0];
-            return a < b;
+            return less(x, y) || (!less(y, x) && a < b);
         };
         if (!std::is_sorted(keep.begin(), keep.end(), canon)) std::sort(keep.begin(), keep.end(), canon);     // a merged family list comes in order
         nm = (int64_t)keep.size();
@@ -494,24 +442,11 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
         R.mum_length = c->match_len; R.mum_start = c->match_start;
     }
     if (!on_device) {
-        m.resize((size_t)nm);
-        for (int64_t i = 0; i < nm; i++) {
-            m.len((size_t)i) = c->match_len[(size_t)i];
-            std::copy(&c->match_start[(size_t)i * N], &c->match_start[(size_t)i * N] + N, m.st((size_t)i));
-        }
-        ChainOrders orders;
-        static const bool elim_compact = getenv("MAUVE_ELIM_COMPACT") != nullptr;       // A/B switch
-        host_eliminate_overlaps(m, &orders, elim_compact);           // default: dead records stay in m, with lcb -1 below
-        t1b = now_ms();
-        if (p->lcb_scoring == MAUVE_LCB_SCORE_SP) {              // LCB weight = sum-of-pairs score of its anchors
-            std::vector<int64_t> mw;
-            rc = match_sp_scores(c, m, nullptr, &p->scoring, mw);
-            if (rc) return rc;
-            const int64_t minw = p->lcb_weight >= 0 ? p->lcb_weight : sp_default_min_weight(w, N, &p->scoring);
-            host_lcb_chain(m, minw, p->collinear != 0, match_lcb, nl, &orders, mw.data());
-            S.match_weight.swap(mw);
-        } else
-        host_lcb_chain(m, lcbw, p->collinear != 0, match_lcb, nl, &orders);
+        seed_matches_to_vec(c, N, nm, m);
+        static const bool elim_compact = getenv("MAUVE_ELIM_COMPACT") != nullptr;       // A/B switch; default: dead records stay in m, with lcb -1 below
+        const int64_t minw_sp = p->lcb_weight >= 0 ? p->lcb_weight : sp_default_min_weight(w, N, &p->scoring);
+        rc = host_chain_lcbs(c, p, m, nullptr, lcbw, minw_sp, match_lcb, nl, &S.match_weight, elim_compact, &t1b);
+        if (rc) return rc;
     }
     if (do_extend && !chains_ready) {
         rc = extend_lcbs(c, p, w, lcbw, m, match_lcb, nl);
@@ -544,38 +479,9 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     // ---- inter-anchor intervals.  Descriptors only: the bases are gathered from the resident packed genomes on
     // the device. ----
     S.gaps.reserve((size_t)R.mum_length.size() + 16);
-    if (device_front) {              // mauve_align: the interval table is made on the device (dp_run_from_anchors)
-        for (int64_t l = 0; l < nl; l++) {
-            const MatchVec &ch = chains[(size_t)l];
-            S.n_anchor += (int64_t)ch.size();
-            for (size_t i = 0; i < ch.size(); i++) S.anchor_cols += ch.len(i);
-        }
-    } else
-    for (int64_t l = 0; l < nl; l++) {
-        const MatchVec &ch = chains[(size_t)l];
-        S.n_anchor += (int64_t)ch.size();
-        for (size_t i = 0; i < ch.size(); i++) {
-            S.anchor_cols += ch.len(i);
-            if (i + 1 == ch.size()) break;
-            int64_t tot = 0, mx = 0; int nonempty = 0;
-            int64_t lo[MAUVE_MAX_SEQ], ln[MAUVE_MAX_SEQ]; bool rv[MAUVE_MAX_SEQ];
-            for (int g = 0; g < N; g++) {
-                gap_of(ch.rec(i), ch.rec(i + 1), g, lo[g], ln[g], rv[g]);
-                tot += ln[g]; mx = std::max(mx, ln[g]); nonempty += ln[g] > 0;
-            }
-            if (tot == 0) continue;
-            AlignState::GapRef gr; gr.lcb = l; gr.idx = (int64_t)i; gr.dp = false; gr.dp_slot = -1; gr.tot = tot;
-            if (p->gapped && nonempty >= 2 && mx <= dp_len_limit(p)) {
-                gr.dp = true; gr.dp_slot = S.n_dp++;
-                for (int g = 0; g < N; g++) {
-                    DpSeqDesc d; d.genome = g; d.rev = rv[g]; d.lo0 = lo[g] - 1; d.len = ln[g];
-                    S.desc.push_back(d);
-                }
-                S.code_total += tot;
-            }
-            S.gaps.push_back(gr);
-        }
-    }
+    S.count_anchors();
+    // (mauve_align, device_front: the interval table is made on the device, dp_run_from_anchors)
+    if (!device_front) host_gap_table(chains, N, nullptr, p->gapped, dp_len_limit(p), S.gaps, S.desc, S.n_dp, S.code_total);
     S.t_dp0 = now_ms();
     if (g_trace_pipeline) fprintf(stderr, "[trace] interval table: %.3f ms (%lld gaps, %lld dp)\n", S.t_dp0 - t3, (long long)S.gaps.size(), (long long)S.n_dp);
     S.open = true;
@@ -644,7 +550,7 @@ static int align_finish(mauve_ctx *c, const uint32_t *dcols, const int64_t *dcol
                 Item it; it.lcb = l; it.idx = (uint32_t)i; it.col0 = col; it.gap = -1;
                 col += ch.len(i);
                 if (gi < S.gaps.size() && S.gaps[gi].lcb == l && S.gaps[gi].idx == (int64_t)i) {
-                    const AlignState::GapRef &gr = S.gaps[gi];
+                    const GapRef &gr = S.gaps[gi];
                     it.gap = (int64_t)gi++;
                     if (gr.dp) { col += dcol_off[(size_t)gr.dp_slot + 1] - dcol_off[(size_t)gr.dp_slot]; R.dp_score[(size_t)l] += dscore[(size_t)gr.dp_slot]; }
                     else col += gr.tot;
@@ -652,17 +558,13 @@ static int align_finish(mauve_ctx *c, const uint32_t *dcols, const int64_t *dcol
                 items[ai++] = it;
             }
             // LCB extent: anchors are ordered, so the ends come from the first and last anchor
-            if (ch.size()) {
-                const size_t last = ch.size() - 1;
+            if (ch.size())
                 for (int g = 0; g < N; g++) {
-                    const int64_t s0 = ch.st(0)[g], s1 = ch.st(last)[g];
-                    int64_t le, re;
-                    if (s0 > 0) { le = s0; re = s1 + ch.len(last) - 1; }
-                    else { le = -s1; re = -s0 + ch.len(0) - 1; }
-                    R.lcb_left[(size_t)l * N + g] = s0 < 0 ? -le : le;
-                    R.lcb_right[(size_t)l * N + g] = s0 < 0 ? -re : re;
+                    int64_t le, re; bool rv;
+                    chain_extent(ch, g, le, re, rv);
+                    R.lcb_left[(size_t)l * N + g] = rv ? -le : le;
+                    R.lcb_right[(size_t)l * N + g] = rv ? -re : re;
                 }
-            }
         }
     }
     const double ta1 = now_ms();
@@ -674,15 +576,8 @@ static int align_finish(mauve_ctx *c, const uint32_t *dcols, const int64_t *dcol
         if (R.cols.size() < need) R.cols.resize(need);
         std::fill(R.cols.begin(), R.cols.end(), full);
         R.cols_fill = full; R.cols_dirty.clear();
-    } else {
-        c->pool->parallel_for((int64_t)R.cols_dirty.size(), 1024, [&](int64_t b, int64_t e) {
-            for (int64_t i = b; i < e; i++) {
-                const auto &d = R.cols_dirty[(size_t)i];
-                std::fill(R.cols.begin() + d.first, R.cols.begin() + d.first + d.second, full);
-            }
-        });
-        R.cols_dirty.clear();
-    }
+    } else
+        restore_cols(R, full, c->pool);
     const double ta2 = now_ms();
     if (!S.anchor_table_done) fill_anchor_table(c);
     // pass 2: every anchor writes its record and the stretch that follows it (independent writes, run on the host
@@ -697,13 +592,13 @@ static int align_finish(mauve_ctx *c, const uint32_t *dcols, const int64_t *dcol
                 const int64_t alen = ch.len(it.idx);
                 uint32_t *o = out + it.col0 + alen;            // the anchor's own columns already hold `full`
                 if (it.gap >= 0) {
-                    const AlignState::GapRef &gr = S.gaps[(size_t)it.gap];
+                    const GapRef &gr = S.gaps[(size_t)it.gap];
                     const size_t glen = (size_t)(gr.dp ? dcol_off[(size_t)gr.dp_slot + 1] - dcol_off[(size_t)gr.dp_slot] : gr.tot);
                     R.cols_dirty[(size_t)a] = {(size_t)(o - out), glen};
                     if (gr.dp) std::copy(dcols + dcol_off[(size_t)gr.dp_slot], dcols + dcol_off[(size_t)gr.dp_slot + 1], o);
                     else for (int g = 0; g < N; g++) {
-                        int64_t lo, ln; bool rv;
-                        gap_of(ch.rec(it.idx), ch.rec(it.idx + 1), g, lo, ln, rv);
+                        int64_t lo, ln;
+                        gap_of(ch.rec(it.idx), ch.rec(it.idx + 1), g, lo, ln);
                         std::fill(o, o + ln, 1u << g); o += ln;
                     }
                 }
@@ -765,18 +660,14 @@ static int align_begin_lcbs(mauve_ctx *c, const mauve_params *p, std::vector<Mat
     c->rec_flags.clear();                 // flags of an earlier call that ended before its recursion must not be taken for this one's
     S.p = *p; S.N = N; S.t0 = now_ms();
     AlignResult &R = c->res;
-    R.sz = mauve_align_sizes();
-    R.mum_length.clear(); R.mum_start.clear(); R.lcb_left.clear(); R.lcb_right.clear(); R.lcb_weight.clear();
-    R.anchor_length.clear(); R.anchor_start.clear(); R.anchor_lcb.clear(); R.iv_left.clear(); R.iv_right.clear();
-    R.iv_reverse.clear(); R.col_off.clear(); R.n_cols = 0; R.dp_score.clear();
-    R.dev_pending = false; R.cols_pending = false; R.stale = false; R.genomes_replaced = false; R.dev_na = 0; R.dev_nm = 0; R.cols_ext = nullptr;
+    result_reset(R);
     memset(&c->stage, 0, sizeof c->stage);
     c->shadow = nullptr;
     int64_t sum = 0; for (int g = 0; g < N; g++) sum += c->lens[g];
     S.sum = sum;
-    int w = p->seed_weight > 0 ? p->seed_weight : mauve_default_seed_weight(sum / N);
-    if (p->seed_pattern) w = mauve_seed_weight(p->seed_pattern);
-    S.full = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
+    int w;
+    (void)resolve_seed(c, p, sum / N, "align_lcbs", &w, nullptr);          // (the weight alone: the chains are the caller's, no pattern is needed)
+    S.full = full_mask(N);
     S.nm = 0; S.nl = (int64_t)lcbs.size();
     S.chains.swap(lcbs);
     R.lcb_weight.assign((size_t)S.nl, 0);
@@ -784,14 +675,26 @@ static int align_begin_lcbs(mauve_ctx *c, const mauve_params *p, std::vector<Mat
     const double t2 = now_ms();
     if (p->recursive) { const int rc = recursive_anchoring(c, p, w, S.chains, N, nullptr); if (rc) return rc; }
     c->stage.recurse_ms = now_ms() - t2;
-    for (int64_t l = 0; l < S.nl; l++) {
-        const MatchVec &ch = S.chains[(size_t)l];
-        S.n_anchor += (int64_t)ch.size();
-        for (size_t i = 0; i < ch.size(); i++) S.anchor_cols += ch.len(i);
-    }
+    S.count_anchors();
     S.t_dp0 = now_ms();
     S.open = true;
     return MAUVE_OK;
+}
+
+// the interval table is on the host (align_begin without device_front): DP of all its intervals into ctx->pin_dcols, host assembly;
+// shadow: the anchor table is filled while the DP kernels run
+static int align_dp_finish(mauve_ctx *c, mauve_align_sizes *sizes, bool shadow)
+{
+    AlignState &S = c->ast;
+    HIPCHK(c, c->pin_dcols.ensure(((size_t)S.code_total + 1) * sizeof(uint32_t)));
+    uint32_t *dcols = c->pin_dcols.as<uint32_t>();
+    S.dcol_off.assign((size_t)S.n_dp + 1, 0); S.dscore.assign((size_t)S.n_dp + 1, 0);
+    int64_t cells = 0;
+    if (shadow && S.n_dp) c->shadow = [c]() { fill_anchor_table(c); };
+    const int rc = align_dp(c, nullptr, S.n_dp, dcols, S.dcol_off.data(), S.dscore.data(), &cells);
+    c->shadow = nullptr;
+    if (rc) return rc;
+    return align_finish(c, dcols, S.dcol_off.data(), S.dscore.data(), cells, sizes);
 }
 
 // the main pass's match list that was set aside in HBM (S.mums_kept) -> back in place and into the result's host tables
@@ -856,9 +759,9 @@ static int align_tail_host_chains(mauve_ctx *c, mauve_align_sizes *sizes)
             for (size_t i = 0; i < ch.size(); i++, a++) {
                 const int32_t code = gapcode[a];
                 if (code == -1) continue;
-                AlignState::GapRef gr; gr.lcb = l; gr.idx = (int64_t)i; gr.dp = code >= 0; gr.dp_slot = code >= 0 ? code : -1; gr.tot = 0;
+                GapRef gr{l, (int64_t)i, code >= 0, code >= 0 ? code : -1, 0};
                 if (!gr.dp)
-                    for (int g = 0; g < N; g++) { int64_t lo, ln; bool rv; gap_of(ch.rec(i), ch.rec(i + 1), g, lo, ln, rv); gr.tot += ln; }
+                    for (int g = 0; g < N; g++) { int64_t lo, ln; gap_of(ch.rec(i), ch.rec(i + 1), g, lo, ln); gr.tot += ln; }
                 S.gaps.push_back(gr);
             }
         }
@@ -929,16 +832,7 @@ static int align_whole(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *s
         if (rc || rc_pf) return rc ? rc : rc_pf;
         return assemble_device(c, S.n_anchor, cells, sizes);
     }
-    if (host_front) {
-        HIPCHK(c, c->pin_dcols.ensure(((size_t)S.code_total + 1) * sizeof(uint32_t)));
-        uint32_t *dcols = c->pin_dcols.as<uint32_t>();
-        S.dcol_off.assign((size_t)S.n_dp + 1, 0); S.dscore.assign((size_t)S.n_dp + 1, 0);
-        if (!no_shadow && S.n_dp) c->shadow = [c]() { fill_anchor_table(c); };       // runs while the DP kernels do
-        rc = align_dp(c, nullptr, S.n_dp, dcols, S.dcol_off.data(), S.dscore.data(), &cells);
-        c->shadow = nullptr;
-        if (rc) return rc;
-        return align_finish(c, dcols, S.dcol_off.data(), S.dscore.data(), cells, sizes);
-    }
+    if (host_front) return align_dp_finish(c, sizes, !no_shadow);
     return align_tail_host_chains(c, sizes);
 }
 
@@ -1046,14 +940,7 @@ int mauve_align_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const in
     if (rc) return rc;
     rc = align_begin(c, p, false, &mv);
     if (rc) return rc;
-    AlignState &S = c->ast;
-    HIPCHK(c, c->pin_dcols.ensure(((size_t)S.code_total + 1) * sizeof(uint32_t)));
-    uint32_t *dcols = c->pin_dcols.as<uint32_t>();
-    S.dcol_off.assign((size_t)S.n_dp + 1, 0); S.dscore.assign((size_t)S.n_dp + 1, 0);
-    int64_t cells = 0;
-    rc = align_dp(c, nullptr, S.n_dp, dcols, S.dcol_off.data(), S.dscore.data(), &cells);
-    if (rc) return rc;
-    return align_finish(c, dcols, S.dcol_off.data(), S.dscore.data(), cells, sizes);
+    return align_dp_finish(c, sizes, false);
 }
 
 int mauve_align_begin_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const int64_t *length, const int64_t *start, int64_t *n_dp,
@@ -1078,7 +965,7 @@ int mauve_align_dp_anchors(mauve_ctx *c, int64_t *left, int64_t *right)
     if (!c || !c->ast.open) { if (c) c->err = "align_dp_anchors: no alignment in progress"; return c ? MAUVE_ERR_STATE : MAUVE_ERR_ARG; }
     const AlignState &S = c->ast;
     const int N = S.N;
-    for (const AlignState::GapRef &gr : S.gaps) {
+    for (const GapRef &gr : S.gaps) {
         if (!gr.dp) continue;
         const MatchVec &ch = S.chains[(size_t)gr.lcb];
         if (left) std::copy(ch.rec((size_t)gr.idx), ch.rec((size_t)gr.idx) + 1 + N, left + gr.dp_slot * (1 + N));

@@ -11,6 +11,17 @@
 //      aligner, so those bases flow down to the subtree that shares them;
 //   3. what is left at the leaves becomes single-genome intervals.
 // Every node is one pass of the same device pipeline (seed pass, batched recursive anchoring, batched DP).
+//
+// A node (prog_node) is a list of stages that hand each other one NodeWork record:
+//   node_search       seed weight and pattern for what is left of the node's genomes, placed-base mask, the search
+//   node_min_weight   minimum LCB weights of the node, scaled by the distances between its subtrees (S11b, S11c)
+//   node_chain        overlap elimination and LCBs: on the device at the root, else host_chain_lcbs
+//   node_pieces       the chains, cut where a stretch between two anchors touches a placed base
+//   (recursive_anchoring, recursive.cpp)
+//   node_split_long   pieces cut again where a stretch is too long for the gapped aligner or only a subset's
+//   host_gap_table    the interval table (host_chain.hpp)
+//   node_dp_plain / node_refine   gapped alignment of the intervals; with refinement also of their rotations (S13)
+//   node_blocks       the node's blocks into the result, their bases out of the pools
 #include "common.hpp"
 #include <algorithm>
 #include <array>
@@ -21,6 +32,8 @@
 int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector<MatchVec> &chains, int N, const int *gmap);
 
 namespace {
+
+const bool g_trace = getenv("MAUVE_TRACE") != nullptr;      // read once, not in the timed path
 
 // The bases of one genome that no block has taken yet: an ordered map start -> end of free stretches (1-based,
 // inclusive, disjoint).  Blocks are carved out one by one; a position is identified by the start of the stretch it lies
@@ -52,15 +65,6 @@ struct FreePool {
     }
 };
 
-inline void gap_of(const int64_t *a, const int64_t *b, int g, int64_t &lo, int64_t &len, bool &rev)
-{
-    const int64_t sa = a[1 + g], sb = b[1 + g];
-    int64_t hi;
-    if (sa > 0) { lo = sa + a[0]; hi = sb - 1; rev = false; }
-    else { lo = -sb + b[0]; hi = -sa - 1; rev = true; }
-    len = hi - lo + 1; if (len < 0) len = 0;
-}
-
 struct Prog {
     mauve_ctx *c; const mauve_params *p; int N;
     std::vector<int32_t> left, right;
@@ -70,6 +74,21 @@ struct Prog {
     AlignResult *R;
     int64_t n_gap_dp = 0, n_cells = 0, n_anchor = 0, n_multi = 0;
     double t_seed = 0, t_chain = 0, t_rec = 0, t_dp = 0, t_blocks = 0;      // stage times summed over the nodes (mauve_last_stage_times)
+};
+
+// what the stages of one node hand each other
+struct NodeWork {
+    int node = 0, n = 0, w = 0; uint64_t pat = 0; uint32_t full = 0;
+    std::vector<int> gm;                       // the node's n genomes: global ids, ascending
+    int64_t rest_len = 0;                      // their bases no block has taken yet
+    GenomeSet gs;
+    int64_t nm = 0; MatchVec m;                // the search's matches; after the chain: overlap-free
+    int64_t lcbw = 0, minw_sp = 0;             // minimum LCB weight: length-weighted, score-weighted (lcb_scoring = SP only)
+    std::vector<int64_t> match_lcb; int64_t nl = 0;
+    std::vector<MatchVec> pieces;              // the node's blocks-to-be: chains, cut
+    std::vector<GapRef> gaps; std::vector<DpSeqDesc> desc; int64_t n_dp = 0, code_total = 0;     // (GapRef::lcb: index into pieces; descriptors carry GLOBAL genome ids)
+    uint32_t *dcols = nullptr; std::vector<int64_t> dcol_off, dscore; int64_t cells = 0;         // DP outputs (dcols: c->pin_dcols)
+    double tn0 = 0, tn1 = 0, tn2 = 0, tn3 = 0; // stage clocks: search from, chain from, recursion from, DP from
 };
 
 int leaves_of(const Prog &P, int node, std::vector<int> &out)
@@ -86,16 +105,8 @@ int upload_mask(Prog &P, const std::vector<int> &gm, GenomeSet &gs)
     size_t words = 0;
     for (size_t j = 0; j < gm.size(); j++) { gs.mask_off[j] = words; words += (size_t)((c->lens[gm[j]] + 63) / 64) + 2; }
     std::vector<uint64_t> bits(words, ~0ULL);
-    for (size_t j = 0; j < gm.size(); j++) {
-        uint64_t *M = bits.data() + gs.mask_off[j];
-        for (const auto &fr : P.rest[gm[j]].free_)
-            for (int64_t b = fr.first - 1; b < fr.second;) {        // clear [lo-1, hi) word-wise
-                const int64_t w = b >> 6, e = std::min<int64_t>(fr.second, (w + 1) << 6);
-                const int n = (int)(e - b), sh = (int)(b & 63);
-                const uint64_t m = (n == 64 ? ~0ULL : ((1ULL << n) - 1ULL)) << sh;
-                M[w] &= ~m; b = e;
-            }
-    }
+    for (size_t j = 0; j < gm.size(); j++)
+        for (const auto &fr : P.rest[gm[j]].free_) clear_bits(bits.data() + gs.mask_off[j], fr.first, fr.second);
     // ambiguous bases stay unusable at every node; contig joins likewise (mauve_set_genomes_contigs)
     if (c->has_invalid)
         for (size_t j = 0; j < gm.size(); j++) {
@@ -119,292 +130,294 @@ int upload_mask(Prog &P, const std::vector<int> &gm, GenomeSet &gs)
     return MAUVE_OK;
 }
 
-int prog_node(Prog &P, int node)
+// seed of the node from what is left of its genomes, their placed-base mask, the search (tn0 .. tn1)
+int node_search(Prog &P, NodeWork &W)
 {
-    if (P.left[node] < 0) return MAUVE_OK;
     mauve_ctx *c = P.c; const mauve_params *p = P.p;
-    std::vector<int> gm; leaves_of(P, node, gm);
-    std::sort(gm.begin(), gm.end());
-    const int n = (int)gm.size();
-    AlignResult &R = *P.R;
+    leaves_of(P, W.node, W.gm);
+    std::sort(W.gm.begin(), W.gm.end());
+    const std::vector<int> &gm = W.gm;
+    const int n = W.n = (int)gm.size();
+    for (int j = 0; j < n; j++) W.rest_len += P.rest[gm[j]].bases();
+    int rc = resolve_seed(c, p, W.rest_len / n, "progressive_align", &W.w, &W.pat);
+    if (rc) return rc;
+    W.full = full_mask(n);
 
-    int64_t rest_len = 0;
-    for (int j = 0; j < n; j++) rest_len += P.rest[gm[j]].bases();
-    int w = p->seed_weight > 0 ? p->seed_weight : mauve_default_seed_weight(rest_len / n);
-    uint64_t pat = p->seed_pattern ? p->seed_pattern : mauve_get_seed(w, p->seed_rank);
-    if (!pat) { c->err = "progressive_align: no seed pattern for this weight/rank"; return MAUVE_ERR_ARG; }
-    w = mauve_seed_weight(pat);
-    const uint32_t full = n >= 32 ? 0xffffffffu : ((1u << n) - 1);
-
-    GenomeSet gs; gs.buf = &c->genomes; gs.nseq = n;
+    GenomeSet &gs = W.gs; gs.buf = &c->genomes; gs.nseq = n;
     for (int j = 0; j < n; j++) { gs.lens.push_back(c->lens[gm[j]]); gs.word_off.push_back(c->word_off[gm[j]]); }
     bool any_placed = false;
     for (int j = 0; j < n; j++) if (!P.rest[gm[j]].whole(c->lens[gm[j]])) any_placed = true;
-    if (any_placed) { int rc = upload_mask(P, gm, gs); if (rc) return rc; }
+    if (any_placed) { rc = upload_mask(P, gm, gs); if (rc) return rc; }
 
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
-    const double tn0 = now_ms();
-    int64_t nm = 0;
-    MatchVec m(n);
-    int rc;
+    W.tn0 = now_ms();
+    W.m = MatchVec(n);
     if (p->seed_family) {                                    // the node searches with the whole seed family
-        rc = seed_family_matches(c, gs, w, p->mode, full, m);
+        rc = seed_family_matches(c, gs, W.w, p->mode, W.full, W.m);
         if (rc) return rc;
-        nm = (int64_t)m.size();
+        W.nm = (int64_t)W.m.size();
     } else {
-        rc = seedpass_run(c, gs, pat, p->mode, full, 1, nullptr, 0, &nm);
+        rc = seedpass_run(c, gs, W.pat, p->mode, W.full, 1, nullptr, 0, &W.nm);
         if (rc) return rc;
-        m.resize((size_t)nm);
-        for (int64_t i = 0; i < nm; i++) {
-            m.len((size_t)i) = c->match_len[(size_t)i];
-            std::copy(&c->match_start[(size_t)i * n], &c->match_start[(size_t)i * n] + n, m.st((size_t)i));
-        }
+        seed_matches_to_vec(c, n, W.nm, W.m);
     }
-    const double tn1 = now_ms();
-    ChainOrders orders;
-    int64_t lcbw = p->lcb_weight >= 0 ? p->lcb_weight * n / P.N : (int64_t)3 * w * n;
+    W.tn1 = now_ms();
+    return MAUVE_OK;
+}
+
+// the node's minimum LCB weights: a given threshold is for all N genomes and is scaled by the node's share of them (of the
+// pairs, for sum-of-pairs scores); both shrink with the distance between the node's two subtrees
+void node_min_weight(const Prog &P, NodeWork &W)
+{
+    const mauve_params *p = P.p;
+    const int64_t n = W.n, N = P.N;
+    W.lcbw = p->lcb_weight >= 0 ? p->lcb_weight * n / N : (int64_t)3 * W.w * n;
+    if (p->lcb_scoring == MAUVE_LCB_SCORE_SP)
+        W.minw_sp = p->lcb_weight >= 0 ? p->lcb_weight * (n * (n - 1) / 2) / (N * (N - 1) / 2) : sp_default_min_weight(W.w, W.n, &p->scoring);
+    if (!p->weight_scaling || P.dist.empty()) return;
     // the node's minimum weight shrinks with the conservation distance between its two subtrees
-    int64_t factor_ppm = 1000000;
-    const bool scaled = p->weight_scaling && !P.dist.empty();
-    if (scaled) {
-        std::vector<int> la, lb;
-        leaves_of(P, P.left[node], la); leaves_of(P, P.right[node], lb);
-        int64_t sum = 0;
-        for (int a : la) for (int b : lb) sum += P.dist[(size_t)a * P.N + b];
-        const int64_t c_ppm = sum / ((int64_t)la.size() * (int64_t)lb.size());
-        factor_ppm = std::max<int64_t>(0, 1000000 - (int64_t)p->conservation_scale_ppm * c_ppm / 1000000);
-        if (!P.bpd.empty()) {                                 // the breakpoint-distance factor multiplies in
-            int64_t bsum = 0;
-            for (int a : la) for (int b : lb) bsum += P.bpd[(size_t)a * P.N + b];
-            const int64_t f2 = std::max<int64_t>(0, 1000000 - (int64_t)p->bp_dist_scale_ppm * (bsum / ((int64_t)la.size() * (int64_t)lb.size())) / 1000000);
-            factor_ppm = factor_ppm * f2 / 1000000;
-        }
-        lcbw = std::max(lcbw * factor_ppm / 1000000, p->min_scaled_penalty);
+    std::vector<int> la, lb;
+    leaves_of(P, P.left[W.node], la); leaves_of(P, P.right[W.node], lb);
+    const int64_t pairs = (int64_t)la.size() * (int64_t)lb.size();
+    int64_t sum = 0;
+    for (int a : la) for (int b : lb) sum += P.dist[(size_t)a * P.N + b];
+    int64_t factor_ppm = std::max<int64_t>(0, 1000000 - (int64_t)p->conservation_scale_ppm * (sum / pairs) / 1000000);
+    if (!P.bpd.empty()) {                                     // the breakpoint-distance factor multiplies in
+        int64_t bsum = 0;
+        for (int a : la) for (int b : lb) bsum += P.bpd[(size_t)a * P.N + b];
+        const int64_t f2 = std::max<int64_t>(0, 1000000 - (int64_t)p->bp_dist_scale_ppm * (bsum / pairs) / 1000000);
+        factor_ppm = factor_ppm * f2 / 1000000;
     }
-    std::vector<int64_t> match_lcb; int64_t nl = 0;
-    // The root's list (all genomes, tens of thousands of matches) is still in HBM in canonical order: overlap elimination and LCBs on the
-    // device (chain_dev.hip), cropped records and labels back -- what mauve_align does.  Nodes below the root have short lists (and a
-    // genome subset: the device chain takes its position width from the context's genomes), score-weighted LCBs need the matches' scores,
-    // a list the device chain declines comes back as MAUVE_ERR_LIMIT: the host chain for those.  MAUVE_HOST_CHAIN: A/B switch.
+    W.lcbw = std::max(W.lcbw * factor_ppm / 1000000, p->min_scaled_penalty);
+    if (p->lcb_scoring == MAUVE_LCB_SCORE_SP) W.minw_sp = std::max(W.minw_sp * factor_ppm / 1000000, p->min_scaled_penalty);
+}
+
+// The root's list (all genomes, tens of thousands of matches) is still in HBM in canonical order: overlap elimination and LCBs on the
+// device (chain_dev.hip), cropped records and labels back -- what mauve_align does.  Nodes below the root have short lists (and a
+// genome subset: the device chain takes its position width from the context's genomes), score-weighted LCBs need the matches' scores,
+// a list the device chain declines comes back as MAUVE_ERR_LIMIT: the host chain for those.  MAUVE_HOST_CHAIN: A/B switch.
+int node_chain(Prog &P, NodeWork &W)
+{
+    mauve_ctx *c = P.c; const mauve_params *p = P.p;
+    const int n = W.n;
+    MatchVec &m = W.m;
     static const bool host_chain_env = getenv("MAUVE_HOST_CHAIN") != nullptr;
-    bool chained = false;
-    if (!host_chain_env && !p->seed_family && n == P.N && nm > 0 && c->dev_rec_n == nm && (p->lcb_scoring == MAUVE_LCB_SCORE_LENGTH || n <= 16)) {
-        if (p->lcb_scoring == MAUVE_LCB_SCORE_SP) {          // the matches' scores are summed on the device too (ch_sp_scores, on the cropped records)
-            int64_t minw = p->lcb_weight >= 0 ? p->lcb_weight * ((int64_t)n * (n - 1) / 2) / ((int64_t)P.N * (P.N - 1) / 2)
-                                              : sp_default_min_weight(w, n, &p->scoring);
-            if (scaled) minw = std::max(minw * factor_ppm / 1000000, p->min_scaled_penalty);
-            rc = chain_device(c, n, minw, p->collinear != 0, m, match_lcb, nl, &p->scoring);
-        } else
-            rc = chain_device(c, n, lcbw, p->collinear != 0, m, match_lcb, nl);
-        if (rc == MAUVE_OK) chained = true;
-        else if (rc != MAUVE_ERR_LIMIT) return rc;
+    const bool sp = p->lcb_scoring == MAUVE_LCB_SCORE_SP;    // the matches' scores are summed on the device too (ch_sp_scores, on the cropped records)
+    int rc = MAUVE_ERR_LIMIT;
+    if (!host_chain_env && !p->seed_family && n == P.N && W.nm > 0 && c->dev_rec_n == W.nm && (!sp || n <= 16)) {
+        rc = chain_device(c, n, sp ? W.minw_sp : W.lcbw, p->collinear != 0, m, W.match_lcb, W.nl, sp ? &p->scoring : nullptr);
+        if (rc && rc != MAUVE_ERR_LIMIT) return rc;
     }
-    if (!chained) {
-        host_eliminate_overlaps(m, &orders);
-        if (p->lcb_scoring == MAUVE_LCB_SCORE_SP) {
-            std::vector<int64_t> mw;
-            rc = match_sp_scores(c, m, gm.data(), &p->scoring, mw);
-            if (rc) return rc;
-            // a given score threshold is for all N genomes: scaled by the node's share of the pairs
-            int64_t minw = p->lcb_weight >= 0 ? p->lcb_weight * ((int64_t)n * (n - 1) / 2) / ((int64_t)P.N * (P.N - 1) / 2)
-                                              : sp_default_min_weight(w, n, &p->scoring);
-            if (scaled) minw = std::max(minw * factor_ppm / 1000000, p->min_scaled_penalty);
-            host_lcb_chain(m, minw, p->collinear != 0, match_lcb, nl, &orders, mw.data());
-        } else
-            host_lcb_chain(m, lcbw, p->collinear != 0, match_lcb, nl, &orders);
-    }
-    if (trace) {
-        int64_t surv = 0; for (size_t i = 0; i < m.size(); i++) if (match_lcb[i] >= 0) surv++;
-        fprintf(stderr, "[trace] node %d (n=%d, w=%d): %lld n-way matches, %zu after overlap elimination, %lld lcbs, %lld anchors\n", node, n, w,
-                (long long)nm, m.size(), (long long)nl, (long long)surv);
+    if (rc) { rc = host_chain_lcbs(c, p, m, W.gm.data(), W.lcbw, W.minw_sp, W.match_lcb, W.nl, nullptr, true); if (rc) return rc; }
+    if (g_trace) {
+        int64_t surv = 0; for (size_t i = 0; i < m.size(); i++) if (W.match_lcb[i] >= 0) surv++;
+        fprintf(stderr, "[trace] node %d (n=%d, w=%d): %lld n-way matches, %zu after overlap elimination, %lld lcbs, %lld anchors\n", W.node, n, W.w,
+                (long long)W.nm, m.size(), (long long)W.nl, (long long)surv);
         if (getenv("MAUVE_TRACE_MATCHES"))
-            for (size_t i = 0; i < m.size(); i++) { fprintf(stderr, "[trace]   m %zu len %lld lcb %lld:", i, (long long)m.len(i), (long long)match_lcb[i]); for (int j = 0; j < n; j++) fprintf(stderr, " %lld", (long long)m.st(i)[j]); fprintf(stderr, "\n"); }
+            for (size_t i = 0; i < m.size(); i++) { fprintf(stderr, "[trace]   m %zu len %lld lcb %lld:", i, (long long)m.len(i), (long long)W.match_lcb[i]); for (int j = 0; j < n; j++) fprintf(stderr, " %lld", (long long)m.st(i)[j]); fprintf(stderr, "\n"); }
     }
-    // chains, cut wherever the stretch between two consecutive anchors touches an already placed base
-    std::vector<MatchVec> pieces; int64_t cur_lcb = -1;
+    return MAUVE_OK;
+}
+
+// chains, cut wherever the stretch between two consecutive anchors touches an already placed base
+void node_pieces(const Prog &P, NodeWork &W)
+{
+    const MatchVec &m = W.m;
+    int64_t cur_lcb = -1;
     for (size_t i = 0; i < m.size(); i++) {
-        const int64_t l = match_lcb[i]; if (l < 0) continue;
+        const int64_t l = W.match_lcb[i]; if (l < 0) continue;
         bool newp = l != cur_lcb;
         if (!newp) {
-            const MatchVec &last = pieces.back();
+            const MatchVec &last = W.pieces.back();
             const int64_t *a = last.st(last.size() - 1);
-            for (int j = 0; j < n && !newp; j++)
-                if (P.rest[gm[j]].stretch_of(std::llabs(a[j])) != P.rest[gm[j]].stretch_of(std::llabs(m.st(i)[j]))) newp = true;
-        }
-        if (newp) { pieces.emplace_back(n); cur_lcb = l; }
-        pieces.back().push(m.rec(i));
-    }
-    const double tn2 = now_ms();
-    if (p->recursive) { rc = recursive_anchoring(c, p, w, pieces, n, gm.data()); if (rc) return rc; }
-    const double tn3 = now_ms();
-    // a stretch shared by >= 2 genomes that is too long for the gapped aligner, or that only a proper subset of
-    // this node's genomes has (and that is long enough to be anchored), ends the block: its bases stay in the
-    // pool for the subtree that shares them
-    if (p->gapped) {
-        std::vector<MatchVec> np2;
-        for (const MatchVec &pc : pieces)
-            for (size_t i = 0; i < pc.size(); i++) {
-                bool split = i == 0;
-                if (!split) {
-                    int64_t mx = 0; int nonempty = 0, big = 0;
-                    for (int j = 0; j < n; j++) { int64_t lo, ln; bool rv; gap_of(pc.rec(i - 1), pc.rec(i), j, lo, ln, rv); mx = std::max(mx, ln); nonempty += ln > 0; big += ln > p->min_recursive_gap; }
-                    split = nonempty >= 2 && (mx > p->max_gapped_len || (big >= 2 && big < n));
-                }
-                if (split) np2.emplace_back(n);
-                np2.back().push(pc.rec(i));
+            for (int j = 0; j < W.n && !newp; j++) {
+                const FreePool &fp = P.rest[W.gm[j]];
+                if (fp.stretch_of(std::llabs(a[j])) != fp.stretch_of(std::llabs(m.st(i)[j]))) newp = true;
             }
-        pieces.swap(np2);
-    }
-    // ---- gapped alignment of the inter-anchor intervals of this node (descriptors carry GLOBAL genome ids) ----
-    struct GapRef { size_t piece, idx; bool dp; int64_t slot; };
-    std::vector<GapRef> gaps; std::vector<DpSeqDesc> desc; int64_t n_dp = 0, code_total = 0;
-    for (size_t q = 0; q < pieces.size(); q++) {
-        const MatchVec &ch = pieces[q];
-        for (size_t i = 0; i + 1 < ch.size(); i++) {
-            int64_t tot = 0, mx = 0; int nonempty = 0; int64_t lo[MAUVE_MAX_SEQ], ln[MAUVE_MAX_SEQ]; bool rv[MAUVE_MAX_SEQ];
-            for (int j = 0; j < n; j++) { gap_of(ch.rec(i), ch.rec(i + 1), j, lo[j], ln[j], rv[j]); tot += ln[j]; mx = std::max(mx, ln[j]); nonempty += ln[j] > 0; }
-            if (!tot) continue;
-            GapRef gr{q, i, false, -1};
-            if (p->gapped && nonempty >= 2 && mx <= p->max_gapped_len) {
-                gr.dp = true; gr.slot = n_dp++;
-                for (int j = 0; j < n; j++) { DpSeqDesc d; d.genome = gm[j]; d.rev = rv[j]; d.lo0 = lo[j] - 1; d.len = ln[j]; desc.push_back(d); }
-                code_total += tot;
-            }
-            gaps.push_back(gr);
         }
+        if (newp) { W.pieces.emplace_back(W.n); cur_lcb = l; }
+        W.pieces.back().push(m.rec(i));
     }
-    HIPCHK(c, c->pin_dcols.ensure(((size_t)code_total + 1) * sizeof(uint32_t)));
-    uint32_t *dcols = c->pin_dcols.as<uint32_t>();
-    std::vector<int64_t> dcol_off((size_t)n_dp + 1, 0), dscore((size_t)n_dp + 1, 0);
-    int64_t cells = 0;
-    c->dp_band_from = INT64_MAX;            // the progressive path splits long intervals instead (DESIGN.md S11)
-    const bool refine = p->refine_rounds > 0 && n >= 3 && n_dp > 0;
-    std::vector<int64_t> dsp; if (refine) dsp.assign((size_t)n_dp + 1, 0);
-    // DESIGN.md S13 (setRefinement): every interval of k >= 3 sequences is also aligned in the rotated orders r = 1 .. min(rounds, k-1) and keeps the
-    // alignment whose sum-of-pairs score (dp_sp_scores) is highest, lowest rotation on ties.  A candidate's slots hold the rotated sequences, so its
-    // column bits are slots of the rotation.  The candidates do not depend on the first alignment, only the choice does: ONE batch holds the
-    // intervals and all their candidates (one sizing pass, one launch with more to balance), the columns stay on the device, the scores come back,
-    // and only the winners' columns are compacted and copied out (dp_fetch_picked) -- at C4's root 57 k candidates of 29 k intervals, 1 k of them win.
-    // Several contexts (mauve_set_shard) keep the two exchanged batches.
-    struct Cand { int64_t iv; int r, k; uint8_t nz[MAUVE_MAX_SEQ]; };
+}
+
+// a stretch shared by >= 2 genomes that is too long for the gapped aligner, or that only a proper subset of
+// this node's genomes has (and that is long enough to be anchored), ends the block: its bases stay in the
+// pool for the subtree that shares them
+void node_split_long(const Prog &P, NodeWork &W)
+{
+    const mauve_params *p = P.p; const int n = W.n;
+    std::vector<MatchVec> np2;
+    for (const MatchVec &pc : W.pieces)
+        for (size_t i = 0; i < pc.size(); i++) {
+            bool split = i == 0;
+            if (!split) {
+                int64_t mx = 0; int nonempty = 0, big = 0;
+                for (int j = 0; j < n; j++) { int64_t lo, ln; gap_of(pc.rec(i - 1), pc.rec(i), j, lo, ln); mx = std::max(mx, ln); nonempty += ln > 0; big += ln > p->min_recursive_gap; }
+                split = nonempty >= 2 && (mx > p->max_gapped_len || (big >= 2 && big < n));
+            }
+            if (split) np2.emplace_back(n);
+            np2.back().push(pc.rec(i));
+        }
+    W.pieces.swap(np2);
+}
+
+int node_dp_plain(Prog &P, NodeWork &W)          // (several contexts: the node's intervals are dealt out)
+{
+    return dp_batch_run_desc(P.c, W.n, W.n_dp, W.desc.data(), &P.p->scoring, W.dcols, W.dcol_off.data(), W.dscore.data(), &W.cells, true, nullptr);
+}
+
+// DESIGN.md S13 (setRefinement): every interval of k >= 3 sequences is also aligned in the rotated orders r = 1 .. min(rounds, k-1) and keeps the
+// alignment whose sum-of-pairs score (dp_sp_scores) is highest, lowest rotation on ties.  A candidate's slots hold the rotated sequences, so its
+// column bits are slots of the rotation.  The candidates do not depend on the first alignment, only the choice does: ONE batch holds the
+// intervals and all their candidates (one sizing pass, one launch with more to balance), the columns stay on the device, the scores come back,
+// and only the winners' columns are compacted and copied out (dp_fetch_picked) -- at C4's root 57 k candidates of 29 k intervals, 1 k of them win.
+// Several contexts (mauve_set_shard) keep the two exchanged batches.
+struct Cand { int64_t iv; int r, k; uint8_t nz[MAUVE_MAX_SEQ]; };
+struct RefineWork {
     std::vector<Cand> cands;
-    if (refine) {
-        const double tr0 = now_ms();
-        int64_t ccodes = 0;
-        // (sized once and filled in place: 86 000 descriptor rows at C4's root; push_back by push_back this took 3 ms.  A batch large enough for the
-        // device front gets only the intervals and the index of every interval's first candidate: the rotated rows are made on the device.)
-        std::vector<DpSeqDesc> &all = c->prog_desc;
-        std::vector<int32_t> cbase((size_t)n_dp + 1, 0);
-        int64_t nc0 = 0;
-        for (int64_t iv = 0; iv < n_dp; iv++) {
-            int k = 0; for (int j = 0; j < n; j++) k += desc[(size_t)(iv * n + j)].len != 0;
-            cbase[(size_t)iv] = (int32_t)nc0;
-            if (k >= 3) nc0 += std::min(p->refine_rounds, k - 1);
-        }
-        cbase[(size_t)n_dp] = (int32_t)nc0;
-        const bool rot_dev = !c->shard_on && nc0 > 0 && nc0 < (1LL << 30) && dp_desc_rotations_on_device(n_dp + nc0);
-        if (!rot_dev) { all.resize((size_t)(n_dp + nc0) * n); std::copy(desc.begin(), desc.end(), all.begin()); }
-        cands.resize((size_t)nc0);
-        DpSeqDesc none; none.genome = gm[0]; none.rev = 0; none.lo0 = 0; none.len = 0;
-        int64_t q0 = 0;
-        for (int64_t iv = 0; iv < n_dp; iv++) {
-            Cand cd; cd.iv = iv; cd.k = 0;
-            int64_t tot = 0;
-            const DpSeqDesc *di = &desc[(size_t)(iv * n)];
-            for (int j = 0; j < n; j++) if (di[j].len) { cd.nz[cd.k++] = (uint8_t)j; tot += di[j].len; }
-            if (cd.k < 3) continue;
-            for (int r = 1; r <= p->refine_rounds && r < cd.k; r++, q0++) {
-                cd.r = r; cands[(size_t)q0] = cd;
-                if (!rot_dev) {
-                    DpSeqDesc *o = &all[(size_t)(n_dp + q0) * n];
-                    for (int j = 0; j < n; j++) o[j] = j < cd.k ? di[cd.nz[(j + r) % cd.k]] : none;
-                }
-                ccodes += tot;
+    std::vector<int32_t> cbase;                // first candidate of every interval (n_dp + 1 entries)
+    bool rot_dev = false;                      // the rotated descriptor rows are made on the device
+    int64_t ccodes = 0, replaced = 0;          // bases of all candidates; intervals that keep a candidate
+    std::vector<int64_t> aoff, ascore, asp;    // of the batch entries: the intervals, then the candidates
+    std::vector<uint32_t> ccols;               // the candidates' columns (the exchanged form only)
+};
+
+// the candidates of every interval; their descriptor rows behind the intervals' in c->prog_desc unless the device makes them
+// (sized once and filled in place: 86 000 descriptor rows at C4's root; push_back by push_back this took 3 ms.  A batch large enough for the
+// device front gets only the intervals and the index of every interval's first candidate: the rotated rows are made on the device.)
+void refine_candidates(Prog &P, NodeWork &W, RefineWork &F)
+{
+    mauve_ctx *c = P.c; const mauve_params *p = P.p;
+    const int n = W.n; const int64_t n_dp = W.n_dp;
+    const std::vector<DpSeqDesc> &desc = W.desc;
+    std::vector<DpSeqDesc> &all = c->prog_desc;
+    F.cbase.assign((size_t)n_dp + 1, 0);
+    int64_t nc0 = 0;
+    for (int64_t iv = 0; iv < n_dp; iv++) {
+        int k = 0; for (int j = 0; j < n; j++) k += desc[(size_t)(iv * n + j)].len != 0;
+        F.cbase[(size_t)iv] = (int32_t)nc0;
+        if (k >= 3) nc0 += std::min(p->refine_rounds, k - 1);
+    }
+    F.cbase[(size_t)n_dp] = (int32_t)nc0;
+    F.rot_dev = !c->shard_on && nc0 > 0 && nc0 < (1LL << 30) && dp_desc_rotations_on_device(n_dp + nc0);
+    if (!F.rot_dev) { all.resize((size_t)(n_dp + nc0) * n); std::copy(desc.begin(), desc.end(), all.begin()); }
+    F.cands.resize((size_t)nc0);
+    DpSeqDesc none; none.genome = W.gm[0]; none.rev = 0; none.lo0 = 0; none.len = 0;
+    int64_t q0 = 0;
+    for (int64_t iv = 0; iv < n_dp; iv++) {
+        Cand cd; cd.iv = iv; cd.k = 0;
+        int64_t tot = 0;
+        const DpSeqDesc *di = &desc[(size_t)(iv * n)];
+        for (int j = 0; j < n; j++) if (di[j].len) { cd.nz[cd.k++] = (uint8_t)j; tot += di[j].len; }
+        if (cd.k < 3) continue;
+        for (int r = 1; r <= p->refine_rounds && r < cd.k; r++, q0++) {
+            cd.r = r; F.cands[(size_t)q0] = cd;
+            if (!F.rot_dev) {
+                DpSeqDesc *o = &all[(size_t)(n_dp + q0) * n];
+                for (int j = 0; j < n; j++) o[j] = j < cd.k ? di[cd.nz[(j + r) % cd.k]] : none;
             }
+            F.ccodes += tot;
         }
-        const int64_t nc = (int64_t)cands.size(), na = n_dp + nc;
-        const bool one_batch = !c->shard_on;
-        const double tr1 = now_ms();
-        std::vector<int64_t> aoff((size_t)na + 1, 0), ascore((size_t)na + 1, 0), asp((size_t)na + 1, 0);
-        std::vector<uint32_t> ccols;                             // (the exchanged form only)
-        if (one_batch && rot_dev) {
-            rc = dp_batch_run_desc_rot(c, n, n_dp, desc.data(), cbase.data(), na, &p->scoring, aoff.data(), ascore.data(), &cells, asp.data());
-            if (rc) return rc;
-        } else if (one_batch) {
-            rc = dp_batch_run_desc(c, n, na, all.data(), &p->scoring, nullptr, aoff.data(), ascore.data(), &cells, false, asp.data());
-            if (rc) return rc;
-        } else {
-            rc = dp_batch_run_desc(c, n, n_dp, all.data(), &p->scoring, dcols, aoff.data(), ascore.data(), &cells, true, asp.data());
-            if (rc) return rc;
-            if (nc) {
-                ccols.resize((size_t)ccodes + 1);
-                std::vector<int64_t> coff((size_t)nc + 1, 0);
-                int64_t cells2 = 0;
-                rc = dp_batch_run_desc(c, n, nc, all.data() + (size_t)n_dp * n, &p->scoring, ccols.data(), coff.data(), ascore.data() + n_dp, &cells2, true, asp.data() + n_dp);
-                if (rc) return rc;
-                cells += cells2;
-                for (int64_t q = 0; q <= nc; q++) aoff[(size_t)(n_dp + q)] = aoff[(size_t)n_dp] + coff[(size_t)q];
-            }
-        }
-        const double tr2 = now_ms();
-        std::vector<int64_t> pick((size_t)n_dp);                // the batch entry whose alignment the interval keeps
-        int64_t replaced = 0;
-        for (int64_t iv = 0; iv < n_dp; iv++) { pick[(size_t)iv] = iv; dsp[(size_t)iv] = asp[(size_t)iv]; }
-        for (int64_t q = 0; q < nc; q++) {                     // candidates of an interval are consecutive, rotations ascending
-            const int64_t iv = cands[(size_t)q].iv;
-            if (asp[(size_t)(n_dp + q)] > dsp[(size_t)iv]) { dsp[(size_t)iv] = asp[(size_t)(n_dp + q)]; replaced += pick[(size_t)iv] == iv; pick[(size_t)iv] = n_dp + q; }
-        }
-        if (one_batch) {
-            rc = dp_fetch_picked(c, n_dp, pick.data(), aoff.data(), dcols, dcol_off.data());
-            if (rc) return rc;
-        } else {
-            // (the originals are in dcols already; winners' columns are spliced in below)
-            std::copy(aoff.begin(), aoff.begin() + n_dp + 1, dcol_off.begin());
-            if (replaced) {
-                std::vector<uint32_t> ncols; ncols.reserve((size_t)dcol_off[(size_t)n_dp]);
-                std::vector<int64_t> noff((size_t)n_dp + 1, 0);
-                for (int64_t iv = 0; iv < n_dp; iv++) {
-                    noff[(size_t)iv] = (int64_t)ncols.size();
-                    const int64_t q = pick[(size_t)iv];
-                    if (q == iv) ncols.insert(ncols.end(), dcols + dcol_off[(size_t)iv], dcols + dcol_off[(size_t)iv + 1]);
-                    else ncols.insert(ncols.end(), ccols.data() + (aoff[(size_t)q] - aoff[(size_t)n_dp]), ccols.data() + (aoff[(size_t)q + 1] - aoff[(size_t)n_dp]));
-                }
-                noff[(size_t)n_dp] = (int64_t)ncols.size();
-                if ((int64_t)ncols.size() > code_total) { c->err = "refinement: more columns than bases"; return MAUVE_ERR_STATE; }
-                memcpy(dcols, ncols.data(), ncols.size() * sizeof(uint32_t));
-                dcol_off.swap(noff);
-            }
-        }
-        if (dcol_off[(size_t)n_dp] > code_total) { c->err = "refinement: more columns than bases"; return MAUVE_ERR_STATE; }
-        // winners that are rotations: their column bits are slots of the rotation -> the node's slots
-        for (int64_t iv = 0; iv < n_dp; iv++) {
-            const int64_t q = pick[(size_t)iv];
-            dscore[(size_t)iv] = ascore[(size_t)q];
-            if (q == iv) continue;
-            const Cand &cd = cands[(size_t)(q - n_dp)];
-            uint32_t map[MAUVE_MAX_SEQ];
-            for (int j = 0; j < cd.k; j++) map[j] = 1u << cd.nz[(j + cd.r) % cd.k];
-            for (int64_t k = dcol_off[(size_t)iv]; k < dcol_off[(size_t)iv + 1]; k++) {
-                const uint32_t mc = dcols[(size_t)k]; uint32_t o = 0;
-                for (int j = 0; j < cd.k; j++) if (mc >> j & 1u) o |= map[j];
-                dcols[(size_t)k] = o;
-            }
-        }
-        if (trace) fprintf(stderr, "[trace] node %d: refinement: %lld candidate alignments of %lld intervals, %lld replaced; candidates %.3f ms, batch %.3f, pick + fetch + remap %.3f\n", node,
-                           (long long)nc, (long long)n_dp, (long long)replaced, tr1 - tr0, tr2 - tr1, now_ms() - tr2);
-    } else {
-        rc = dp_batch_run_desc(c, n, n_dp, desc.data(), &p->scoring, dcols, dcol_off.data(), dscore.data(), &cells, true, nullptr);   // (several contexts: the node's intervals are dealt out)
+    }
+}
+
+// every interval keeps the batch entry with the highest sum-of-pairs score; the winners' columns into dcols (one batch: compacted on the
+// device and fetched; exchanged form: spliced on the host), rotations' column bits back to the node's slots
+int refine_pick(Prog &P, NodeWork &W, RefineWork &F)
+{
+    mauve_ctx *c = P.c;
+    const int64_t n_dp = W.n_dp, nc = (int64_t)F.cands.size();
+    uint32_t *dcols = W.dcols; std::vector<int64_t> &dcol_off = W.dcol_off;
+    const std::vector<int64_t> &aoff = F.aoff, &asp = F.asp;
+    std::vector<int64_t> pick((size_t)n_dp), dsp((size_t)n_dp + 1, 0);      // the batch entry whose alignment the interval keeps, and its score
+    for (int64_t iv = 0; iv < n_dp; iv++) { pick[(size_t)iv] = iv; dsp[(size_t)iv] = asp[(size_t)iv]; }
+    for (int64_t q = 0; q < nc; q++) {                     // candidates of an interval are consecutive, rotations ascending
+        const int64_t iv = F.cands[(size_t)q].iv;
+        if (asp[(size_t)(n_dp + q)] > dsp[(size_t)iv]) { dsp[(size_t)iv] = asp[(size_t)(n_dp + q)]; F.replaced += pick[(size_t)iv] == iv; pick[(size_t)iv] = n_dp + q; }
+    }
+    if (!c->shard_on) {
+        const int rc = dp_fetch_picked(c, n_dp, pick.data(), aoff.data(), dcols, dcol_off.data());
         if (rc) return rc;
+    } else {
+        // (the originals are in dcols already; winners' columns are spliced in below)
+        std::copy(aoff.begin(), aoff.begin() + n_dp + 1, dcol_off.begin());
+        if (F.replaced) {
+            std::vector<uint32_t> ncols; ncols.reserve((size_t)dcol_off[(size_t)n_dp]);
+            std::vector<int64_t> noff((size_t)n_dp + 1, 0);
+            for (int64_t iv = 0; iv < n_dp; iv++) {
+                noff[(size_t)iv] = (int64_t)ncols.size();
+                const int64_t q = pick[(size_t)iv];
+                if (q == iv) ncols.insert(ncols.end(), dcols + dcol_off[(size_t)iv], dcols + dcol_off[(size_t)iv + 1]);
+                else ncols.insert(ncols.end(), F.ccols.data() + (aoff[(size_t)q] - aoff[(size_t)n_dp]), F.ccols.data() + (aoff[(size_t)q + 1] - aoff[(size_t)n_dp]));
+            }
+            noff[(size_t)n_dp] = (int64_t)ncols.size();
+            if ((int64_t)ncols.size() > W.code_total) { c->err = "refinement: more columns than bases"; return MAUVE_ERR_STATE; }
+            memcpy(dcols, ncols.data(), ncols.size() * sizeof(uint32_t));
+            dcol_off.swap(noff);
+        }
     }
-    P.n_gap_dp += n_dp; P.n_cells += cells;
-    { const double tn4 = now_ms(); P.t_seed += tn1 - tn0; P.t_chain += tn2 - tn1; P.t_rec += tn3 - tn2; P.t_dp += tn4 - tn3; }
-    if (trace) {
-        int64_t big = 0; for (int64_t k = 0; k < n_dp; k++) { int64_t mx = 0; for (int j = 0; j < n; j++) mx = std::max(mx, desc[(size_t)(k * n + j)].len); big = std::max(big, mx); }
-        fprintf(stderr, "[trace] node %d (n=%d, pool %lld): seed %.1f ms (%lld mums), chain %.1f, recursion %.1f, dp %.1f ms (%lld intervals, %lld cells, longest side %lld)\n",
-                node, n, (long long)rest_len, tn1 - tn0, (long long)nm, tn2 - tn1, tn3 - tn2, now_ms() - tn3, (long long)n_dp, (long long)cells, (long long)big);
+    if (dcol_off[(size_t)n_dp] > W.code_total) { c->err = "refinement: more columns than bases"; return MAUVE_ERR_STATE; }
+    // winners that are rotations: their column bits are slots of the rotation -> the node's slots
+    for (int64_t iv = 0; iv < n_dp; iv++) {
+        const int64_t q = pick[(size_t)iv];
+        W.dscore[(size_t)iv] = F.ascore[(size_t)q];
+        if (q == iv) continue;
+        const Cand &cd = F.cands[(size_t)(q - n_dp)];
+        uint32_t map[MAUVE_MAX_SEQ];
+        for (int j = 0; j < cd.k; j++) map[j] = 1u << cd.nz[(j + cd.r) % cd.k];
+        for (int64_t k = dcol_off[(size_t)iv]; k < dcol_off[(size_t)iv + 1]; k++) {
+            const uint32_t mc = dcols[(size_t)k]; uint32_t o = 0;
+            for (int j = 0; j < cd.k; j++) if (mc >> j & 1u) o |= map[j];
+            dcols[(size_t)k] = o;
+        }
     }
-    // ---- blocks ----
-    const double tb0 = now_ms();
+    return MAUVE_OK;
+}
+
+// candidates, the batch (one with device rotations, one with host rows, or -- several contexts -- the two exchanged ones), pick + fetch + remap
+int node_refine(Prog &P, NodeWork &W)
+{
+    mauve_ctx *c = P.c; const mauve_params *p = P.p;
+    const int n = W.n; const int64_t n_dp = W.n_dp;
+    const double tr0 = now_ms();
+    RefineWork F;
+    refine_candidates(P, W, F);
+    const int64_t nc = (int64_t)F.cands.size(), na = n_dp + nc;
+    const std::vector<DpSeqDesc> &all = c->prog_desc;
+    const double tr1 = now_ms();
+    F.aoff.assign((size_t)na + 1, 0); F.ascore.assign((size_t)na + 1, 0); F.asp.assign((size_t)na + 1, 0);
+    int rc;
+    if (!c->shard_on && F.rot_dev)
+        rc = dp_batch_run_desc_rot(c, n, n_dp, W.desc.data(), F.cbase.data(), na, &p->scoring, F.aoff.data(), F.ascore.data(), &W.cells, F.asp.data());
+    else if (!c->shard_on)
+        rc = dp_batch_run_desc(c, n, na, all.data(), &p->scoring, nullptr, F.aoff.data(), F.ascore.data(), &W.cells, false, F.asp.data());
+    else {
+        rc = dp_batch_run_desc(c, n, n_dp, all.data(), &p->scoring, W.dcols, F.aoff.data(), F.ascore.data(), &W.cells, true, F.asp.data());
+        if (rc) return rc;
+        if (nc) {
+            F.ccols.resize((size_t)F.ccodes + 1);
+            std::vector<int64_t> coff((size_t)nc + 1, 0);
+            int64_t cells2 = 0;
+            rc = dp_batch_run_desc(c, n, nc, all.data() + (size_t)n_dp * n, &p->scoring, F.ccols.data(), coff.data(), F.ascore.data() + n_dp, &cells2, true, F.asp.data() + n_dp);
+            if (rc) return rc;
+            W.cells += cells2;
+            for (int64_t q = 0; q <= nc; q++) F.aoff[(size_t)(n_dp + q)] = F.aoff[(size_t)n_dp] + coff[(size_t)q];
+        }
+    }
+    if (rc) return rc;
+    const double tr2 = now_ms();
+    rc = refine_pick(P, W, F);
+    if (rc) return rc;
+    if (g_trace) fprintf(stderr, "[trace] node %d: refinement: %lld candidate alignments of %lld intervals, %lld replaced; candidates %.3f ms, batch %.3f, pick + fetch + remap %.3f\n", W.node,
+                         (long long)nc, (long long)n_dp, (long long)F.replaced, tr1 - tr0, tr2 - tr1, now_ms() - tr2);
+    return MAUVE_OK;
+}
+
+// the node's pieces as blocks of the result: anchors, DP columns (local genome bits -> global ones) or, where no DP ran, the
+// stretches genome by genome; the blocks' extents leave the pools
+void node_blocks(Prog &P, NodeWork &W)
+{
+    AlignResult &R = *P.R;
+    const std::vector<int> &gm = W.gm; const int n = W.n, N = P.N;
     uint32_t gfull = 0; for (int j = 0; j < n; j++) gfull |= 1u << gm[j];
     // local genome bits -> global ones, a byte at a time
     bool same_bits = true; for (int j = 0; j < n; j++) same_bits = same_bits && gm[j] == j;
@@ -418,45 +431,74 @@ int prog_node(Prog &P, int node)
             }
     std::vector<std::vector<std::pair<int64_t, int64_t>>> placed((size_t)n);
     size_t gi = 0;
-    const int N = P.N;
-    for (size_t q = 0; q < pieces.size(); q++) {
-        const MatchVec &ch = pieces[q];
+    for (size_t q = 0; q < W.pieces.size(); q++) {
+        const MatchVec &ch = W.pieces[q];
         R.col_off.push_back((int64_t)R.cols.size());
         R.dp_score.push_back(0);
         P.n_anchor += (int64_t)ch.size(); P.n_multi++;
         for (size_t i = 0; i < ch.size(); i++) {
             R.cols.insert(R.cols.end(), (size_t)ch.len(i), gfull);
-            if (gi < gaps.size() && gaps[gi].piece == q && gaps[gi].idx == i) {
-                const GapRef &gr = gaps[gi++];
-                if (gr.dp) {
-                    const uint32_t *src = dcols + dcol_off[(size_t)gr.slot], *end = dcols + dcol_off[(size_t)gr.slot + 1];
-                    if (same_bits) R.cols.insert(R.cols.end(), src, end);               // (the root, and any node of genomes 0 .. n-1)
-                    else {
-                        const size_t at = R.cols.size();
-                        R.cols.resize(at + (size_t)(end - src));
-                        uint32_t *dst = R.cols.data() + at;
-                        for (; src < end; src++) { const uint32_t m = *src; *dst++ = lut[0][m & 255] | lut[1][m >> 8 & 255] | lut[2][m >> 16 & 255] | lut[3][m >> 24]; }
-                    }
-                    R.dp_score.back() += dscore[(size_t)gr.slot];
-                } else {
-                    for (int j = 0; j < n; j++) { int64_t lo, ln; bool rv; gap_of(ch.rec(i), ch.rec(i + 1), j, lo, ln, rv); R.cols.insert(R.cols.end(), (size_t)ln, 1u << gm[j]); }
+            if (gi >= W.gaps.size() || W.gaps[gi].lcb != (int64_t)q || W.gaps[gi].idx != (int64_t)i) continue;
+            const GapRef &gr = W.gaps[gi++];
+            if (gr.dp) {
+                const uint32_t *src = W.dcols + W.dcol_off[(size_t)gr.dp_slot], *end = W.dcols + W.dcol_off[(size_t)gr.dp_slot + 1];
+                if (same_bits) R.cols.insert(R.cols.end(), src, end);               // (the root, and any node of genomes 0 .. n-1)
+                else {
+                    const size_t at = R.cols.size();
+                    R.cols.resize(at + (size_t)(end - src));
+                    uint32_t *dst = R.cols.data() + at;
+                    for (; src < end; src++) { const uint32_t m = *src; *dst++ = lut[0][m & 255] | lut[1][m >> 8 & 255] | lut[2][m >> 16 & 255] | lut[3][m >> 24]; }
                 }
-            }
+                R.dp_score.back() += W.dscore[(size_t)gr.dp_slot];
+            } else
+                for (int j = 0; j < n; j++) { int64_t lo, ln; gap_of(ch.rec(i), ch.rec(i + 1), j, lo, ln); R.cols.insert(R.cols.end(), (size_t)ln, 1u << gm[j]); }
         }
         const size_t base = R.iv_left.size();
         R.iv_left.resize(base + N, 0); R.iv_right.resize(base + N, 0); R.iv_reverse.resize(base + N, 0);
-        const size_t last = ch.size() - 1;
         for (int j = 0; j < n; j++) {
-            const int64_t s0 = ch.st(0)[j], s1 = ch.st(last)[j];
-            int64_t le, re;
-            if (s0 > 0) { le = s0; re = s1 + ch.len(last) - 1; } else { le = -s1; re = -s0 + ch.len(0) - 1; }
-            R.iv_left[base + gm[j]] = le; R.iv_right[base + gm[j]] = re; R.iv_reverse[base + gm[j]] = s0 < 0;
+            int64_t le, re; bool rv;
+            chain_extent(ch, j, le, re, rv);
+            R.iv_left[base + gm[j]] = le; R.iv_right[base + gm[j]] = re; R.iv_reverse[base + gm[j]] = rv;
             placed[(size_t)j].push_back({le, re});
         }
     }
     for (int j = 0; j < n; j++) for (const auto &pl : placed[(size_t)j]) P.rest[gm[j]].carve(pl.first, pl.second);
+}
+
+int prog_node(Prog &P, int node)
+{
+    if (P.left[node] < 0) return MAUVE_OK;
+    mauve_ctx *c = P.c; const mauve_params *p = P.p;
+    NodeWork W; W.node = node;
+    int rc = node_search(P, W);
+    if (rc) return rc;
+    node_min_weight(P, W);
+    rc = node_chain(P, W);
+    if (rc) return rc;
+    node_pieces(P, W);
+    W.tn2 = now_ms();
+    if (p->recursive) { rc = recursive_anchoring(c, p, W.w, W.pieces, W.n, W.gm.data()); if (rc) return rc; }
+    W.tn3 = now_ms();
+    if (p->gapped) node_split_long(P, W);
+    // ---- gapped alignment of the inter-anchor intervals of this node ----
+    host_gap_table(W.pieces, W.n, W.gm.data(), p->gapped, p->max_gapped_len, W.gaps, W.desc, W.n_dp, W.code_total);
+    HIPCHK(c, c->pin_dcols.ensure(((size_t)W.code_total + 1) * sizeof(uint32_t)));
+    W.dcols = c->pin_dcols.as<uint32_t>();
+    W.dcol_off.assign((size_t)W.n_dp + 1, 0); W.dscore.assign((size_t)W.n_dp + 1, 0);
+    c->dp_band_from = INT64_MAX;            // the progressive path splits long intervals instead (DESIGN.md S11)
+    rc = p->refine_rounds > 0 && W.n >= 3 && W.n_dp > 0 ? node_refine(P, W) : node_dp_plain(P, W);
+    if (rc) return rc;
+    P.n_gap_dp += W.n_dp; P.n_cells += W.cells;
+    { const double tn4 = now_ms(); P.t_seed += W.tn1 - W.tn0; P.t_chain += W.tn2 - W.tn1; P.t_rec += W.tn3 - W.tn2; P.t_dp += tn4 - W.tn3; }
+    if (g_trace) {
+        int64_t big = 0; for (const DpSeqDesc &d : W.desc) big = std::max(big, d.len);
+        fprintf(stderr, "[trace] node %d (n=%d, pool %lld): seed %.1f ms (%lld mums), chain %.1f, recursion %.1f, dp %.1f ms (%lld intervals, %lld cells, longest side %lld)\n",
+                node, W.n, (long long)W.rest_len, W.tn1 - W.tn0, (long long)W.nm, W.tn2 - W.tn1, W.tn3 - W.tn2, now_ms() - W.tn3, (long long)W.n_dp, (long long)W.cells, (long long)big);
+    }
+    const double tb0 = now_ms();
+    node_blocks(P, W);
     P.t_blocks += now_ms() - tb0;
-    if (trace) fprintf(stderr, "[trace] node %d: blocks %.1f ms\n", node, now_ms() - tb0);
+    if (g_trace) fprintf(stderr, "[trace] node %d: blocks %.1f ms\n", node, now_ms() - tb0);
     rc = prog_node(P, P.left[node]);
     if (rc) return rc;
     return prog_node(P, P.right[node]);
@@ -591,17 +633,16 @@ static int progressive_core(mauve_ctx *c, const mauve_params *p, mauve_align_siz
     const double t0 = now_ms();
     const int N = c->nseq;
     int64_t sum = 0; for (int g = 0; g < N; g++) sum += c->lens[g];
-    int w = p->seed_weight > 0 ? p->seed_weight : mauve_default_seed_weight(sum / N);
-    uint64_t pat = p->seed_pattern ? p->seed_pattern : mauve_get_seed(w, p->seed_rank);
-    if (!pat) { c->err = "progressive_align: no seed pattern for this weight/rank"; return MAUVE_ERR_ARG; }
+    int w; uint64_t pat;
+    { const int rs = resolve_seed(c, p, sum / N, "progressive_align", &w, &pat); if (rs) return rs; }
     RepeatScope rp_scope(c);                         // whole-genome multiplicities of the root pattern, once for every node
-    { const int rr = repeat_begin(c, p, mauve_seed_weight(pat), pat); if (rr) return rr; }
+    { const int rr = repeat_begin(c, p, w, pat); if (rr) return rr; }
     Prog P; P.c = c; P.p = p; P.N = N;
     P.left.assign((size_t)(2 * N - 1), -1); P.right.assign((size_t)(2 * N - 1), -1);
     int rc = 0;
     if (given_left) { std::copy(given_left, given_left + (2 * N - 1), P.left.begin()); std::copy(given_right, given_right + (2 * N - 1), P.right.begin()); }
     const bool need_bp = p->weight_scaling && p->bp_dist_scale_ppm > 0;
-    const int64_t bp_min = p->bp_dist_min_score >= 0 ? p->bp_dist_min_score : 2 * (int64_t)mauve_seed_weight(pat);
+    const int64_t bp_min = p->bp_dist_min_score >= 0 ? p->bp_dist_min_score : 2 * (int64_t)w;
     if (need_bp) P.bpd.assign((size_t)N * N, 0);
     bool have_bp = false;
     if (!given_left) { rc = guide_tree_core(c, pat, dist, P.left.data(), P.right.data(), bp_min, need_bp ? P.bpd.data() : nullptr); have_bp = need_bp; }
@@ -618,18 +659,14 @@ static int progressive_core(mauve_ctx *c, const mauve_params *p, mauve_align_siz
             for (int64_t &v : P.bpd) v = mx ? v * 1000000 / mx : 0;
         }
     }
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = g_trace;
     const double tg1 = now_ms();
     if (trace) fprintf(stderr, "[trace] progressive: guide tree %.1f ms\n", tg1 - t0);
     if (tree_left) std::copy(P.left.begin(), P.left.end(), tree_left);
     if (tree_right) std::copy(P.right.begin(), P.right.end(), tree_right);
     AlignResult &R = c->res;
-    R.sz = mauve_align_sizes();
-    R.mum_length.clear(); R.mum_start.clear(); R.lcb_left.clear(); R.lcb_right.clear(); R.lcb_weight.clear();
-    R.anchor_length.clear(); R.anchor_start.clear(); R.anchor_lcb.clear(); R.iv_left.clear(); R.iv_right.clear();
-    R.iv_reverse.clear(); R.col_off.clear(); R.cols.clear(); R.dp_score.clear();
-    R.dev_pending = false; R.cols_pending = false; R.stale = false; R.genomes_replaced = false; R.dev_na = 0; R.dev_nm = 0; R.cols_ext = nullptr; R.cols_fill = 0; R.cols_dirty.clear();
-    R.cols_fill = 0; R.cols_dirty.clear();           // mauve_align's prefilled-buffer invariant no longer holds
+    result_reset(R);
+    R.cols.clear(); R.cols_fill = 0; R.cols_dirty.clear();           // mauve_align's prefilled-buffer invariant no longer holds
     P.R = &R;
     P.rest.assign((size_t)N, FreePool());
     for (int g = 0; g < N; g++) P.rest[(size_t)g].reset(c->lens[g]);

@@ -110,15 +110,6 @@ struct WorkList {
     const int64_t *b(size_t i) const { return &d[i * rec() + 2 + 1 + N]; }
 };
 
-inline void gap_of(const int64_t *a, const int64_t *b, int g, int64_t &lo, int64_t &len)
-{
-    const int64_t sa = a[1 + g], sb = b[1 + g];
-    int64_t hi;
-    if (sa > 0) { lo = sa + a[0]; hi = sb - 1; }
-    else { lo = -sb + b[0]; hi = -sa - 1; }
-    len = hi - lo + 1; if (len < 0) len = 0;
-}
-
 // which seed weight a gap wants at this level (0 = none), DESIGN.md S8
 inline int gap_weight(int N, const int64_t *a, const int64_t *b, int prev_w, int64_t min_gap)
 {
@@ -139,7 +130,7 @@ inline int gap_weight(int N, const int64_t *a, const int64_t *b, int prev_w, int
 
 int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector<MatchVec> &chains, int N, const int *gmap)
 {
-    const uint32_t full = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
+    const uint32_t full = full_mask(N);
     static const bool trace = getenv("MAUVE_TRACE") != nullptr;
     const double t_stage0 = now_ms();
     WorkList work(N);
@@ -152,15 +143,9 @@ int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector
         size_t off = 0;
         for (size_t l = 0; l < chains.size(); l++) {
             const size_t n = chains[l].size();
-            if (use_flags) {
-                const uint8_t *fl = flags.data() + off;
-                for (size_t i = 0; i + 1 < n; i++)
-                    if (fl[i] && gap_weight(N, chains[l].rec(i), chains[l].rec(i + 1), w0, p->min_recursive_gap))
-                        work.push((int64_t)l, w0, chains[l].rec(i), chains[l].rec(i + 1));
-            } else
-                for (size_t i = 0; i + 1 < n; i++)
-                    if (gap_weight(N, chains[l].rec(i), chains[l].rec(i + 1), w0, p->min_recursive_gap))
-                        work.push((int64_t)l, w0, chains[l].rec(i), chains[l].rec(i + 1));
+            for (size_t i = 0; i + 1 < n; i++)
+                if ((!use_flags || flags[off + i]) && gap_weight(N, chains[l].rec(i), chains[l].rec(i + 1), w0, p->min_recursive_gap))
+                    work.push((int64_t)l, w0, chains[l].rec(i), chains[l].rec(i + 1));
             off += n;
         }
     }

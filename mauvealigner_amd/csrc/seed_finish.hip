@@ -297,8 +297,7 @@ static int canon_device(mauve_ctx *ctx, const GenomeSet &gs, const SeedRequest &
     const int pos_bits = pos_bits_of(gs);
     // the bits above the position hold the first component (0 .. N-1; N = dropped).  An N-way search (mask = every genome) only
     // has matches that start in genome 0: one bit tells them from the dropped ones, which at bacterial sizes saves a sort pass
-    const uint32_t full_mask = N >= 32 ? 0xffffffffu : ((1u << N) - 1);
-    const bool nway_only = rq.mask != 0 && (uint32_t)rq.mask == full_mask && rq.mode != MAUVE_MODE_PAIRWISE;
+    const bool nway_only = rq.mask != 0 && (uint32_t)rq.mask == full_mask(N) && rq.mode != MAUVE_MODE_PAIRWISE;
     int fbits = 1; if (!nway_only) while ((1 << fbits) <= N) fbits++;
     { KernelTimer t(ctx, MAUVE_K_CANON, ncand);
       hipLaunchKernelGGL(canon_keys, dim3((ncand + 255) / 256), dim3(256), 0, ctx->stream, ctx->mlen.as<int32_t>(),

@@ -444,3 +444,15 @@ def test_host_spin_pool():
                         os.path.join(ROOT, "tests", "cpp", "workers_test.cpp"), "-o", exe], check=True)
         r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and r.stdout.strip() == "OK", r.stdout + r.stderr
+
+
+def test_host_chain_steps():
+    """csrc/host_chain.hpp (the pure steps between the seed pass and the DP stage that the align path, the progressive
+    path and the recursion share): gap_of, chain_extent, canon_less, clear_bits, full_mask and host_gap_table on hand
+    cases with the expected numbers written out.  Host-only C++, plain g++."""
+    with tempfile.TemporaryDirectory() as td:
+        exe = os.path.join(td, "host_chain_test")
+        subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "mauvealigner_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "cpp", "host_chain_test.cpp"), "-o", exe], check=True)
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout.strip() == "OK", r.stdout + r.stderr
