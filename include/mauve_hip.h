@@ -452,6 +452,39 @@ int mauve_extract_select(mauve_ctx *ctx, const mauve_extract_params *p, int64_t 
                          const int64_t *range_col, const int64_t *range_len, int64_t *n_sel);
 int mauve_extract_fetch(mauve_ctx *ctx, char *rows, int64_t row_stride,       /* rows[k*row_stride + j], row_stride >= n_sel */
                         int64_t *sel_iv, int64_t *sel_col, int64_t *range_off); /* [n_sel], [n_sel], [n_range+1]; any may be NULL */
+/* ---- pairwise column statistics of the alignment: IdentityMatrix behind --lcb-stats (mauveAligner.cpp:784-800,
+        calculateBackboneCoverage.cpp:106-127), BackboneIdentityMatrix (pairCompare.cpp:57-60,77, calculateBackboneCoverage2.cpp:98-121), the
+        pairwise loop of gappiness (gappiness.cpp:33-50) and computeSPScore (multiEVD.cpp:41-46, repeatoire.cpp:2527) -- what two rows show
+        against each other, counted on the coordinate index in force and the resident genomes.  Frozen form DESIGN.md S16.  The cell of a
+        genome in a column is the S15 cell; letter codes A, C, G, T, N -> 0..4.
+        A record is MAUVE_PAIR_STATS_WORDS int64_t for one ordered pair (a, b) over one range, with x the cell of a and y the cell of b:
+          [5*code(x) + code(y)], 0..24  columns where both have a residue
+          [25] only_a  x is a residue, y is '-'            [26] only_b  x is '-', y is a residue
+          [27] runs_a  the columns of [25] whose predecessor is missing or no only_a column; [28] runs_b the same for [26]
+          [29] neither both '-'                            [30], [31] 0
+        The predecessor is the nearest earlier column of the same range that is not a `neither` column (computeSPScore's run rule: two
+        gaps neither score nor interrupt a run, two residues end it, every range starts with no run open).  Slots 0..26 and 29 sum to
+        the range's length; the pair (b, a) is the transposed table with 25 <-> 26 and 27 <-> 28.
+        Pairs: pair_a == NULL: all nseq(nseq-1)/2 pairs a < b, row-major in the upper triangle (n_pair and pair_b are not read); else
+        1 <= n_pair <= 1024 ordered pairs, duplicates allowed.  Ranges: as for mauve_extract_select (range_iv == NULL: one range per
+        interval, all its columns; n_range = 0 and empty ranges are legal and give zeros).
+        stats: per_range = 0: [n_pair][32], every pair's sum of its per-range records (overlapping ranges count twice, runs do not cross a
+        range boundary); per_range != 0: [n_range][n_pair][32].  Page-locked stats (mauve_host_alloc) are copied directly.  All counts are
+        integers and independent of any tiling: two calls return identical bytes.  The call neither needs nor disturbs the extract
+        selection in force.
+        MAUVE_ERR_ARG: n_pair outside [1, 1024], a == b or an id outside [0, nseq), and the range errors of mauve_extract_select;
+        MAUVE_ERR_LIMIT: more than 2^24 records; MAUVE_ERR_STATE: as for mauve_extract_select.
+        Derived on the host, without a context, for n_rec records:
+        mauve_pair_stats_identity: (s[0] + s[6] + s[12] + s[18] + s[24]) / the sum of s[0..24], 0.0 when that sum is 0 (IdentityMatrix's
+          rule: N against N counts as equal there too);
+        mauve_pair_stats_sp_score: the sum of s[5x+y] * matrix[x'][y'] + gap_open * (s[27] + s[28]) + gap_extend * (s[25] + s[26] - s[27] - s[28]),
+          N scoring as A (x' = x < 4 ? x : 0): the pair's share of computeSPScore of the range's rows. ---- */
+#define MAUVE_PAIR_STATS_WORDS 32
+int mauve_pair_stats(mauve_ctx *ctx, int64_t n_pair, const int32_t *pair_a, const int32_t *pair_b,
+                     int64_t n_range, const int64_t *range_iv, const int64_t *range_col, const int64_t *range_len,
+                     int per_range, int64_t *stats);
+void mauve_pair_stats_identity(const int64_t *stats, int64_t n_rec, double *identity);
+void mauve_pair_stats_sp_score(const int64_t *stats, int64_t n_rec, const mauve_scoring *sc, int64_t *score);
 /* IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760; format mfa2xmfa.cpp:64-115).
    Two-phase: buf == NULL returns the needed size (including NUL) in *len. */
 int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_t *len);

@@ -34,6 +34,7 @@ EXPORTS = [
     "mauve_set_repeat_penalty", "mauve_seed_multiplicity", "mauve_match_sp_scores_repeat",
     "mauve_coord_index", "mauve_coord_index_alignment", "mauve_coord_index_size", "mauve_column_positions", "mauve_seqpos_to_column", "mauve_translate_positions",
     "mauve_default_extract_params", "mauve_extract_select", "mauve_extract_fetch",
+    "mauve_pair_stats", "mauve_pair_stats_identity", "mauve_pair_stats_sp_score",
 ]
 
 
@@ -209,6 +210,37 @@ def default_scoring():
     s = Scoring()
     load().mauve_default_scoring(C.byref(s))
     return s
+
+
+PAIR_STATS_WORDS = 32                 # MAUVE_PAIR_STATS_WORDS: int64 per record
+
+
+def pair_stats_identity(stats):
+    """mauve_pair_stats_identity (host entry, no context): records [..., 32] -> identity [...] (equal letters / columns where both have a residue)"""
+    st = np.ascontiguousarray(stats, np.int64)
+    if st.ndim < 1 or st.shape[-1] != PAIR_STATS_WORDS:
+        raise ValueError("pair_stats_identity: records of %d int64 expected" % PAIR_STATS_WORDS)
+    out = np.zeros(st.shape[:-1], np.float64)
+    L = load()
+    L.mauve_pair_stats_identity.restype = None
+    if out.size:
+        L.mauve_pair_stats_identity(_p(st, C.c_int64), C.c_int64(out.size), _p(out, C.c_double))
+    return out
+
+
+def pair_stats_sp_score(stats, scoring=None):
+    """mauve_pair_stats_sp_score (host entry, no context): records [..., 32] -> the pairs' sum-of-pairs scores [...] under `scoring` (a
+    Scoring, None = the default)"""
+    st = np.ascontiguousarray(stats, np.int64)
+    if st.ndim < 1 or st.shape[-1] != PAIR_STATS_WORDS:
+        raise ValueError("pair_stats_sp_score: records of %d int64 expected" % PAIR_STATS_WORDS)
+    sc = scoring if scoring is not None else default_scoring()
+    out = np.zeros(st.shape[:-1], np.int64)
+    L = load()
+    L.mauve_pair_stats_sp_score.restype = None
+    if out.size:
+        L.mauve_pair_stats_sp_score(_p(st, C.c_int64), C.c_int64(out.size), C.byref(sc), _p(out, C.c_int64))
+    return out
 
 
 def pack_codes(codes):
@@ -879,6 +911,37 @@ class Context:
             require = sum(1 << int(g) for g in require)
         self.extract_select(keep, require, drop_empty, polymorphic, ranges)
         return self.extract_fetch(out)
+
+    # ---- pairwise column statistics ----
+    def pair_stats(self, pairs=None, ranges=None, per_range=False, out=None):
+        """mauve_pair_stats: what two rows of the alignment show against each other -> int64 records [n_pair, 32], with per_range
+        [n_range, n_pair, 32].  pairs = (a, b) id arrays of ordered pairs (None: all pairs a < b, row-major), ranges as for
+        extract_select (None: every interval whole), out = the result array (e.g. from pinned_empty: copied without staging)."""
+        N = self.coord_index_size()[0]
+        z8, z4 = np.zeros(1, np.int64), np.zeros(1, np.int32)
+        if pairs is None:
+            n_pair, args_p = N * (N - 1) // 2, (C.c_int64(0), None, None)
+        else:
+            pa, pb = (np.ascontiguousarray(x, np.int32) for x in pairs)
+            if pa.ndim != 1 or pa.shape != pb.shape:
+                raise ValueError("pair_stats: the pair arrays differ in length")
+            n_pair, args_p = len(pa), (C.c_int64(len(pa)), _p(pa if len(pa) else z4, C.c_int32), _p(pb if len(pa) else z4, C.c_int32))
+        if ranges is None:
+            n_range, args_r = self.coord_index_size()[1], (C.c_int64(0), None, None, None)
+        else:
+            iv, col, ln = (np.ascontiguousarray(x, np.int64) for x in ranges)
+            if not (len(iv) == len(col) == len(ln)):
+                raise ValueError("pair_stats: the range arrays differ in length")
+            n_range = len(iv)
+            args_r = (C.c_int64(n_range), _p(iv if n_range else z8, C.c_int64), _p(col if n_range else z8, C.c_int64), _p(ln if n_range else z8, C.c_int64))
+        shape = (n_range, n_pair, PAIR_STATS_WORDS) if per_range else (n_pair, PAIR_STATS_WORDS)
+        if n_pair > 1024 or n_pair * (n_range if per_range else 1) > 1 << 24:
+            # the library refuses these before it writes a record: nothing to allocate, and its error comes before any word about `out`
+            self._chk(self.L.mauve_pair_stats(self.h, *args_p, *args_r, C.c_int(int(bool(per_range))), _p(z8, C.c_int64)), "mauve_pair_stats")
+            raise RuntimeError("mauve_pair_stats accepted a request beyond its limits")
+        st = self._co_out((out,), 0, shape, np.int64) if out is not None else np.zeros(shape, np.int64)
+        self._chk(self.L.mauve_pair_stats(self.h, *args_p, *args_r, C.c_int(int(bool(per_range))), _p(st if st.size else z8, C.c_int64)), "mauve_pair_stats")
+        return st
 
     def stage_times(self):
         t = StageTimes()

@@ -277,6 +277,10 @@ struct mauve_ctx {
     } ex;
     DevBuf ex_work, ex_bits, ex_sel, ex_mat;   // ranges and their scan; flag words and their scan; sel_iv | sel_col | range_off; the matrix (padded pitch)
     PinnedBuf pin_ex;                    // ranges on their way in, counts and the error flag coming back, staging of pageable outputs
+    // pairwise column statistics (pairstat_dev.hip): no state between calls, work buffers apart from the selection's
+    DevBuf ps_work, ps_out;              // flag words, ranges, their units' scan, the pair lists; the records
+    PinnedBuf pin_ps;                    // ranges and pairs on their way in, the unit count and the error flag coming back; pageable records are
+                                         // staged through pin_ex (ex_copy_out), where the extract stage keeps nothing between calls
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them
     DevBuf rec_genomes, rec_seg;         // recursive anchoring: gap sub-sequences + segment table
