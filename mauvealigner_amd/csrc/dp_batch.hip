@@ -41,6 +41,20 @@ struct DpMeta {
 
 struct DpScoring { int32_t go, ge; int32_t s[4][4]; };
 
+// One profile row against each base, and the cost of opening / extending a gap across it: the sum-of-pairs scores of the row's packed
+// base counts cn (a byte per base).  Six named values, into registers of the caller's: a struct of them that a caller selects from
+// by a base's bits ends up as a runtime-indexed array, and that goes to scratch.
+__device__ __forceinline__ void dp_row_coef(uint32_t cn, const DpScoring &sc, int32_t &s0, int32_t &s1, int32_t &s2, int32_t &s3, int32_t &gxo, int32_t &gxe)
+{
+    const int32_t c0 = cn & 255, c1 = (cn >> 8) & 255, c2 = (cn >> 16) & 255, c3 = cn >> 24;
+    const int32_t rr = c0 + c1 + c2 + c3;
+    s0 = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
+    s1 = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
+    s2 = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
+    s3 = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
+    gxo = sc.go * rr; gxe = sc.ge * rr;
+}
+
 // what every DP kernel takes behind its list: the bases, the per-interval records, both profile buffers, traceback, parked rows, reversed ops, scores.
 // The kernels take them as __restrict__ pointer parameters and put them into this record on entry; the interval functions take the record.  (As
 // the kernel argument itself the record would carry no __restrict__: dp_step_wide then needs 17 more registers and loses a wave per SIMD.)
@@ -291,16 +305,7 @@ __device__ __forceinline__ void dp_stripe_begin(DpStripe &S, int32_t s, int lane
     F.s = s; S.m = m; F.n = n; F.seq = seq;
     S.i = s * 64 + lane + 1;
     S.active = S.i <= m;
-    const uint32_t cn = S.active ? Pc[S.i - 1] : 0u;
-    const int32_t c0 = cn & 255, c1 = (cn >> 8) & 255, c2 = (cn >> 16) & 255, c3 = cn >> 24;
-    const int32_t r = c0 + c1 + c2 + c3;
-    // sum-of-pairs substitution score of this profile column against each base (named registers: a
-    // runtime-indexed array would go to scratch)
-    S.sub0 = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-    S.sub1 = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-    S.sub2 = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-    S.sub3 = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-    S.gxo = sc.go * r; S.gxe = sc.ge * r;
+    dp_row_coef(S.active ? Pc[S.i - 1] : 0u, sc, S.sub0, S.sub1, S.sub2, S.sub3, S.gxo, S.gxe);
     F.gyo = sc.go * krows; F.gye = sc.ge * krows;
     F.rin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (n + 1);      // written by stripe s-1
     S.rout = rowbuf + (size_t)(s & 1) * 3 * (n + 1);
@@ -490,6 +495,17 @@ constexpr int DP2_REC = 16 * (16 + DP2_T);       // per wave: reversed op record
 constexpr int DP2_SEQ = 16 * (DP2_T + 4);        // per wave: the groups' sequences, each behind G bytes of padding
 constexpr int DP2_WAVES = 2;                     // waves per workgroup (40 KB of LDS: four workgroups per CU)
 
+// of a lane's R rows (or columns) the one with index ro: where the final cell sits.  L: Dp2Rows, DpScanA or DpScanB (the whole record, not
+// its three arrays: with those as parameters the compiler turns the selects into an index and the record goes to scratch)
+template <class Rows>
+__device__ __forceinline__ void dp_row_pick(const Rows &L, int ro, int32_t &m_, int32_t &x_, int32_t &y_)
+{
+    constexpr int R = sizeof(L.M) / sizeof(int32_t);
+    m_ = L.M[0]; x_ = L.X[0]; y_ = L.Y[0];
+#pragma unroll
+    for (int r = 1; r < R; r++) if (ro == r) { m_ = L.M[r]; x_ = L.X[r]; y_ = L.Y[r]; }
+}
+
 template <int R>
 struct Dp2Rows {
     int32_t M[R], X[R], Y[R];                    // column j-1 before a step, column j after it
@@ -498,14 +514,7 @@ struct Dp2Rows {
     {
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            const uint32_t cn = i0 + r < m ? Pc[i0 + r] : 0u;         // rows beyond the profile: zeros (their cells feed nothing)
-            const int32_t c0 = cn & 255, c1 = (cn >> 8) & 255, c2 = (cn >> 16) & 255, c3 = cn >> 24;
-            const int32_t rr = c0 + c1 + c2 + c3;
-            s0[r] = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-            s1[r] = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-            s2[r] = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-            s3[r] = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-            gxo[r] = sc.go * rr; gxe[r] = sc.ge * rr;
+            dp_row_coef(i0 + r < m ? Pc[i0 + r] : 0u, sc, s0[r], s1[r], s2[r], s3[r], gxo[r], gxe[r]);     // rows beyond the profile: zeros (their cells feed nothing)
             M[r] = X[r] = Y[r] = DP_NEG_INF;
         }
     }
@@ -538,12 +547,7 @@ struct Dp2Rows {
         }
         return tb;
     }
-    __device__ __forceinline__ void row(int ro, int32_t &m_, int32_t &x_, int32_t &y_) const
-    {
-        m_ = M[0]; x_ = X[0]; y_ = Y[0];
-#pragma unroll
-        for (int r = 1; r < R; r++) if (ro == r) { m_ = M[r]; x_ = X[r]; y_ = Y[r]; }
-    }
+    __device__ __forceinline__ void row(int ro, int32_t &m_, int32_t &x_, int32_t &y_) const { dp_row_pick(*this, ro, m_, x_, y_); }
 };
 
 // ---- sub-wave groups: 64 / G intervals per wave, G lanes x R rows each, everything of a step in LDS ----
@@ -850,128 +854,6 @@ __host__ __device__ __forceinline__ int64_t dp3_scan_steps(int64_t m, int64_t n)
     return a < b ? a : b;
 }
 
-template <int R>
-struct Dp3A {
-    int32_t M[R], X[R], Y[R];
-    int32_t s0[R], s1[R], s2[R], s3[R], gxo[R], gxe[R], E;
-    __device__ __forceinline__ void constants(const uint32_t *Pc, int32_t i0, int32_t m, const DpScoring &sc)
-    {
-        int32_t bsum = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t cn = i0 + r < m ? Pc[i0 + r] : 0u;
-            const int32_t c0 = cn & 255, c1 = (cn >> 8) & 255, c2 = (cn >> 16) & 255, c3 = cn >> 24;
-            const int32_t rr = c0 + c1 + c2 + c3;
-            s0[r] = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-            s1[r] = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-            s2[r] = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-            s3[r] = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-            gxo[r] = sc.go * rr; gxe[r] = sc.ge * rr; bsum += gxe[r];
-            M[r] = X[r] = Y[r] = DP_NEG_INF;
-        }
-        E = wave_prefix_sum(bsum);
-    }
-    // column j from column j - 1.  b: base of column j (wave-uniform); t?o / t?n: the row above the band at columns j - 1 / j.
-    // (J1: j >= 1.  Column 0 has no M and no Y; it is peeled off the sweep's loop so that the other columns do not pay eight selects for it.)
-    template <bool J1>
-    __device__ __forceinline__ uint32_t step(uint32_t b, int32_t gyo, int32_t gye, int32_t tMo, int32_t tXo, int32_t tYo,
-                                             int32_t tMn, int32_t tXn, int32_t tYn)
-    {
-        constexpr bool j1 = J1;
-        int32_t Md = lane0_set(wave_shr1z(M[R - 1]), tMo), Xd = lane0_set(wave_shr1z(X[R - 1]), tXo), Yd = lane0_set(wave_shr1z(Y[R - 1]), tYo);
-        const bool lo = (b & 1u) != 0, hi = (b & 2u) != 0;
-        int32_t Mn[R], Yn[R];
-        uint32_t tb = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int32_t bd = max(max(Md, Xd), Yd);
-            const uint32_t pm = Md == bd ? 0u : (Xd == bd ? 1u : 2u);
-            const int32_t sa = lo ? s1[r] : s0[r], sb = lo ? s3[r] : s2[r];
-            const int32_t mv = max(bd + (hi ? sb : sa), DP_NEG_INF);
-            const int32_t ya = M[r] + gyo, yb = X[r] + gyo, yc = Y[r] + gye;
-            const int32_t by = max(max(ya, yb), yc);
-            const uint32_t py = ya == by ? 0u : (yb == by ? 16u : 32u);
-            Mn[r] = j1 ? mv : DP_NEG_INF; Yn[r] = j1 ? max(by, DP_NEG_INF) : DP_NEG_INF;
-            tb |= (pm | py) << (8 * r);
-            Md = M[r]; Xd = X[r]; Yd = Y[r];
-        }
-        // the scanned state: local chains, one prefix maximum over the lanes, then the cells with their real carry-in
-        const int32_t Mu0 = lane0_set(wave_shr1z(Mn[R - 1]), tMn), Yu0 = lane0_set(wave_shr1z(Yn[R - 1]), tYn);
-        int32_t a = DP_NEG_INF, Mu = Mu0, Yu = Yu0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int32_t t = max(Mu, Yu) + gxo[r];
-            a = r == 0 ? max(t, DP_NEG_INF) : max(max(t, a + gxe[r]), DP_NEG_INF);
-            Mu = Mn[r]; Yu = Yn[r];
-        }
-        const int32_t pv = wave_prefix_max(a - E);
-        const int32_t xout = max(E + pv, tXn + E);
-        int32_t Xu = lane0_set(wave_shr1z(xout), tXn);
-        Mu = Mu0; Yu = Yu0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int32_t xa = Mu + gxo[r], xb = Xu + gxe[r], xc = Yu + gxo[r];
-            const int32_t bx = max(max(xa, xb), xc);
-            const uint32_t px = xa == bx ? 0u : (xb == bx ? 4u : 8u);
-            tb |= px << (8 * r);
-            Xu = max(bx, DP_NEG_INF);
-            X[r] = Xu; Mu = Mn[r]; Yu = Yn[r]; M[r] = Mn[r]; Y[r] = Yn[r];
-        }
-        return tb;
-    }
-};
-
-template <int R>
-struct Dp3B {
-    int32_t M[R], X[R], Y[R];
-    uint32_t bases;                                        // 2 bits per column of the lane
-    int32_t E;
-    // row i from row i - 1.  s0..s3, gxo, gxe: the profile row (wave-uniform); l?o / l?n: the column left of the band at rows i - 1 / i.
-    __device__ __forceinline__ uint32_t step(int32_t s0, int32_t s1, int32_t s2, int32_t s3, int32_t gxo, int32_t gxe, int32_t gyo, int32_t gye,
-                                             int32_t lMo, int32_t lXo, int32_t lYo, int32_t lMn, int32_t lXn, int32_t lYn)
-    {
-        int32_t Md = lane0_set(wave_shr1z(M[R - 1]), lMo), Xd = lane0_set(wave_shr1z(X[R - 1]), lXo), Yd = lane0_set(wave_shr1z(Y[R - 1]), lYo);
-        int32_t Mn[R], Xn[R];
-        uint32_t tb = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int32_t bd = max(max(Md, Xd), Yd);
-            const uint32_t pm = Md == bd ? 0u : (Xd == bd ? 1u : 2u);
-            const uint32_t b = (bases >> (2 * r)) & 3u;
-            const int32_t sa = (b & 1u) ? s1 : s0, sb = (b & 1u) ? s3 : s2;
-            Mn[r] = max(bd + ((b & 2u) ? sb : sa), DP_NEG_INF);
-            const int32_t xa = M[r] + gxo, xb = X[r] + gxe, xc = Y[r] + gxo;
-            const int32_t bx = max(max(xa, xb), xc);
-            const uint32_t px = xa == bx ? 0u : (xb == bx ? 4u : 8u);
-            Xn[r] = max(bx, DP_NEG_INF);
-            tb |= (pm | px) << (8 * r);
-            Md = M[r]; Xd = X[r]; Yd = Y[r];
-        }
-        const int32_t Ml0 = lane0_set(wave_shr1z(Mn[R - 1]), lMn), Xl0 = lane0_set(wave_shr1z(Xn[R - 1]), lXn);
-        int32_t a = DP_NEG_INF, Ml = Ml0, Xl = Xl0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int32_t t = max(Ml, Xl) + gyo;
-            a = r == 0 ? max(t, DP_NEG_INF) : max(max(t, a + gye), DP_NEG_INF);
-            Ml = Mn[r]; Xl = Xn[r];
-        }
-        const int32_t pv = wave_prefix_max(a - E);
-        const int32_t yout = max(E + pv, lYn + E);
-        int32_t Yl = lane0_set(wave_shr1z(yout), lYn);
-        Ml = Ml0; Xl = Xl0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const int32_t ya = Ml + gyo, yb = Xl + gyo, yc = Yl + gye;
-            const int32_t by = max(max(ya, yb), yc);
-            const uint32_t py = ya == by ? 0u : (yb == by ? 16u : 32u);
-            tb |= py << (8 * r);
-            Yl = max(by, DP_NEG_INF);
-            Y[r] = Yl; Ml = Mn[r]; Xl = Xn[r]; M[r] = Mn[r]; X[r] = Xn[r];
-        }
-        return tb;
-    }
-};
-
 // Traceback of one step, all lanes together: from (ti, tj) in `state` the wave looks 64 cells ahead along the state's own
 // direction (M: the diagonal, X: up, Y: left) -- lane l reads the byte of cell l -- and a ballot tells how long the run of
 // "the predecessor is the same state again" is: a gap of 6.7 kb is a hundred ballots, not 6.7 k dependent loads.  The bytes
@@ -1050,200 +932,9 @@ __host__ __device__ __forceinline__ bool dp3_admissible(int64_t total_len, int64
     return total_len * krows_max * (a > b ? a : b) < (1LL << 28) && ge <= 0 && go <= 0;
 }
 
-// orientation A, all bands: rows on the lanes (R per lane, bands of 64 R), column by column.  Leaves (m, n) in fM / fX / fY.
-template <int R>
-__device__ __forceinline__ void dp3_sweep_a(int lane, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows,
-                                            int32_t *rowbuf, uint8_t *tbp, int32_t mpad, int32_t &fM, int32_t &fX, int32_t &fY)
-{
-    constexpr int BAND = 64 * R;
-    const int32_t nbands = (m + BAND - 1) / BAND;
-    const int32_t gyo = sc.go * krows, gye = sc.ge * krows;
-    for (int32_t s = 0; s < nbands; s++) {
-        Dp3A<R> L;
-        const int32_t i0 = s * BAND + lane * R;                      // 0-based first row of the lane
-        L.constants(Pc, i0, m, sc);
-        const int32_t *rin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (n + 1);
-        int32_t *rout = rowbuf + (size_t)(s & 1) * 3 * (n + 1);
-        const bool park = s + 1 < nbands, writes = (s * 64 + lane) * 4 < mpad;
-        // What a column needs from outside the band -- its base, and (bands below the first) the parked row of the band above --
-        // is fetched by the whole wave 64 columns at a time, one chunk ahead, and handed out with v_readlane: a load per
-        // column would put a memory round trip into every step.  Chunk k: lane l holds column 64 k + l.
-        auto chunk = [&](int32_t k, uint32_t &sq, int32_t &cM, int32_t &cX, int32_t &cY) {
-            const int32_t col = 64 * k + lane;
-            sq = (uint32_t)seq[min(max(col - 1, 0), n - 1)];
-            if (s == 0) { cM = col == 0 ? 0 : DP_NEG_INF; cX = DP_NEG_INF; cY = col == 0 ? DP_NEG_INF : gyo + (col - 1) * gye; }
-            else { const int32_t cc = min(col, n); cM = rin[cc]; cX = rin[(n + 1) + cc]; cY = rin[2 * (n + 1) + cc]; }
-        };
-        uint32_t sq_cur, sq_nxt; int32_t cM_cur, cX_cur, cY_cur, cM_nxt, cX_nxt, cY_nxt;
-        chunk(0, sq_nxt, cM_nxt, cX_nxt, cY_nxt);
-        int32_t tMo = DP_NEG_INF, tXo = DP_NEG_INF, tYo = DP_NEG_INF;
-        uint8_t *tw = tbp + (size_t)(s * 64 + lane) * 4;
-        for (int32_t k = 0; 64 * k <= n; k++) {
-            sq_cur = sq_nxt; cM_cur = cM_nxt; cX_cur = cX_nxt; cY_cur = cY_nxt;
-            chunk(k + 1, sq_nxt, cM_nxt, cX_nxt, cY_nxt);
-            const int32_t jend = min(64 * k + 63, n);
-            auto line = [&](int32_t j, auto first) {
-                const int sel = j & 63;
-                const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int32_t)sq_cur, sel);
-                const int32_t tMn = __builtin_amdgcn_readlane(cM_cur, sel), tXn = __builtin_amdgcn_readlane(cX_cur, sel),
-                              tYn = __builtin_amdgcn_readlane(cY_cur, sel);
-                const uint32_t tbw = L.template step<!decltype(first)::value>(b, gyo, gye, tMo, tXo, tYo, tMn, tXn, tYn);
-                if (writes) *reinterpret_cast<uint32_t *>(tw) = tbw;
-                if (park && lane == 63) { rout[j] = L.M[R - 1]; rout[(n + 1) + j] = L.X[R - 1]; rout[2 * (n + 1) + j] = L.Y[R - 1]; }
-                tMo = tMn; tXo = tXn; tYo = tYn;
-            };
-            int32_t j = 64 * k;
-            if (k == 0) { line(0, std::true_type()); j = 1; tw += mpad; }           // column 0, peeled
-            for (; j <= jend; j++, tw += mpad) line(j, std::false_type());
-        }
-        __threadfence_block();
-        if (s == nbands - 1) {
-            int32_t a = L.M[0], b2 = L.X[0], c2 = L.Y[0];
-#pragma unroll
-            for (int r = 1; r < R; r++) if (((m - 1) % R) == r) { a = L.M[r]; b2 = L.X[r]; c2 = L.Y[r]; }
-            const int owner = ((m - 1) % BAND) / R;
-            fM = __shfl(a, owner); fX = __shfl(b2, owner); fY = __shfl(c2, owner);
-        }
-    }
-}
-
-// orientation B, all bands: columns on the lanes, row by row
-template <int R>
-__device__ __forceinline__ void dp3_sweep_b(int lane, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows,
-                                            int32_t *rowbuf, uint8_t *tbp, int32_t npad, int32_t &fM, int32_t &fX, int32_t &fY)
-{
-    constexpr int BAND = 64 * R;
-    const int32_t nbands = (n + BAND - 1) / BAND;
-    const int32_t gyo = sc.go * krows, gye = sc.ge * krows;
-    for (int32_t s = 0; s < nbands; s++) {
-        Dp3B<R> L;
-        const int32_t j0 = s * BAND + lane * R;                      // 0-based first column index (j - 1) of the lane
-        L.bases = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            L.bases |= (uint32_t)(j0 + r < n ? seq[j0 + r] : 0) << (2 * r);
-            // row 0: only Y exists (analytic, not clamped: the anti-diagonal sweeps' boundary row)
-            L.M[r] = DP_NEG_INF; L.X[r] = DP_NEG_INF; L.Y[r] = gyo + (j0 + r) * gye;
-        }
-        L.E = (lane + 1) * R * gye;
-        const int32_t *cin = rowbuf + (size_t)((s & 1) ^ 1) * 3 * (m + 1);
-        int32_t *cout = rowbuf + (size_t)(s & 1) * 3 * (m + 1);
-        const bool park = s + 1 < nbands, writes = (s * 64 + lane) * 4 < npad;
-        // per row from outside the band: the profile column's counts and (bands right of the first) the parked column of the
-        // band to the left -- fetched 64 rows at a time, one chunk ahead (see orientation A).  Chunk k: lane l holds row 64 k + l + 1.
-        auto chunk = [&](int32_t k, uint32_t &pc, int32_t &cM, int32_t &cX, int32_t &cY) {
-            const int32_t row = min(64 * k + lane + 1, m);
-            pc = Pc[row - 1];
-            if (s == 0) { cM = cX = cY = DP_NEG_INF; }
-            else { cM = cin[row]; cX = cin[(m + 1) + row]; cY = cin[2 * (m + 1) + row]; }
-        };
-        // column 0 (band 0): M and Y do not exist there, X is the chain down from (0, 0)
-        int32_t lMo, lXo, lYo;
-        if (s == 0) { lMo = 0; lXo = DP_NEG_INF; lYo = DP_NEG_INF; }
-        else { lMo = __builtin_amdgcn_readfirstlane(cin[0]); lXo = __builtin_amdgcn_readfirstlane(cin[(m + 1)]); lYo = __builtin_amdgcn_readfirstlane(cin[2 * (m + 1)]); }
-        if (park && lane == 63) { cout[0] = L.M[R - 1]; cout[(m + 1)] = L.X[R - 1]; cout[2 * (m + 1)] = L.Y[R - 1]; }    // row 0 of the band's last column
-        uint32_t pc_cur, pc_nxt; int32_t cM_cur, cX_cur, cY_cur, cM_nxt, cX_nxt, cY_nxt;
-        chunk(0, pc_nxt, cM_nxt, cX_nxt, cY_nxt);
-        uint8_t *tw = tbp + (size_t)(s * 64 + lane) * 4;
-        for (int32_t k = 0; 64 * k < m; k++) {
-            pc_cur = pc_nxt; cM_cur = cM_nxt; cX_cur = cX_nxt; cY_cur = cY_nxt;
-            chunk(k + 1, pc_nxt, cM_nxt, cX_nxt, cY_nxt);
-            const int32_t iend = min(64 * k + 64, m);
-            for (int32_t i = 64 * k + 1; i <= iend; i++, tw += npad) {
-                const int sel = (i - 1) & 63;
-                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int32_t)pc_cur, sel);
-                const int32_t c0 = c & 255, c1 = (c >> 8) & 255, c2 = (c >> 16) & 255, c3 = c >> 24, rr = c0 + c1 + c2 + c3;
-                const int32_t s0 = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-                const int32_t s1 = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-                const int32_t s2 = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-                const int32_t s3 = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-                const int32_t gxo = sc.go * rr, gxe = sc.ge * rr;
-                int32_t lMn, lXn, lYn;
-                if (s == 0) {
-                    const int32_t xa = lMo + gxo, xb = lXo + gxe, xc = lYo + gxo, bx = max(max(xa, xb), xc);
-                    lMn = DP_NEG_INF; lYn = DP_NEG_INF; lXn = max(bx, DP_NEG_INF);
-                } else { lMn = __builtin_amdgcn_readlane(cM_cur, sel); lXn = __builtin_amdgcn_readlane(cX_cur, sel); lYn = __builtin_amdgcn_readlane(cY_cur, sel); }
-                const uint32_t tbw = L.step(s0, s1, s2, s3, gxo, gxe, gyo, gye, lMo, lXo, lYo, lMn, lXn, lYn);
-                if (writes) *reinterpret_cast<uint32_t *>(tw) = tbw;
-                if (park && lane == 63) { cout[i] = L.M[R - 1]; cout[(m + 1) + i] = L.X[R - 1]; cout[2 * (m + 1) + i] = L.Y[R - 1]; }
-                lMo = lMn; lXo = lXn; lYo = lYn;
-            }
-        }
-        __threadfence_block();
-        if (s == nbands - 1) {
-            int32_t a = L.M[0], b2 = L.X[0], c2 = L.Y[0];
-#pragma unroll
-            for (int r = 1; r < R; r++) if (((n - 1) % R) == r) { a = L.M[r]; b2 = L.X[r]; c2 = L.Y[r]; }
-            const int owner = ((n - 1) % BAND) / R;
-            fM = __shfl(a, owner); fX = __shfl(b2, owner); fY = __shfl(c2, owner);
-        }
-    }
-}
-
-// The layout of one step on one wave: the orientation by cost, as few rows (A) / columns (B) per lane as cover the dimension with the 64 lanes, at most 4
-// (then bands).  A: line j at tbp + j * stride; B: line i - 1 at tbp + (i - 1) * stride.
-__device__ __forceinline__ void dp3_layout(Dp3Walk &W, const uint8_t *tbp, int32_t m, int32_t n)
-{
-    W.tb = tbp; W.orient_b = dp3_orient_b(m, n);
-    const int32_t ldim = W.orient_b ? n : m;
-    W.R = dp3_rows_per_lane(ldim); W.stride = dp3_pad(ldim);
-}
-// ... and the sweep in that layout, by one wave.  Leaves (m, n) in fM / fX / fY.
-__device__ __forceinline__ void dp3_sweep(const Dp3Walk &W, int lane, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows,
-                                          int32_t *rowbuf, uint8_t *tbp, int32_t &fM, int32_t &fX, int32_t &fY)
-{
-    const int32_t pad = (int32_t)W.stride;
-    if (!W.orient_b) {
-        if (W.R == 1) dp3_sweep_a<1>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
-        else if (W.R == 2) dp3_sweep_a<2>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
-        else dp3_sweep_a<4>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
-    } else {
-        if (W.R == 1) dp3_sweep_b<1>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
-        else if (W.R == 2) dp3_sweep_b<2>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
-        else dp3_sweep_b<4>(lane, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, fM, fX, fY);
-    }
-}
-
-__device__ void dp3_interval(int nseq, int64_t iv, const DpBufs &B, uint8_t *win)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t *seq_off = B.seq_off;
-    DpMeta mt = dp_meta_zero();
-    const int64_t base = seq_off[iv * nseq];
-    for (int g = 0; g < nseq; g++) {
-        const int64_t so = seq_off[iv * nseq + g];
-        const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
-        if (n == 0) continue;
-        const uint8_t *seq = B.codes + so;
-        const DpStep P = dp_step_ptrs(B, mt, base);
-        if (mt.krows == 0) {
-            dp_first_profile<64>(P, seq, n, g, lane);
-            mt.m = n; mt.krows = 1;
-            __threadfence_block();
-            continue;
-        }
-        const int32_t m = mt.m;
-        int32_t fM = DP_NEG_INF, fX = DP_NEG_INF, fY = DP_NEG_INF;   // values at (m, n)
-        uint8_t *tbp = B.tb + B.tb_off[iv];
-        Dp3Walk W; W.win = win; W.cap = DP2_TB_DW * 4;
-        dp3_layout(W, tbp, m, n);
-        dp3_sweep(W, lane, m, n, P.Pc, seq, B.sc, mt.krows, B.rows + B.rows_off[iv], tbp, fM, fX, fY);
-        int state;
-        const int32_t best = dp_pick_state(fM, fX, fY, state);
-        uint8_t *opr = B.ops + base;                       // reversed ops, capacity m + n
-        const int32_t len = dp3_walk(W, m, n, state, opr, lane);
-        __threadfence_block();
-        dp_rebuild<1>(P, opr, len, seq, g, lane, 0);
-        dp_step_done(mt, (int64_t)m * n, best, len);
-        __threadfence_block();
-    }
-    if (lane == 0) B.meta[iv] = mt;
-}
-
-
 // ================================================================================================================
 // Wide sweep: ONE interval over the 16 waves of a workgroup, all of them on the same column (A) / row (B) at the same time.
-// A single wave takes bands(m) x (n + 1) dependent column steps for a step of the progressive alignment (dp3_sweep_a: the bands
+// A single wave takes bands(m) x (n + 1) dependent column steps for a step of the progressive alignment (dp_sweep_a<R, 1>: the bands
 // one after the other); the largest interval of a launch -- 1 600 x 1 600 at C5, a 6.7 kb insertion in five of eight genomes at
 // C4 -- then IS the launch (C5: 4.2 of 5.8 ms for one interval of 302 000).  The scan formulation has no such chain across the
 // bands: M and the element-wise gap state of column j read column j - 1 only, and the scanned state is a max-plus prefix over
@@ -1251,8 +942,8 @@ __device__ void dp3_interval(int nseq, int64_t iv, const DpBufs &B, uint8_t *win
 // element-wise cells and publishes its last row (barrier), every wave scans its rows with E the prefix sums over the whole
 // super-band and publishes its aggregate max(a - E) (barrier), every wave folds the aggregates of the waves above into its
 // carry -- which also is, plus a constant, the scanned value of the row above its first one, so nothing else has to cross --
-// and finishes its cells.  Two barriers per column, no dependent chain across waves.  The arithmetic is dp3's (same clamp, same
-// tie rules; E stays far from the clamp for every interval dp3_admissible lets in), the traceback layout is dp3's with R = 4
+// and finishes its cells.  Two barriers per column, no dependent chain across waves.  The arithmetic is the one-wave sweep's (the same code: DpScanA / DpScanB;
+// E stays far from the clamp for every interval dp3_admissible lets in), the traceback layout is the one-wave sweep's with R = 4
 // (wave w of super-band q is band 16 q + w), so dp3_walk reads it; steps small in both dimensions run the one-wave sweep.
 // ================================================================================================================
 constexpr int DPW_MAXW = 8;                       // waves of a workgroup (one shape is built: 8 waves x 4 rows per lane, a super-band of 2048 rows)
@@ -1322,9 +1013,11 @@ __device__ __forceinline__ bool dpw_wait(const unsigned long long *p, unsigned l
     return ok;
 }
 
-// orientation A: rows on the lanes of all waves, column by column.  Dp3A::step cut at its two exchange points.
+// ---- the cells of one line of the scan, cut at its two exchange points.  A wave on its own (W = 1) runs the three phases back to back and passes
+// the value from outside the band as the carry; the waves of a workgroup exchange their last cells after phase 1 and their aggregates after phase 2.
+// orientation A: rows on the lanes, column by column; X is the scanned state
 template <int R>
-struct DpwA {
+struct DpScanA {
     int32_t M[R], X[R], Y[R];
     int32_t s0[R], s1[R], s2[R], s3[R], gxo[R], gxe[R], E;
     int32_t Mn[R], Yn[R], Mu0, Yu0, pv; uint32_t tb;
@@ -1333,21 +1026,18 @@ struct DpwA {
         int32_t bsum = 0;
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            const uint32_t cn = i0 + r < m ? Pc[i0 + r] : 0u;
-            const int32_t c0 = cn & 255, c1 = (cn >> 8) & 255, c2 = (cn >> 16) & 255, c3 = cn >> 24;
-            const int32_t rr = c0 + c1 + c2 + c3;
-            s0[r] = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-            s1[r] = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-            s2[r] = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-            s3[r] = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-            gxo[r] = sc.go * rr; gxe[r] = sc.ge * rr; bsum += gxe[r];
+            dp_row_coef(i0 + r < m ? Pc[i0 + r] : 0u, sc, s0[r], s1[r], s2[r], s3[r], gxo[r], gxe[r]);
+            bsum += gxe[r];
             M[r] = X[r] = Y[r] = DP_NEG_INF;
         }
         return bsum;
     }
-    // M and Y of column j from column j - 1.  t?o: the row above the wave's first one at column j - 1
-    __device__ __forceinline__ void phase1(uint32_t b, bool j1, int32_t gyo, int32_t gye, int32_t tMo, int32_t tXo, int32_t tYo)
+    // M and Y of column j from column j - 1.  b: base of column j (wave-uniform); t?o: the row above the wave's first one at column j - 1
+    // (J1: j >= 1.  Column 0 has no M and no Y; it is peeled off the sweep's loop so that the other columns do not pay eight selects for it.)
+    template <bool J1>
+    __device__ __forceinline__ void phase1(uint32_t b, int32_t gyo, int32_t gye, int32_t tMo, int32_t tXo, int32_t tYo)
     {
+        constexpr bool j1 = J1;
         int32_t Md = lane0_set(wave_shr1z(M[R - 1]), tMo), Xd = lane0_set(wave_shr1z(X[R - 1]), tXo), Yd = lane0_set(wave_shr1z(Y[R - 1]), tYo);
         const bool lo = (b & 1u) != 0, hi = (b & 2u) != 0;
         tb = 0;
@@ -1365,7 +1055,7 @@ struct DpwA {
             Md = M[r]; Xd = X[r]; Yd = Y[r];
         }
     }
-    // the wave's own part of the scan.  tMn / tYn: the row above the wave's first one at column j
+    // the wave's own part of the scan: local chains, one prefix maximum over the lanes.  tMn / tYn: the row above the wave's first one at column j
     __device__ __forceinline__ void phase2(int32_t tMn, int32_t tYn)
     {
         Mu0 = lane0_set(wave_shr1z(Mn[R - 1]), tMn); Yu0 = lane0_set(wave_shr1z(Yn[R - 1]), tYn);
@@ -1378,7 +1068,8 @@ struct DpwA {
         }
         pv = wave_prefix_max(a - E);
     }
-    // X of column j.  carry: max(X of the row above the super-band, aggregates of the waves above); tXn: X of the row above the wave's first one
+    // X of column j: the cells with their real carry-in.  carry: max(X of the row above the (super-)band, aggregates of the waves above);
+    // tXn: X of the row above the wave's first one
     __device__ __forceinline__ uint32_t phase3(int32_t carry, int32_t tXn)
     {
         const int32_t xout = max(E + pv, carry + E);
@@ -1397,12 +1088,14 @@ struct DpwA {
     }
 };
 
-// orientation B: columns on the lanes of all waves, row by row (Dp3B::step cut the same way; Y is the scanned state)
+// orientation B: columns on the lanes, row by row; Y is the scanned state
 template <int R>
-struct DpwB {
+struct DpScanB {
     int32_t M[R], X[R], Y[R];
-    uint32_t bases; int32_t E;
+    uint32_t bases;                                        // 2 bits per column of the lane
+    int32_t E;
     int32_t Mn[R], Xn[R], Ml0, Xl0, pv; uint32_t tb;
+    // M and X of row i from row i - 1.  s0..s3, gxo, gxe: the profile row (wave-uniform); l?o: the column left of the wave's first one at row i - 1
     __device__ __forceinline__ void phase1(int32_t s0, int32_t s1, int32_t s2, int32_t s3, int32_t gxo, int32_t gxe, int32_t lMo, int32_t lXo, int32_t lYo)
     {
         int32_t Md = lane0_set(wave_shr1z(M[R - 1]), lMo), Xd = lane0_set(wave_shr1z(X[R - 1]), lXo), Yd = lane0_set(wave_shr1z(Y[R - 1]), lYo);
@@ -1422,6 +1115,7 @@ struct DpwB {
             Md = M[r]; Xd = X[r]; Yd = Y[r];
         }
     }
+    // lMn / lXn: the column left of the wave's first one at row i
     __device__ __forceinline__ void phase2(int32_t gyo, int32_t gye, int32_t lMn, int32_t lXn)
     {
         Ml0 = lane0_set(wave_shr1z(Mn[R - 1]), lMn); Xl0 = lane0_set(wave_shr1z(Xn[R - 1]), lXn);
@@ -1452,39 +1146,48 @@ struct DpwB {
     }
 };
 
-// orientation A over the whole workgroup.  Every wave of the workgroup calls it (uniform barriers); (m, n) is left in S.fin.
+// The sweeps.  W = 1: by ONE wave (wv = 0, no S, no cluster), the bands of 64 R rows / columns one after the other; (m, n) is left in fM / fX / fY on
+// every lane.  W > 1: every wave of the workgroup calls it (uniform barriers), the W waves hold a super-band side by side, wave wv its band q W + wv;
+// fM / fX / fY are written by the one lane that holds (m, n) (the caller passes S.fin).  One traceback layout for both: four bytes per lane at
+// (band * 64 + lane) * 4 of the line, of which the first R are used -- what Dp3Walk::P reads.
+
+// orientation A, all (super-)bands: rows on the lanes (R per lane), column by column
 template <int R, int W>
-__device__ __forceinline__ void dpw_sweep_a(DpwShared &S, int lane, int wv, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc,
-                                            int32_t krows, int32_t *rowbuf, uint8_t *tbp, int32_t mpad, const DpwCluster &CL)
+__device__ __forceinline__ void dp_sweep_a(DpwShared *S, int lane, int wv, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc,
+                                           int32_t krows, int32_t *rowbuf, uint8_t *tbp, int32_t mpad, const DpwCluster &CL,
+                                           int32_t &fM, int32_t &fX, int32_t &fY)
 {
-    constexpr int DPW_BAND = 64 * R, DPW_WAVES = W;
-    static_assert(DPW_BAND * DPW_WAVES == DPW_SB, "a super-band is 2048 rows");
-    const int32_t nsb = (m + DPW_SB - 1) / DPW_SB;
+    constexpr int BAND = 64 * R, SB = BAND * W;
+    static_assert(W == 1 || (R == 4 && SB == DPW_SB), "the wide sweep: a byte per row (the walk's R = 4 layout), a super-band is 2048 rows");
+    const bool cluster = W > 1 && CL.on();
+    const int32_t nsb = (m + SB - 1) / SB;
     const int32_t gyo = sc.go * krows, gye = sc.ge * krows;
     for (int32_t q = 0; q < nsb; q++) {
-        if (CL.on() && q % CL.K != CL.c) continue;               // a cluster: this workgroup's super-bands only
-        const int32_t sb0 = q * DPW_SB;
-        const int32_t nw = min(DPW_WAVES, (m - sb0 + DPW_BAND - 1) / DPW_BAND);        // waves that hold rows of the profile
-        const bool act = wv < nw;
-        DpwA<R> L;
-        const int32_t i0 = sb0 + wv * DPW_BAND + lane * R;
-        const int32_t bsum = L.constants(Pc, i0, m, sc);
-        const int32_t el = wave_prefix_sum(bsum);
-        if (lane == 63) S.esum[wv] = el;
-        __syncthreads();
+        if (cluster && q % CL.K != CL.c) continue;               // a cluster: this workgroup's super-bands only
+        const int32_t sb0 = q * SB, band = q * W + wv;
+        const bool act = W == 1 || wv < (m - sb0 + BAND - 1) / BAND;     // waves that hold rows of the profile
+        DpScanA<R> L;
+        const int32_t i0 = (band * 64 + lane) * R;                   // 0-based first row of the lane
+        const int32_t el = wave_prefix_sum(L.constants(Pc, i0, m, sc));
         int32_t eoff = 0;
-        for (int u = 0; u < wv; u++) eoff += S.esum[u];
+        if constexpr (W > 1) {
+            if (lane == 63) S->esum[wv] = el;
+            __syncthreads();
+            for (int u = 0; u < wv; u++) eoff += S->esum[u];
+        }
         L.E = el + eoff;                                         // prefix sums of gxe over the rows of the SUPER-band
         // parked rows: two buffers by parity for a workgroup on its own; a cluster has several super-bands in flight: one buffer per super-band
-        const int32_t *rin = rowbuf + (size_t)(CL.on() ? q - 1 : ((q & 1) ^ 1)) * 3 * (n + 1);
-        int32_t *rout = rowbuf + (size_t)(CL.on() ? q : (q & 1)) * 3 * (n + 1);
-        const bool park = q + 1 < nsb && wv == DPW_WAVES - 1;     // (a super-band that is followed by another one is full)
-        const bool writes = act && i0 < mpad;
-        const bool feed = CL.on() && q > 0;                       // the row above comes from another workgroup: wait for its progress before every fetch
+        const int32_t *rin = rowbuf + (size_t)(cluster ? q - 1 : ((q & 1) ^ 1)) * 3 * (n + 1);
+        int32_t *rout = rowbuf + (size_t)(cluster ? q : (q & 1)) * 3 * (n + 1);
+        const bool park = q + 1 < nsb && wv == W - 1;             // (a super-band that is followed by another one is full)
+        const bool writes = act && (band * 64 + lane) * 4 < mpad;
+        const bool feed = cluster && q > 0;                       // the row above comes from another workgroup: wait for its progress before every fetch
         const unsigned long long *ptok = CL.flags + (feed ? (q - 1) % CL.K : 0);
         bool good = true;
-        // per column from outside the super-band: the base, and the parked row of the super-band above (dp3_sweep_a's chunks; every wave
-        // keeps its own copy: the base and the X of that row are needed by all of them)
+        // What a column needs from outside the (super-)band -- its base, and (below the first) the parked row of the one above --
+        // is fetched by the whole wave 64 columns at a time, one chunk ahead, and handed out with v_readlane: a load per
+        // column would put a memory round trip into every step.  Chunk k: lane l holds column 64 k + l.  (Every wave keeps its
+        // own copy: the base and the X of that row are needed by all of them.)
         auto chunk = [&](int32_t k, uint32_t &sq, int32_t &cM, int32_t &cX, int32_t &cY) {
             const int32_t col = 64 * k + lane;
             sq = (uint32_t)seq[min(max(col - 1, 0), n - 1)];
@@ -1492,90 +1195,98 @@ __device__ __forceinline__ void dpw_sweep_a(DpwShared &S, int lane, int wv, int3
             else { const int32_t cc = min(col, n); cM = rin[cc]; cX = rin[(n + 1) + cc]; cY = rin[2 * (n + 1) + cc]; }
         };
         uint32_t sq_cur, sq_nxt; int32_t cM_cur, cX_cur, cY_cur, cM_nxt, cX_nxt, cY_nxt;
-        if (feed) good &= dpw_wait(ptok, CL.tok(q - 1, min(63, n) + 1), CL.failed());
+        if constexpr (W > 1) if (feed) good &= dpw_wait(ptok, CL.tok(q - 1, min(63, n) + 1), CL.failed());
         chunk(0, sq_nxt, cM_nxt, cX_nxt, cY_nxt);
         int32_t tMo = DP_NEG_INF, tXo = DP_NEG_INF, tYo = DP_NEG_INF;
-        uint8_t *tw = tbp + i0;                                   // one byte per row, R of them per lane: dp3's layout for R = 4 (P(x) = x)
+        uint8_t *tw = tbp + (size_t)(band * 64 + lane) * 4;
         for (int32_t k = 0; 64 * k <= n; k++) {
             sq_cur = sq_nxt; cM_cur = cM_nxt; cX_cur = cX_nxt; cY_cur = cY_nxt;
-            if (feed && 64 * (k + 1) <= n) good &= dpw_wait(ptok, CL.tok(q - 1, min(64 * k + 127, n) + 1), CL.failed());
+            if constexpr (W > 1) if (feed && 64 * (k + 1) <= n) good &= dpw_wait(ptok, CL.tok(q - 1, min(64 * k + 127, n) + 1), CL.failed());
             chunk(k + 1, sq_nxt, cM_nxt, cX_nxt, cY_nxt);
             const int32_t jend = min(64 * k + 63, n);
-            for (int32_t j = 64 * k; j <= jend; j++, tw += mpad) {
+            auto line = [&](int32_t j, auto first) {
                 const int sel = j & 63;
                 const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int32_t)sq_cur, sel);
                 const int32_t sM = __builtin_amdgcn_readlane(cM_cur, sel), sX = __builtin_amdgcn_readlane(cX_cur, sel), sY = __builtin_amdgcn_readlane(cY_cur, sel);
-                if (act) {
-                    L.phase1(b, j >= 1, gyo, gye, tMo, tXo, tYo);
-                    if (lane == 63) { S.botM[wv] = L.Mn[R - 1]; S.botE[wv] = L.Yn[R - 1]; }
-                }
-                __syncthreads();
+                if (act) L.template phase1<!decltype(first)::value>(b, gyo, gye, tMo, tXo, tYo);
                 int32_t tMn = sM, tYn = sY;
-                if (act) {
-                    if (wv > 0) { tMn = S.botM[wv - 1]; tYn = S.botE[wv - 1]; }
-                    L.phase2(tMn, tYn);
-                    if (lane == 63) S.agg[wv] = L.pv;
+                if constexpr (W > 1) {
+                    if (act && lane == 63) { S->botM[wv] = L.Mn[R - 1]; S->botE[wv] = L.Yn[R - 1]; }
+                    __syncthreads();
+                    if (act && wv > 0) { tMn = S->botM[wv - 1]; tYn = S->botE[wv - 1]; }
                 }
-                __syncthreads();
+                if (act) L.phase2(tMn, tYn);
+                int32_t carry = sX, tXn = sX;
+                if constexpr (W > 1) {
+                    if (act && lane == 63) S->agg[wv] = L.pv;
+                    __syncthreads();
+                    if (act) {
+                        carry = max(sX, dpw_carry(S->agg, wv, lane));
+                        if (wv > 0) tXn = carry + eoff;          // = what the last row of the wave above holds: E_last + max(its aggregate, its carry)
+                    }
+                }
                 if (act) {
-                    const int32_t carry = max(sX, dpw_carry(S.agg, wv, lane));
-                    const int32_t tXn = wv > 0 ? carry + eoff : sX;      // = what the last row of the wave above holds: E_last + max(its aggregate, its carry)
                     const uint32_t tbw = L.phase3(carry, tXn);
-                    if (writes) { if (R == 4) *reinterpret_cast<uint32_t *>(tw) = tbw; else *reinterpret_cast<uint16_t *>(tw) = (uint16_t)tbw; }
+                    if (writes) *reinterpret_cast<uint32_t *>(tw) = tbw;
                     if (park && lane == 63) { rout[j] = L.M[R - 1]; rout[(n + 1) + j] = L.X[R - 1]; rout[2 * (n + 1) + j] = L.Y[R - 1]; }
                     tMo = tMn; tXo = tXn; tYo = tYn;
                 }
-            }
-            if (CL.on() && park) dpw_publish(CL.flags + CL.c, CL.tok(q, jend + 1));       // (wave-uniform: the parking wave) columns 0 .. jend are out
+            };
+            int32_t j = 64 * k;
+            if (k == 0) { line(0, std::true_type()); j = 1; tw += mpad; }           // column 0, peeled
+            for (; j <= jend; j++, tw += mpad) line(j, std::false_type());
+            if constexpr (W > 1) if (cluster && park) dpw_publish(CL.flags + CL.c, CL.tok(q, jend + 1));       // (wave-uniform: the parking wave) columns 0 .. jend are out
         }
-        if (!good && lane == 0) __hip_atomic_store(CL.failed(), 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (W > 1) if (!good && lane == 0) __hip_atomic_store(CL.failed(), 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (q == nsb - 1) {
             const int32_t rel = m - 1 - sb0;                        // the row of (m, .) inside the super-band
-            if (wv == rel / DPW_BAND && lane == (rel % DPW_BAND) / R) {
-                const int ro = rel % R;
-                int32_t a = L.M[0], b2 = L.X[0], c2 = L.Y[0];
-#pragma unroll
-                for (int r = 1; r < R; r++) if (ro == r) { a = L.M[r]; b2 = L.X[r]; c2 = L.Y[r]; }
-                S.fin[0] = a; S.fin[1] = b2; S.fin[2] = c2;
-            }
+            const int owner = (rel % BAND) / R;
+            int32_t a, b2, c2;
+            dp_row_pick(L, rel % R, a, b2, c2);
+            if constexpr (W == 1) { fM = __shfl(a, owner); fX = __shfl(b2, owner); fY = __shfl(c2, owner); }
+            else if (wv == rel / BAND && lane == owner) { fM = a; fX = b2; fY = c2; }
         }
         __threadfence_block();
-        __syncthreads();                                          // parked row, esum and fin before anybody goes on
+        if constexpr (W > 1) __syncthreads();                     // parked row, esum and fin before anybody goes on
     }
 }
 
-// orientation B over the whole workgroup
+// orientation B, all (super-)bands: columns on the lanes, row by row
 template <int R, int W>
-__device__ __forceinline__ void dpw_sweep_b(DpwShared &S, int lane, int wv, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc,
-                                            int32_t krows, int32_t *rowbuf, uint8_t *tbp, int32_t npad, const DpwCluster &CL)
+__device__ __forceinline__ void dp_sweep_b(DpwShared *S, int lane, int wv, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc,
+                                           int32_t krows, int32_t *rowbuf, uint8_t *tbp, int32_t npad, const DpwCluster &CL,
+                                           int32_t &fM, int32_t &fX, int32_t &fY)
 {
-    constexpr int DPW_BAND = 64 * R, DPW_WAVES = W;
-    static_assert(DPW_BAND * DPW_WAVES == DPW_SB, "a super-band is 2048 rows");
-    const int32_t nsb = (n + DPW_SB - 1) / DPW_SB;
+    constexpr int BAND = 64 * R, SB = BAND * W;
+    static_assert(W == 1 || (R == 4 && SB == DPW_SB), "the wide sweep: a byte per column (the walk's R = 4 layout), a super-band is 2048 columns");
+    const bool cluster = W > 1 && CL.on();
+    const int32_t nsb = (n + SB - 1) / SB;
     const int32_t gyo = sc.go * krows, gye = sc.ge * krows;
     for (int32_t q = 0; q < nsb; q++) {
-        if (CL.on() && q % CL.K != CL.c) continue;
-        const int32_t sb0 = q * DPW_SB;
-        const int32_t nw = min(DPW_WAVES, (n - sb0 + DPW_BAND - 1) / DPW_BAND);
-        const bool act = wv < nw;
-        DpwB<R> L;
-        const int32_t j0 = sb0 + wv * DPW_BAND + lane * R;          // 0-based first column index (j - 1) of the lane
+        if (cluster && q % CL.K != CL.c) continue;
+        const int32_t sb0 = q * SB, band = q * W + wv;
+        const bool act = W == 1 || wv < (n - sb0 + BAND - 1) / BAND;
+        DpScanB<R> L;
+        const int32_t j0 = (band * 64 + lane) * R;                   // 0-based first column index (j - 1) of the lane
         L.bases = 0;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             L.bases |= (uint32_t)(j0 + r < n ? seq[j0 + r] : 0) << (2 * r);
-            L.M[r] = DP_NEG_INF; L.X[r] = DP_NEG_INF; L.Y[r] = gyo + (j0 + r) * gye;     // row 0: only Y exists (analytic, not clamped)
+            // row 0: only Y exists (analytic, not clamped: the anti-diagonal sweeps' boundary row)
+            L.M[r] = DP_NEG_INF; L.X[r] = DP_NEG_INF; L.Y[r] = gyo + (j0 + r) * gye;
         }
-        const int32_t eoff = wv * DPW_BAND * gye;
+        const int32_t eoff = wv * BAND * gye;
         L.E = (lane + 1) * R * gye + eoff;                          // prefix sums of gye over the columns of the SUPER-band
-        const int32_t *cin = rowbuf + (size_t)(CL.on() ? q - 1 : ((q & 1) ^ 1)) * 3 * (m + 1);
-        int32_t *cout = rowbuf + (size_t)(CL.on() ? q : (q & 1)) * 3 * (m + 1);
-        const bool park = q + 1 < nsb && wv == DPW_WAVES - 1;
-        const bool writes = act && j0 < npad;
-        const bool feed = CL.on() && q > 0;                       // (lines of the parked column: row i is line i, row 0 included: i + 1 of them after row i)
+        const int32_t *cin = rowbuf + (size_t)(cluster ? q - 1 : ((q & 1) ^ 1)) * 3 * (m + 1);
+        int32_t *cout = rowbuf + (size_t)(cluster ? q : (q & 1)) * 3 * (m + 1);
+        const bool park = q + 1 < nsb && wv == W - 1;
+        const bool writes = act && (band * 64 + lane) * 4 < npad;
+        const bool feed = cluster && q > 0;                       // (lines of the parked column: row i is line i, row 0 included: i + 1 of them after row i)
         const unsigned long long *ptok = CL.flags + (feed ? (q - 1) % CL.K : 0);
         bool good = true;
-        if (feed) good &= dpw_wait(ptok, CL.tok(q - 1, min(64, m) + 1), CL.failed());
+        if constexpr (W > 1) if (feed) good &= dpw_wait(ptok, CL.tok(q - 1, min(64, m) + 1), CL.failed());
+        // per row from outside the (super-)band: the profile column's counts and (right of the first) the parked column of the
+        // one to the left -- fetched 64 rows at a time, one chunk ahead (see orientation A).  Chunk k: lane l holds row 64 k + l + 1.
         auto chunk = [&](int32_t k, uint32_t &pc, int32_t &cM, int32_t &cX, int32_t &cY) {
             const int32_t row = min(64 * k + lane + 1, m);
             pc = Pc[row - 1];
@@ -1587,72 +1298,130 @@ __device__ __forceinline__ void dpw_sweep_b(DpwShared &S, int lane, int wv, int3
         int32_t lMo, lXo, lYo;
         if (wv == 0 && q == 0) { lMo = 0; lXo = DP_NEG_INF; lYo = DP_NEG_INF; }
         else if (wv == 0) { lMo = __builtin_amdgcn_readfirstlane(cin[0]); lXo = __builtin_amdgcn_readfirstlane(cin[(m + 1)]); lYo = __builtin_amdgcn_readfirstlane(cin[2 * (m + 1)]); }
-        else { lMo = DP_NEG_INF; lXo = DP_NEG_INF; lYo = gyo + (sb0 + wv * DPW_BAND - 1) * gye; }
-        // (the super-band's own left column at row i - 1, for the chain down column 0 of the first super-band)
+        else { lMo = DP_NEG_INF; lXo = DP_NEG_INF; lYo = gyo + (sb0 + wv * BAND - 1) * gye; }
+        // (the super-band's own left column at row i - 1, for the chain down column 0 of the first super-band: M and Y do not exist there,
+        // X is the chain down from (0, 0))
         int32_t sMo = lMo, sXo = lXo, sYo = lYo;
         if (wv != 0) { if (q == 0) { sMo = 0; sXo = DP_NEG_INF; sYo = DP_NEG_INF; } }
-        if (park && lane == 63) { cout[0] = L.M[R - 1]; cout[(m + 1)] = L.X[R - 1]; cout[2 * (m + 1)] = L.Y[R - 1]; }
+        if (park && lane == 63) { cout[0] = L.M[R - 1]; cout[(m + 1)] = L.X[R - 1]; cout[2 * (m + 1)] = L.Y[R - 1]; }    // row 0 of the band's last column
         uint32_t pc_cur, pc_nxt; int32_t cM_cur, cX_cur, cY_cur, cM_nxt, cX_nxt, cY_nxt;
         chunk(0, pc_nxt, cM_nxt, cX_nxt, cY_nxt);
-        uint8_t *tw = tbp + j0;
+        uint8_t *tw = tbp + (size_t)(band * 64 + lane) * 4;
         for (int32_t k = 0; 64 * k < m; k++) {
             pc_cur = pc_nxt; cM_cur = cM_nxt; cX_cur = cX_nxt; cY_cur = cY_nxt;
-            if (feed && 64 * (k + 1) < m) good &= dpw_wait(ptok, CL.tok(q - 1, min(64 * k + 128, m) + 1), CL.failed());
+            if constexpr (W > 1) if (feed && 64 * (k + 1) < m) good &= dpw_wait(ptok, CL.tok(q - 1, min(64 * k + 128, m) + 1), CL.failed());
             chunk(k + 1, pc_nxt, cM_nxt, cX_nxt, cY_nxt);
             const int32_t iend = min(64 * k + 64, m);
             for (int32_t i = 64 * k + 1; i <= iend; i++, tw += npad) {
                 const int sel = (i - 1) & 63;
-                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int32_t)pc_cur, sel);
-                const int32_t c0 = c & 255, c1 = (c >> 8) & 255, c2 = (c >> 16) & 255, c3 = c >> 24, rr = c0 + c1 + c2 + c3;
-                const int32_t s0 = c0 * sc.s[0][0] + c1 * sc.s[1][0] + c2 * sc.s[2][0] + c3 * sc.s[3][0];
-                const int32_t s1 = c0 * sc.s[0][1] + c1 * sc.s[1][1] + c2 * sc.s[2][1] + c3 * sc.s[3][1];
-                const int32_t s2 = c0 * sc.s[0][2] + c1 * sc.s[1][2] + c2 * sc.s[2][2] + c3 * sc.s[3][2];
-                const int32_t s3 = c0 * sc.s[0][3] + c1 * sc.s[1][3] + c2 * sc.s[2][3] + c3 * sc.s[3][3];
-                const int32_t gxo = sc.go * rr, gxe = sc.ge * rr;
+                int32_t s0, s1, s2, s3, gxo, gxe;
+                dp_row_coef((uint32_t)__builtin_amdgcn_readlane((int32_t)pc_cur, sel), sc, s0, s1, s2, s3, gxo, gxe);
                 // the column left of the SUPER-band at row i (wave-uniform, every wave computes it: its Y is the carry's floor)
                 int32_t sMn, sXn, sYn;
                 if (q == 0) {
                     const int32_t xa = sMo + gxo, xb = sXo + gxe, xc = sYo + gxo, bx = max(max(xa, xb), xc);
                     sMn = DP_NEG_INF; sYn = DP_NEG_INF; sXn = max(bx, DP_NEG_INF);
                 } else { sMn = __builtin_amdgcn_readlane(cM_cur, sel); sXn = __builtin_amdgcn_readlane(cX_cur, sel); sYn = __builtin_amdgcn_readlane(cY_cur, sel); }
-                if (act) {
-                    L.phase1(s0, s1, s2, s3, gxo, gxe, lMo, lXo, lYo);
-                    if (lane == 63) { S.botM[wv] = L.Mn[R - 1]; S.botE[wv] = L.Xn[R - 1]; }
-                }
-                __syncthreads();
+                if (act) L.phase1(s0, s1, s2, s3, gxo, gxe, lMo, lXo, lYo);
                 int32_t lMn = sMn, lXn = sXn;
-                if (act) {
-                    if (wv > 0) { lMn = S.botM[wv - 1]; lXn = S.botE[wv - 1]; }
-                    L.phase2(gyo, gye, lMn, lXn);
-                    if (lane == 63) S.agg[wv] = L.pv;
+                if constexpr (W > 1) {
+                    if (act && lane == 63) { S->botM[wv] = L.Mn[R - 1]; S->botE[wv] = L.Xn[R - 1]; }
+                    __syncthreads();
+                    if (act && wv > 0) { lMn = S->botM[wv - 1]; lXn = S->botE[wv - 1]; }
                 }
-                __syncthreads();
+                if (act) L.phase2(gyo, gye, lMn, lXn);
+                int32_t carry = sYn, lYn = sYn;
+                if constexpr (W > 1) {
+                    if (act && lane == 63) S->agg[wv] = L.pv;
+                    __syncthreads();
+                    if (act) {
+                        carry = max(sYn, dpw_carry(S->agg, wv, lane));
+                        if (wv > 0) lYn = carry + eoff;
+                    }
+                }
                 if (act) {
-                    const int32_t carry = max(sYn, dpw_carry(S.agg, wv, lane));
-                    const int32_t lYn = wv > 0 ? carry + eoff : sYn;
                     const uint32_t tbw = L.phase3(gyo, gye, carry, lYn);
-                    if (writes) { if (R == 4) *reinterpret_cast<uint32_t *>(tw) = tbw; else *reinterpret_cast<uint16_t *>(tw) = (uint16_t)tbw; }
+                    if (writes) *reinterpret_cast<uint32_t *>(tw) = tbw;
                     if (park && lane == 63) { cout[i] = L.M[R - 1]; cout[(m + 1) + i] = L.X[R - 1]; cout[2 * (m + 1) + i] = L.Y[R - 1]; }
                     lMo = lMn; lXo = lXn; lYo = lYn;
                 }
                 sMo = sMn; sXo = sXn; sYo = sYn;
             }
-            if (CL.on() && park) dpw_publish(CL.flags + CL.c, CL.tok(q, iend + 1));       // rows 0 .. iend of the parked column are out
+            if constexpr (W > 1) if (cluster && park) dpw_publish(CL.flags + CL.c, CL.tok(q, iend + 1));       // rows 0 .. iend of the parked column are out
         }
-        if (!good && lane == 0) __hip_atomic_store(CL.failed(), 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (W > 1) if (!good && lane == 0) __hip_atomic_store(CL.failed(), 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (q == nsb - 1) {
-            const int32_t rel = n - 1 - sb0;
-            if (wv == rel / DPW_BAND && lane == (rel % DPW_BAND) / R) {
-                const int ro = rel % R;
-                int32_t a = L.M[0], b2 = L.X[0], c2 = L.Y[0];
-#pragma unroll
-                for (int r = 1; r < R; r++) if (ro == r) { a = L.M[r]; b2 = L.X[r]; c2 = L.Y[r]; }
-                S.fin[0] = a; S.fin[1] = b2; S.fin[2] = c2;
-            }
+            const int32_t rel = n - 1 - sb0;                        // the column of (., n) inside the super-band
+            const int owner = (rel % BAND) / R;
+            int32_t a, b2, c2;
+            dp_row_pick(L, rel % R, a, b2, c2);
+            if constexpr (W == 1) { fM = __shfl(a, owner); fX = __shfl(b2, owner); fY = __shfl(c2, owner); }
+            else if (wv == rel / BAND && lane == owner) { fM = a; fX = b2; fY = c2; }
         }
         __threadfence_block();
-        __syncthreads();
+        if constexpr (W > 1) __syncthreads();
     }
+}
+
+// The layout of one step on one wave: the orientation by cost, as few rows (A) / columns (B) per lane as cover the dimension with the 64 lanes, at most 4
+// (then bands).  A: line j at tbp + j * stride; B: line i - 1 at tbp + (i - 1) * stride.
+__device__ __forceinline__ void dp3_layout(Dp3Walk &W, const uint8_t *tbp, int32_t m, int32_t n)
+{
+    W.tb = tbp; W.orient_b = dp3_orient_b(m, n);
+    const int32_t ldim = W.orient_b ? n : m;
+    W.R = dp3_rows_per_lane(ldim); W.stride = dp3_pad(ldim);
+}
+// ... and the sweep in that layout, by one wave.  Leaves (m, n) in fM / fX / fY.
+__device__ __forceinline__ void dp3_sweep(const Dp3Walk &W, int lane, int32_t m, int32_t n, const uint32_t *Pc, const uint8_t *seq, const DpScoring &sc, int32_t krows,
+                                          int32_t *rowbuf, uint8_t *tbp, int32_t &fM, int32_t &fX, int32_t &fY)
+{
+    const int32_t pad = (int32_t)W.stride;
+    const DpwCluster alone = { 1, 0, nullptr, 0 };
+    if (!W.orient_b) {
+        if (W.R == 1) dp_sweep_a<1, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+        else if (W.R == 2) dp_sweep_a<2, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+        else dp_sweep_a<4, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+    } else {
+        if (W.R == 1) dp_sweep_b<1, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+        else if (W.R == 2) dp_sweep_b<2, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+        else dp_sweep_b<4, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+    }
+}
+
+__device__ void dp3_interval(int nseq, int64_t iv, const DpBufs &B, uint8_t *win)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t *seq_off = B.seq_off;
+    DpMeta mt = dp_meta_zero();
+    const int64_t base = seq_off[iv * nseq];
+    for (int g = 0; g < nseq; g++) {
+        const int64_t so = seq_off[iv * nseq + g];
+        const int32_t n = (int32_t)(seq_off[iv * nseq + g + 1] - so);
+        if (n == 0) continue;
+        const uint8_t *seq = B.codes + so;
+        const DpStep P = dp_step_ptrs(B, mt, base);
+        if (mt.krows == 0) {
+            dp_first_profile<64>(P, seq, n, g, lane);
+            mt.m = n; mt.krows = 1;
+            __threadfence_block();
+            continue;
+        }
+        const int32_t m = mt.m;
+        int32_t fM = DP_NEG_INF, fX = DP_NEG_INF, fY = DP_NEG_INF;   // values at (m, n)
+        uint8_t *tbp = B.tb + B.tb_off[iv];
+        Dp3Walk W; W.win = win; W.cap = DP2_TB_DW * 4;
+        dp3_layout(W, tbp, m, n);
+        dp3_sweep(W, lane, m, n, P.Pc, seq, B.sc, mt.krows, B.rows + B.rows_off[iv], tbp, fM, fX, fY);
+        int state;
+        const int32_t best = dp_pick_state(fM, fX, fY, state);
+        uint8_t *opr = B.ops + base;                       // reversed ops, capacity m + n
+        const int32_t len = dp3_walk(W, m, n, state, opr, lane);
+        __threadfence_block();
+        dp_rebuild<1>(P, opr, len, seq, g, lane, 0);
+        dp_step_done(mt, (int64_t)m * n, best, len);
+        __threadfence_block();
+    }
+    if (lane == 0) B.meta[iv] = mt;
 }
 
 // one interval, all its progressive steps, by the whole workgroup (dp3_interval's structure; the walk is wave 0's, the rebuild everybody's) -- or by a
@@ -1714,8 +1483,8 @@ __device__ void dp_interval_wide(int nseq, int64_t iv, const DpBufs &B, DpwClust
             Wk.orient_b = wide_b; Wk.R = 4; Wk.stride = pad;              // (a byte per row / column: the walk's R = 4 layout whatever R the sweep ran with)
             DpwCluster C1 = CL; if (nsb < 2) C1.K = 1;                    // one super-band: nothing to share (the lead runs it as if alone)
             if (C1.on() || lead) {
-                if (!wide_b) dpw_sweep_a<R, W>(S, lane, wv, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1);
-                else dpw_sweep_b<R, W>(S, lane, wv, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1);
+                if (!wide_b) dp_sweep_a<R, W>(&S, lane, wv, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1, S.fin[0], S.fin[1], S.fin[2]);
+                else dp_sweep_b<R, W>(&S, lane, wv, m, n, P.Pc, seq, sc, mt.krows, rowbuf, tbp, pad, C1, S.fin[0], S.fin[1], S.fin[2]);
             }
             if (C1.on()) {
                 // the traceback bytes (and, from whoever ran the last super-band, the final cell) to the lead
