@@ -14,18 +14,18 @@
 
 namespace mems {
 
-class HipCoordinateIndex {
-public:
-    // the index of a caller's alignment: every base of a sequence may lie in at most one interval of the list (else gnException)
-    explicit HipCoordinateIndex(const IntervalList &il, HipContext &hc = HipContext::global()) : hc_(&hc)
+// an IntervalList in the arrays of mauve_align_fetch, as the entry points that take a caller's alignment want it (cols is never empty)
+struct HipIntervalArrays {
+    size_t K;
+    uint N;
+    std::vector<int64_t> left, right, col_off;
+    std::vector<int8_t> rev;
+    std::vector<uint32_t> cols;
+    HipIntervalArrays(const IntervalList &il, const char *who) : K(il.size()), N((uint)il.seq_table.size())
     {
-        const size_t K = il.size();
-        uint N = (uint)il.seq_table.size();
         for (const Interval &iv : il) N = std::max(N, iv.SeqCount());
-        if (N == 0) throw genome::gnException("HipCoordinateIndex: the interval list names no sequence");
-        std::vector<int64_t> left(K * N, 0), right(K * N, 0), col_off(K + 1, 0);
-        std::vector<int8_t> rev(K * N, 0);
-        std::vector<uint32_t> cols;
+        if (N == 0) throw genome::gnException(std::string(who) + ": the interval list names no sequence");
+        left.assign(K * N, 0); right.assign(K * N, 0); col_off.assign(K + 1, 0); rev.assign(K * N, 0);
         for (size_t i = 0; i < K; i++) {
             const Interval &iv = il[i];
             for (uint g = 0; g < iv.SeqCount(); g++) {
@@ -36,8 +36,17 @@ public:
             col_off[i + 1] = (int64_t)cols.size();
         }
         if (cols.empty()) cols.push_back(0);
-        hc.check(mauve_coord_index_alignment(hc.get(), (int)N, (int64_t)K, left.data(), right.data(), rev.data(), col_off.data(), cols.data()), "mauve_coord_index_alignment");
-        n_ = N;
+    }
+};
+
+class HipCoordinateIndex {
+public:
+    // the index of a caller's alignment: every base of a sequence may lie in at most one interval of the list (else gnException)
+    explicit HipCoordinateIndex(const IntervalList &il, HipContext &hc = HipContext::global()) : hc_(&hc)
+    {
+        const HipIntervalArrays a(il, "HipCoordinateIndex");
+        hc.check(mauve_coord_index_alignment(hc.get(), (int)a.N, (int64_t)a.K, a.left.data(), a.right.data(), a.rev.data(), a.col_off.data(), a.cols.data()), "mauve_coord_index_alignment");
+        n_ = a.N;
     }
     // the index of the alignment the context holds (after Aligner::align / ProgressiveAligner::align); the sequence count is the alignment's
     explicit HipCoordinateIndex(HipContext &hc) : hc_(&hc), n_(0)

@@ -28,4 +28,5 @@
 #include "ProgressiveAligner.h"
 #include "Backbone.h"
 #include "Islands.h"
+#include "AlignmentScore.h"
 #endif

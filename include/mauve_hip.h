@@ -485,6 +485,37 @@ int mauve_pair_stats(mauve_ctx *ctx, int64_t n_pair, const int32_t *pair_a, cons
                      int per_range, int64_t *stats);
 void mauve_pair_stats_identity(const int64_t *stats, int64_t n_rec, double *identity);
 void mauve_pair_stats_sp_score(const int64_t *stats, int64_t n_rec, const mauve_scoring *sc, int64_t *score);
+/* ---- an alignment scored against a correct one: scoreAlignment <correct alignment> <calculated alignment> (scoreAlignment.cpp:99-457),
+        counted on two coordinate indices.  Frozen form DESIGN.md S17.  T is the correct alignment, loaded by the first call below; C, the
+        calculated one, is the coordinate index in force (S14); both are over the same nseq genomes and follow S14's position rule.  No
+        genome data is read: neither call needs resident genomes.
+        For an ordered pair (i, j), i != j, and a base p of genome i that is a residue in some column of T: T_ij(p) is the position of j's
+        residue in that column (none: j gapped there or absent from the interval); P_ij(p) is the position of j's residue in the column of
+        C that holds base p of i (none: no interval of C covers p, j is absent from it, or j is gapped there); inside_ij(p): p lies in an
+        interval of C in which j is present.  A record is MAUVE_SCORE_WORDS int64_t per ordered pair, every such base in exactly one slot:
+          [0] tp            T_ij a base, P_ij the same base      [1] fp_base   T_ij a base, P_ij another base
+          [2] fp_gap        T_ij a base, P_ij none, inside_ij    [3] fn_unaligned  T_ij a base, P_ij none, not inside_ij
+          [4] fn_base       T_ij none, P_ij a base               [5] tn        both none            [6], [7] 0
+        Slots 0..5 of record (i, j) sum to the residues genome i has in T; the diagonal records are zero.  Only positions are compared
+        (the tool's test is cor_baseJ == +-calc_baseJ, :424-427).  A base whose intervals in C all lack j counts as fn_unaligned (the
+        tool's "bad context" branch, :345-350, would call it FP).
+        The first call takes the correct alignment in the arrays of the fetch, with the argument and consistency checks of the index of a
+        caller's alignment (MAUVE_ERR_ARG, the text names the interval / the two overlapping intervals); positions of 2^31 or more:
+        MAUVE_ERR_LIMIT.  It is a snapshot with device buffers of its own: index calls, alignments and genome uploads leave it as it is
+        (one truth scores many calculated alignments), the next such call replaces it, the context's end frees it; it touches neither
+        the index in force nor an extract selection.
+        The second writes records[nseq * nseq][8], row-major (i, j); page-locked records are copied directly.  MAUVE_ERR_STATE: no
+        truth, no index in force, or the two differ in nseq.  A truth without intervals or columns gives zeros.  All counts are integers
+        and independent of any tiling: two calls return identical bytes.
+        The third, on the host and without a context, gives the tool's totals: TP = the sum over i < j of [0], FP = over i < j of
+        [1] + [2], FN = over i < j of [3] plus over all i != j of [4], TN = over all i != j of [5], unaligned_fn = over i < j of [3],
+        total = the four. ---- */
+#define MAUVE_SCORE_WORDS 8
+typedef struct { int64_t tp, tn, fp, fn, total, unaligned_fn; } mauve_score_totals;
+int mauve_score_truth(mauve_ctx *ctx, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse,
+                      const int64_t *col_off, const uint32_t *cols);
+int mauve_score_alignment(mauve_ctx *ctx, int64_t *records /* nseq*nseq*8 */);
+void mauve_score_totals_from(const int64_t *records, int nseq, mauve_score_totals *out);
 /* IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760; format mfa2xmfa.cpp:64-115).
    Two-phase: buf == NULL returns the needed size (including NUL) in *len. */
 int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_t *len);

@@ -35,6 +35,7 @@ EXPORTS = [
     "mauve_coord_index", "mauve_coord_index_alignment", "mauve_coord_index_size", "mauve_column_positions", "mauve_seqpos_to_column", "mauve_translate_positions",
     "mauve_default_extract_params", "mauve_extract_select", "mauve_extract_fetch",
     "mauve_pair_stats", "mauve_pair_stats_identity", "mauve_pair_stats_sp_score",
+    "mauve_score_truth", "mauve_score_alignment", "mauve_score_totals_from",
 ]
 
 
@@ -240,6 +241,29 @@ def pair_stats_sp_score(stats, scoring=None):
     L.mauve_pair_stats_sp_score.restype = None
     if out.size:
         L.mauve_pair_stats_sp_score(_p(st, C.c_int64), C.c_int64(out.size), C.byref(sc), _p(out, C.c_int64))
+    return out
+
+
+SCORE_WORDS = 8                       # MAUVE_SCORE_WORDS: int64 per ordered genome pair
+
+
+class ScoreTotals(C.Structure):
+    _fields_ = [("tp", C.c_int64), ("tn", C.c_int64), ("fp", C.c_int64), ("fn", C.c_int64), ("total", C.c_int64), ("unaligned_fn", C.c_int64)]
+
+
+def score_totals(records):
+    """mauve_score_totals_from (host entry, no context): records [N, N, 8] of Context.score_alignment -> the totals of scoreAlignment.cpp under
+    the keys of accuracy.score_alignment_reference (tp, tn, fp, fn, total, sensitivity, specificity), and unaligned_fn"""
+    rec = np.ascontiguousarray(records, np.int64)
+    if rec.ndim != 3 or rec.shape[0] != rec.shape[1] or rec.shape[2] != SCORE_WORDS:
+        raise ValueError("score_totals: records [N, N, %d] expected" % SCORE_WORDS)
+    t = ScoreTotals()
+    L = load()
+    L.mauve_score_totals_from.restype = None
+    L.mauve_score_totals_from(_p(rec if rec.size else np.zeros(1, np.int64), C.c_int64), C.c_int(rec.shape[0]), C.byref(t))
+    out = {k: int(getattr(t, k)) for k, _ in ScoreTotals._fields_}
+    out["sensitivity"] = out["tp"] / max(out["tp"] + out["fn"], 1)
+    out["specificity"] = out["tn"] / max(out["tn"] + out["fp"], 1)
     return out
 
 
@@ -942,6 +966,33 @@ class Context:
         st = self._co_out((out,), 0, shape, np.int64) if out is not None else np.zeros(shape, np.int64)
         self._chk(self.L.mauve_pair_stats(self.h, *args_p, *args_r, C.c_int(int(bool(per_range))), _p(st if st.size else z8, C.c_int64)), "mauve_pair_stats")
         return st
+
+    # ---- an alignment scored against a correct one ----
+    def score_truth(self, aln):
+        """mauve_score_truth: the correct alignment (dict with left, right, reverse, col_off, cols, e.g. accuracy.truth_alignment or a fetched
+        result) into the context's second index slot; it stays through index calls, alignments and genome uploads"""
+        left = np.ascontiguousarray(aln["left"], np.int64)
+        right = np.ascontiguousarray(aln["right"], np.int64)
+        reverse = np.ascontiguousarray(aln["reverse"], np.int8)
+        col_off = np.ascontiguousarray(aln["col_off"], np.int64)
+        cols = np.ascontiguousarray(aln["cols"], np.uint32)
+        if left.ndim != 2 or right.shape != left.shape or reverse.shape != left.shape:
+            raise ValueError("score_truth: left, right and reverse must be [n_iv, nseq]")
+        n_iv, N = left.shape
+        self._chk(self.L.mauve_score_truth(self.h, N, C.c_int64(n_iv), _p(left, C.c_int64), _p(right, C.c_int64), _p(reverse, C.c_int8),
+                                           _p(col_off, C.c_int64), _p(cols if len(cols) else np.zeros(1, np.uint32), C.c_uint32)), "mauve_score_truth")
+        self._score_n = N
+
+    def score_alignment(self, out=None):
+        """mauve_score_alignment: the index in force against the correct alignment -> int64 records [N, N, 8] (tp, fp_base, fp_gap,
+        fn_unaligned, fn_base, tn, 0, 0 per ordered pair); out = the result array (e.g. from pinned_empty: copied without staging)"""
+        N = getattr(self, "_score_n", 0)
+        if N == 0:                                               # no truth: the library says so (nothing is written)
+            self._chk(self.L.mauve_score_alignment(self.h, _p(np.zeros(SCORE_WORDS, np.int64), C.c_int64)), "mauve_score_alignment")
+            raise RuntimeError("mauve_score_alignment ran without a correct alignment")
+        rec = self._co_out((out,), 0, (N, N, SCORE_WORDS), np.int64) if out is not None else np.zeros((N, N, SCORE_WORDS), np.int64)
+        self._chk(self.L.mauve_score_alignment(self.h, _p(rec, C.c_int64)), "mauve_score_alignment")
+        return rec
 
     def stage_times(self):
         t = StageTimes()

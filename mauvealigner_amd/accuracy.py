@@ -104,13 +104,13 @@ def score_alignment_reference(aln, origins):
     return {"tp": tp, "tn": tn, "fp": fp, "fn": fn, "total": total, "sensitivity": tp / max(tp + fn, 1), "specificity": tn / max(tn + fp, 1)}
 
 
-def truth_xmfa(genomes, origins, names):
-    """The generator's truth as the XMFA file scoreAlignment takes as its <correct alignment>: one block, every sequence
-    forward from base 1 -- so only for genome sets without rearrangements.  Bases that share an ancestor coordinate
-    share a column; bases inserted after the split get columns of their own behind the ancestor column they follow."""
-    N = len(genomes)
+def _truth_columns(origins, who):
+    """the one-block truth's columns: -> (allk, col, ncol); row r of allk is one base, allk[r, 3] its genome, allk[r, 4] its 0-based
+    position, col[r] its column.  Bases that share an ancestor coordinate share a column; bases inserted after the split get columns of
+    their own behind the ancestor column they follow."""
+    N = len(origins)
     if any((np.asarray(o) < 0).any() for o in origins):
-        raise ValueError("truth_xmfa: the genomes carry inversions; one forward block cannot hold them")
+        raise ValueError("%s: the genomes carry inversions; one forward block cannot hold them" % who)
     keys = []
     for g in range(N):
         o = np.asarray(origins[g], np.int64)
@@ -127,7 +127,15 @@ def truth_xmfa(genomes, origins, names):
     newcol = np.ones(len(allk), bool)
     newcol[1:] = np.any(allk[1:, :3] != allk[:-1, :3], axis=1)
     col = np.cumsum(newcol) - 1
-    ncol = int(col[-1]) + 1
+    return allk, col, int(col[-1]) + 1
+
+
+def truth_xmfa(genomes, origins, names):
+    """The generator's truth as the XMFA file scoreAlignment takes as its <correct alignment>: one block, every sequence
+    forward from base 1 -- so only for genome sets without rearrangements.  Bases that share an ancestor coordinate
+    share a column; bases inserted after the split get columns of their own behind the ancestor column they follow."""
+    N = len(genomes)
+    allk, col, ncol = _truth_columns(origins, "truth_xmfa")
     out = ["#FormatVersion Mauve1\n"]
     for g in range(N):
         row = np.full(ncol, ord("-"), np.uint8)
@@ -138,3 +146,15 @@ def truth_xmfa(genomes, origins, names):
         out.extend(text[p:p + 80] + "\n" for p in range(0, ncol, 80))
     out.append("=\n")
     return "".join(out)
+
+
+def truth_alignment(genomes, origins):
+    """The same one-block truth in the arrays of a fetched alignment -> dict(left, right, reverse [1, N], col_off [2], cols): what
+    Context.score_truth takes.  Same ValueError on inversions as truth_xmfa."""
+    N = len(genomes)
+    allk, col, ncol = _truth_columns(origins, "truth_alignment")
+    cols = np.zeros(ncol, np.uint32)
+    np.bitwise_or.at(cols, col, (np.uint32(1) << allk[:, 3].astype(np.uint32)))
+    lens = np.array([len(g) for g in genomes], np.int64)
+    return {"left": (lens > 0).astype(np.int64)[None, :], "right": lens[None, :].copy(), "reverse": np.zeros((1, N), np.int8),
+            "col_off": np.array([0, ncol], np.int64), "cols": cols}

@@ -268,6 +268,11 @@ struct mauve_ctx {
     struct CoordIndex { bool valid = false; int N = 0; int64_t n_iv = 0, n_cols = 0; uint64_t genome_gen = 0; struct ::CoordDev *dev = nullptr; } co;     // dev: the kernels' view of the index, owned by coord_dev.hip (coord_index_release)
     DevBuf co_index, co_q;               // the index; one chunk of queries and their answers
     PinnedBuf pin_coord;                 // ... on their way from / to pageable caller arrays, and the error flag
+    // scoring against a correct alignment (score_dev.hip): a second index, of the correct alignment, read-only beside the one in
+    // force; replaced by the next mauve_score_truth, untouched by mauve_coord_index*, alignments and genome uploads
+    CoordIndex co_truth;
+    DevBuf co_truth_index, sc_out;       // that index; the error flag and the records
+    PinnedBuf pin_sc;                    // the error flag coming back, staging of pageable records
     // column extraction (extract_dev.hip): the selection a fetch turns into letters -- the selected columns as (interval, column)
     // in ex_sel, with the request; it belongs to the index and the genomes it was made on (an index call clears `valid`, genome_gen tells an upload)
     struct ExtractSel {
@@ -516,7 +521,10 @@ int assemble_device(mauve_ctx *c, int64_t na, int64_t cells, mauve_align_sizes *
 // or above nseq -- else MAUVE_ERR_ARG with `who` in the text (backbone_dev.hip; the _alignment entry points of the backbone, the homology
 // pass and the coordinate index)
 int check_columns(mauve_ctx *c, const char *who, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int64_t *col_off, const uint32_t *d_cols);
-void coord_index_release(mauve_ctx *c);  // coord_dev.hip: the host side of the coordinate index (its device buffers go with the context's DevBufs)
+void coord_index_release(mauve_ctx *c);  // coord_dev.hip: the host side of the coordinate indices (their device buffers go with the context's DevBufs)
+// coord_dev.hip: the index of a caller's alignment into the slot X / index (mauve_coord_index_alignment: co / co_index; mauve_score_truth: co_truth / co_truth_index)
+int coord_index_arrays(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right,
+                       const int8_t *reverse, const int64_t *col_off, const uint32_t *cols);
 int materialize_result(mauve_ctx *c);
 int materialize_tables(mauve_ctx *c);
 int fetch_columns(mauve_ctx *c, uint32_t *dst);

@@ -19,25 +19,14 @@
 #include <algorithm>
 #include <cstring>
 
-constexpr int CO_SAMPLE = 512;                    // residues between two samples; more than a block holds, so a block carries at most one
-
-void coord_index_release(mauve_ctx *c) { delete c->co.dev; c->co.dev = nullptr; c->co.valid = false; }
+void coord_index_release(mauve_ctx *c)
+{
+    for (mauve_ctx::CoordIndex *X : {&c->co, &c->co_truth}) { delete X->dev; X->dev = nullptr; X->valid = false; }
+}
 
 namespace {
 
 struct CoordTotals { int64_t v[MAUVE_MAX_SEQ]; };  // residues of every genome by the interval ends
-
-// position of the k-th (0-based) set bit of x; x holds more than k
-__device__ __forceinline__ int co_select64(uint64_t x, int k)
-{
-    int pos = 0;
-#pragma unroll
-    for (int s = 32; s; s >>= 1) {
-        const int c = __popcll((x >> pos) & ((1ull << s) - 1));
-        if (k >= c) { k -= c; pos += s; }
-    }
-    return pos;
-}
 
 __global__ void __launch_bounds__(256) coord_build(const uint32_t *__restrict__ cols, int64_t n_cols, int N, int64_t nb1, CoordRec *__restrict__ rec, uint32_t *__restrict__ cnt)
 {
@@ -100,35 +89,6 @@ __global__ void __launch_bounds__(256) coord_iv_rows(CoordDev D, const int64_t *
     ivt[t] = CoordIv{left[t], right[t], co_rank(r, (int)(x - b * CO_BLOCK), &present), x << 1 | (rev[t] ? 1 : 0)};
 }
 
-// rule 2: the interval and the (whole-array) column of base p of genome g, and the interval's first column.  0 found, 1 no interval covers p, else an error flag
-__device__ __forceinline__ uint32_t co_find(const CoordDev &D, int64_t g, int64_t p, int64_t *iv, int64_t *x, int64_t *col0, uint32_t *bad)
-{
-    if (g < 0 || g >= D.N || p < 1) { *bad = CO_BAD_ARG; return 2; }
-    uint32_t a = D.tab_off[g], e = D.tab_off[g + 1];
-    if (a == e || D.tleft[a] > p) return 1;
-    while (e - a > 1) { const uint32_t mid = (a + e) >> 1; if (D.tleft[mid] <= p) a = mid; else e = mid; }
-    if (p > D.tright[a]) return 1;
-    const int64_t i = D.tiv[a];
-    const CoordIv I = D.ivt[(size_t)i * D.N + g];
-    const int64_t T = I.base + ((I.col0_rev & 1) ? I.right - p : p - I.left);          // rank of the residue in the whole array
-    const int64_t j = T / CO_SAMPLE, cap = (int64_t)D.samp_off[g + 1] - D.samp_off[g];
-    if (j + 1 >= cap) { *bad = CO_BAD_INDEX; return 2; }
-    int64_t lo = D.samp[D.samp_off[g] + j], hi = D.samp[D.samp_off[g] + j + 1];
-    if (hi >= D.nb1) hi = D.nb1 - 1;
-    while (hi > lo) { const int64_t mid = (lo + hi + 1) >> 1; if (D.rec[(size_t)mid * D.N + g].rank <= T) lo = mid; else hi = mid - 1; }
-    const CoordRec r = D.rec[(size_t)lo * D.N + g];
-    int64_t rem = T - r.rank;
-    uint64_t ww = 0; int wk = -1;
-#pragma unroll
-    for (int k = 0; k < CO_WORDS; k++) {
-        const int c = __popcll(r.w[k]);
-        if (wk < 0) { if (rem >= 0 && rem < c) { wk = k; ww = r.w[k]; } else rem -= c; }
-    }
-    if (wk < 0) { *bad = CO_BAD_INDEX; return 2; }
-    *iv = i; *x = lo * CO_BLOCK + wk * 64 + co_select64(ww, (int)rem); *col0 = I.col0_rev >> 1;
-    return 0;
-}
-
 // rules 1 and 3: a thread per (query, genome); the 64 / N queries of a wave lie in consecutive lanes, so a query's `defined` mask is a
 // piece of one ballot and the positions leave in one coalesced store.  FROM_POS: the column comes from rule 2 (every lane of a query
 // runs the same search: the loads are the same addresses)
@@ -189,22 +149,25 @@ __global__ void __launch_bounds__(256) coord_select(CoordDev D, int64_t n, const
 inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 // the kernels turn column offsets into block indices: they ascend from 0 (checked before anything is sized by them)
-int coord_check_offsets(mauve_ctx *c, int64_t n_iv, const int64_t *col_off)
+int coord_check_offsets(mauve_ctx *c, const char *who, int64_t n_iv, const int64_t *col_off)
 {
     bool ok = col_off[0] == 0;
     for (int64_t i = 0; i < n_iv && ok; i++) ok = col_off[i + 1] >= col_off[i];
-    if (!ok) c->err = "coord_index: col_off must ascend from 0";
+    if (!ok) c->err = std::string(who) + ": col_off must ascend from 0";
     return ok ? MAUVE_OK : MAUVE_ERR_ARG;
 }
 
-// Build the index of an alignment whose columns are on the device (d_cols) and whose interval table is on the host.
-int coord_build_index(mauve_ctx *c, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off, const uint32_t *d_cols)
+// Build the index of an alignment whose columns are on the device (d_cols) and whose interval table is on the host, into the slot X with
+// its buffer (the index in force: ctx->co / co_index; the correct alignment of DESIGN.md S17: ctx->co_truth / co_truth_index).  bb_work is
+// scratch of the build: the call ends in a stream synchronise.
+int coord_build_index(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse,
+                      const int64_t *col_off, const uint32_t *d_cols)
 {
-    mauve_ctx::CoordIndex &X = c->co;
     X.valid = false;
-    if (N < 1 || N > MAUVE_MAX_SEQ) { c->err = "coord_index: genome count out of range"; return MAUVE_ERR_ARG; }
+    const std::string w = who;
+    if (N < 1 || N > MAUVE_MAX_SEQ) { c->err = w + ": genome count out of range"; return MAUVE_ERR_ARG; }
     const int64_t n_cols = col_off[n_iv], nb1 = n_cols / CO_BLOCK + 1;
-    if (n_iv * N > 0x7fffffff || nb1 * N > 0x7fffffff) { c->err = "coord_index: alignment too large for the index"; return MAUVE_ERR_LIMIT; }
+    if (n_iv * N > 0x7fffffff || nb1 * N > 0x7fffffff) { c->err = w + ": alignment too large for the index"; return MAUVE_ERR_LIMIT; }
     // the genome tables: every genome's intervals by left end; a base lies in at most one of them (rule 2 needs that)
     struct Row { int64_t left, right, iv; };
     std::vector<int64_t> tleft, tright, tiv;
@@ -215,13 +178,13 @@ int coord_build_index(mauve_ctx *c, int N, int64_t n_iv, const int64_t *left, co
         rows.clear();
         for (int64_t i = 0; i < n_iv; i++) {
             const int64_t l = left[(size_t)(i * N + g)], r = right[(size_t)(i * N + g)];
-            if (l < 0 || (l && r < l)) { c->err = "coord_index: interval " + std::to_string(i) + " has ends out of order in genome " + std::to_string(g); return MAUVE_ERR_ARG; }
+            if (l < 0 || (l && r < l)) { c->err = w + ": interval " + std::to_string(i) + " has ends out of order in genome " + std::to_string(g); return MAUVE_ERR_ARG; }
             if (l) { rows.push_back(Row{l, r, i}); want.v[g] += r - l + 1; }
         }
         std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.left != b.left ? a.left < b.left : a.iv < b.iv; });
         for (size_t k = 1; k < rows.size(); k++)
             if (rows[k].left <= rows[k - 1].right) {
-                c->err = "coord_index: intervals " + std::to_string(rows[k - 1].iv) + " and " + std::to_string(rows[k].iv) + " overlap in genome " + std::to_string(g);
+                c->err = w + ": intervals " + std::to_string(rows[k - 1].iv) + " and " + std::to_string(rows[k].iv) + " overlap in genome " + std::to_string(g);
                 return MAUVE_ERR_ARG;
             }
         D.tab_off[g] = (uint32_t)tleft.size();
@@ -238,9 +201,9 @@ int coord_build_index(mauve_ctx *c, int N, int64_t n_iv, const int64_t *left, co
     const size_t w_pre = up64(n_rec * 4), w_bsum = w_pre + up64((n_rec + 1) * 8), w_left = w_bsum + up64((size_t)n_tiles * 8), w_right = w_left + up64(n_ivg * 8),
                  w_rev = w_right + up64(n_ivg * 8), w_flag = w_rev + up64(n_ivg), w_total = w_flag + 64;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->co_index.ensure(total + 64));
+    HIPCHK(c, index.ensure(total + 64));
     HIPCHK(c, c->bb_work.ensure(w_total));
-    char *ix = c->co_index.as<char>(), *wk = c->bb_work.as<char>();
+    char *ix = index.as<char>(), *wk = c->bb_work.as<char>();
     D.rec = reinterpret_cast<const CoordRec *>(ix); D.ivt = reinterpret_cast<const CoordIv *>(ix + o_ivt); D.col_off = reinterpret_cast<const int64_t *>(ix + o_off);
     D.tleft = reinterpret_cast<const int64_t *>(ix + o_tl); D.tright = reinterpret_cast<const int64_t *>(ix + o_tr); D.tiv = reinterpret_cast<const int64_t *>(ix + o_ti);
     D.samp = reinterpret_cast<const uint32_t *>(ix + o_samp);
@@ -274,7 +237,7 @@ int coord_build_index(mauve_ctx *c, int N, int64_t n_iv, const int64_t *left, co
     uint32_t flag = 0;
     HIPCHK(c, hipMemcpyAsync(&flag, wk + w_flag, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));               // (the tables above are host vectors of this call)
-    if (flag) { c->err = "coord_index: the columns do not hold the residues the interval ends announce"; return MAUVE_ERR_ARG; }
+    if (flag) { c->err = w + ": the columns do not hold the residues the interval ends announce"; return MAUVE_ERR_ARG; }
     if (!X.dev) X.dev = new CoordDev;
     *X.dev = D;
     X.N = N; X.n_iv = n_iv; X.n_cols = n_cols; X.genome_gen = c->genome_gen; X.valid = true;
@@ -364,6 +327,25 @@ int coord_run(mauve_ctx *c, int kind, int64_t n, const int64_t *a, const int64_t
 
 }  // namespace
 
+// The index of a caller's alignment (the arrays of mauve_align_fetch) in the slot X: argument checks, the columns against the interval ends,
+// the build.  bb_cols holds the caller's columns during the call.
+int coord_index_arrays(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right,
+                       const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)
+{
+    X.valid = false;
+    if (nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !col_off || (n_iv && (!left || !right || !reverse)) || (n_iv && col_off[n_iv] > 0 && !cols)) {
+        c->err = std::string(who) + ": bad arguments"; return MAUVE_ERR_ARG;
+    }
+    if (const int rco = coord_check_offsets(c, who, n_iv, col_off)) return rco;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)col_off[n_iv] * 4;
+    HIPCHK(c, c->bb_cols.ensure(nb + 64));
+    if (nb) HIPCHK(c, hipMemcpyAsync(c->bb_cols.p, cols, nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                            // cols is the caller's (pageable) memory
+    if (n_iv) if (const int rcc = check_columns(c, who, nseq, n_iv, left, right, col_off, c->bb_cols.as<uint32_t>())) return rcc;
+    return coord_build_index(c, who, X, index, nseq, n_iv, left, right, reverse, col_off, c->bb_cols.as<uint32_t>());
+}
+
 extern "C" {
 
 int mauve_coord_index(mauve_ctx *c)
@@ -375,7 +357,7 @@ int mauve_coord_index(mauve_ctx *c)
     const int64_t n_iv = R.sz.n_iv;
     if ((int64_t)R.col_off.size() != n_iv + 1) { c->err = "coord_index: no alignment in this context"; return MAUVE_ERR_STATE; }
     const int N = n_iv ? (int)(R.iv_left.size() / (size_t)n_iv) : c->nseq;
-    if (const int rco = coord_check_offsets(c, n_iv, R.col_off.data())) return rco;
+    if (const int rco = coord_check_offsets(c, "coord_index", n_iv, R.col_off.data())) return rco;
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t *d_cols;
     if (R.cols_pending) d_cols = c->res_cols.as<uint32_t>();                // still where the assembly stage wrote them
@@ -385,24 +367,14 @@ int mauve_coord_index(mauve_ctx *c)
         if (nb) HIPCHK(c, hipMemcpyAsync(c->bb_cols.p, R.cols_data(), nb, hipMemcpyHostToDevice, c->stream));
         d_cols = c->bb_cols.as<uint32_t>();
     }
-    return coord_build_index(c, N, n_iv, R.iv_left.data(), R.iv_right.data(), R.iv_reverse.data(), R.col_off.data(), d_cols);
+    return coord_build_index(c, "coord_index", c->co, c->co_index, N, n_iv, R.iv_left.data(), R.iv_right.data(), R.iv_reverse.data(), R.col_off.data(), d_cols);
 }
 
 int mauve_coord_index_alignment(mauve_ctx *c, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)
 {
     if (!c) return MAUVE_ERR_ARG;
     c->co.valid = false; c->ex.valid = false;               // (a selection, DESIGN.md S15, belongs to the index it was made on)
-    if (nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !col_off || (n_iv && (!left || !right || !reverse)) || (n_iv && col_off[n_iv] > 0 && !cols)) {
-        c->err = "coord_index: bad arguments"; return MAUVE_ERR_ARG;
-    }
-    if (const int rco = coord_check_offsets(c, n_iv, col_off)) return rco;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = (size_t)col_off[n_iv] * 4;
-    HIPCHK(c, c->bb_cols.ensure(nb + 64));
-    if (nb) HIPCHK(c, hipMemcpyAsync(c->bb_cols.p, cols, nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                            // cols is the caller's (pageable) memory
-    if (n_iv) if (const int rcc = check_columns(c, "coord_index", nseq, n_iv, left, right, col_off, c->bb_cols.as<uint32_t>())) return rcc;
-    return coord_build_index(c, nseq, n_iv, left, right, reverse, col_off, c->bb_cols.as<uint32_t>());
+    return coord_index_arrays(c, "coord_index", c->co, c->co_index, nseq, n_iv, left, right, reverse, col_off, cols);
 }
 
 int mauve_coord_index_size(mauve_ctx *c, int *nseq, int64_t *n_iv, int64_t *n_cols)

@@ -1,10 +1,11 @@
-// coord_index.hpp -- the coordinate index as its kernels see it: shared by coord_dev.hip, which builds and queries it, and
-// extract_dev.hip, which reads ranks from it.
+// coord_index.hpp -- the coordinate index as its kernels see it: shared by coord_dev.hip, which builds and queries it,
+// extract_dev.hip and pairstat_dev.hip, which read ranks from it, and score_dev.hip, which looks bases up in it (S17).
 #pragma once
 #include "common.hpp"
 
 constexpr int CO_WORDS = 7;                       // 64-column words per block record (with the rank: 64 bytes)
 constexpr int CO_BLOCK = CO_WORDS * 64;           // columns per block
+constexpr int CO_SAMPLE = 512;                    // residues between two samples; more than a block holds, so a block carries at most one
 constexpr uint32_t CO_BAD_ARG = 1u, CO_BAD_INDEX = 2u;      // the error flag: a query out of range; columns that disagree with the interval ends
 
 struct alignas(64) CoordRec { int64_t rank; uint64_t w[CO_WORDS]; };
@@ -37,4 +38,45 @@ __device__ __forceinline__ int64_t co_rank(const CoordRec &r, int off, bool *pre
     }
     *present = p;
     return n;
+}
+
+// position of the k-th (0-based) set bit of x; x holds more than k
+__device__ __forceinline__ int co_select64(uint64_t x, int k)
+{
+    int pos = 0;
+#pragma unroll
+    for (int s = 32; s; s >>= 1) {
+        const int c = __popcll((x >> pos) & ((1ull << s) - 1));
+        if (k >= c) { k -= c; pos += s; }
+    }
+    return pos;
+}
+
+// rule 2: the interval and the (whole-array) column of base p of genome g, and the interval's first column.  0 found, 1 no interval covers p, else an error flag
+__device__ __forceinline__ uint32_t co_find(const CoordDev &D, int64_t g, int64_t p, int64_t *iv, int64_t *x, int64_t *col0, uint32_t *bad)
+{
+    if (g < 0 || g >= D.N || p < 1) { *bad = CO_BAD_ARG; return 2; }
+    uint32_t a = D.tab_off[g], e = D.tab_off[g + 1];
+    if (a == e || D.tleft[a] > p) return 1;
+    while (e - a > 1) { const uint32_t mid = (a + e) >> 1; if (D.tleft[mid] <= p) a = mid; else e = mid; }
+    if (p > D.tright[a]) return 1;
+    const int64_t i = D.tiv[a];
+    const CoordIv I = D.ivt[(size_t)i * D.N + g];
+    const int64_t T = I.base + ((I.col0_rev & 1) ? I.right - p : p - I.left);          // rank of the residue in the whole array
+    const int64_t j = T / CO_SAMPLE, cap = (int64_t)D.samp_off[g + 1] - D.samp_off[g];
+    if (j + 1 >= cap) { *bad = CO_BAD_INDEX; return 2; }
+    int64_t lo = D.samp[D.samp_off[g] + j], hi = D.samp[D.samp_off[g] + j + 1];
+    if (hi >= D.nb1) hi = D.nb1 - 1;
+    while (hi > lo) { const int64_t mid = (lo + hi + 1) >> 1; if (D.rec[(size_t)mid * D.N + g].rank <= T) lo = mid; else hi = mid - 1; }
+    const CoordRec r = D.rec[(size_t)lo * D.N + g];
+    int64_t rem = T - r.rank;
+    uint64_t ww = 0; int wk = -1;
+#pragma unroll
+    for (int k = 0; k < CO_WORDS; k++) {
+        const int c = __popcll(r.w[k]);
+        if (wk < 0) { if (rem >= 0 && rem < c) { wk = k; ww = r.w[k]; } else rem -= c; }
+    }
+    if (wk < 0) { *bad = CO_BAD_INDEX; return 2; }
+    *iv = i; *x = lo * CO_BLOCK + wk * 64 + co_select64(ww, (int)rem); *col0 = I.col0_rev >> 1;
+    return 0;
 }
