@@ -4,9 +4,10 @@
 //
 // Shape: the list is a few 10^4 .. 10^5 records and the elimination is a chain of dependent passes (genome after
 // genome, pass after pass).  The passes of one genome decompose into independent overlap clusters (see
-// ch_cluster_pass), so a genome costs a fixed, short sequence of launches -- its order by the radix sort of
-// seed_pass.hip, a prefix maximum of the right ends, the cluster starts, one thread per cluster for ALL its passes,
-// the survivors' order -- with no launch per pass and no host round trip.  The LCB graph (collinear runs in genome-0
+// ch_cluster_pass), and the clusters can be cut from the list as it ENTERS the stage, for every genome alike: the
+// orders of all genomes (one batched radix sort, seed_pass.hip), the prefix maxima of the right ends and the cluster
+// starts are made up front in launches with a genome dimension, and a genome's turn is ONE launch -- one thread per
+// cluster for ALL its passes -- with no launch per pass and no host round trip.  The LCB graph (collinear runs in genome-0
 // order, their weights, the per-genome neighbour lists) is built by flag compactions; the greedy breakpoint
 // elimination over that compact graph (10^2 .. 10^4 nodes, inherently sequential) stays on the host (lcb_greedy,
 // chain_host.cpp).  Every kernel is tiled (1024 entries per workgroup, four consecutive entries per thread); the
@@ -25,18 +26,40 @@ namespace {
 using namespace devscan;
 constexpr int CH_TILE = devscan::TILE;
 
-// records as the seed pass left them (int64 length[n], start[n*N]) -> working arrays (int32)
+// the counter block: [0] na, [1] K, [2] link check, [3] fail, [CH_CNT_ALIVE + g] entries of genome g alive when the stage starts,
+// [CH_CNT_CL + g] overlap clusters of genome g.  (chain_order_device keeps two words at 16 once the graph is done; the host reads the
+// first 64 words back, the per-genome cluster counts are read on the device only.)
+constexpr int CH_CNT_ALIVE = 8, CH_CNT_CL = CH_CNT_ALIVE + MAUVE_MAX_SEQ, CH_CNT_WORDS = 128;
+static_assert(CH_CNT_CL + MAUVE_MAX_SEQ <= CH_CNT_WORDS && CH_CNT_WORDS <= 256, "counter block");
+
+// Where the sort keys of the genomes go: (left end, match index) of genome g at key / val + g * n, except those of a genome that needs
+// no sort (key0 / val0: genome 0 of the main list, already in order), which go where the sorted ones end up.
+struct ChKeyDst { uint32_t *key, *val, *key0, *val0; };
+// sort key of match i in genome g: the left end of an alive match (dead ones sort behind everything), value = match index
+__device__ __forceinline__ void ch_put_key(const ChKeyDst &kd, uint32_t n, uint32_t i, int g, int32_t s, bool alive, uint32_t dead_key)
+{
+    uint32_t *k = g ? kd.key + (size_t)g * n : kd.key0, *v = g ? kd.val + (size_t)g * n : kd.val0;
+    k[i] = alive ? (uint32_t)(s < 0 ? -s : s) : dead_key;
+    v[i] = i;
+}
+
+// records as the seed pass left them (int64 length[n], start[n*N]) -> working arrays (int32), and the sort keys of every genome
 // (both init kernels also clear what the stage accumulates into -- the counter block and the node weights -- instead of two memsets)
 __global__ void __launch_bounds__(256) ch_init(const int64_t *__restrict__ rlen, const int64_t *__restrict__ rst, uint32_t n, int N,
                                                int32_t *__restrict__ len, int32_t *__restrict__ st, uint32_t *__restrict__ crop,
-                                               uint32_t *__restrict__ cnt, unsigned long long *__restrict__ weight)
+                                               uint32_t *__restrict__ cnt, unsigned long long *__restrict__ weight, ChKeyDst kd, uint32_t dead_key)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < 64) cnt[i] = 0;
+    if (i < (uint32_t)CH_CNT_WORDS) cnt[i] = 0;
     if (i >= n) return;
     weight[i] = 0;
-    len[i] = (int32_t)rlen[i];
-    for (int g = 0; g < N; g++) st[(size_t)i * N + g] = (int32_t)rst[(size_t)i * N + g];
+    const int32_t l = (int32_t)rlen[i];
+    len[i] = l;
+    for (int g = 0; g < N; g++) {
+        const int32_t s = (int32_t)rst[(size_t)i * N + g];
+        st[(size_t)i * N + g] = s;
+        ch_put_key(kd, n, i, g, s, l > 0, dead_key);
+    }
     crop[2 * (size_t)i] = 0; crop[2 * (size_t)i + 1] = 0;
 }
 
@@ -46,15 +69,17 @@ __global__ void __launch_bounds__(256) ch_init(const int64_t *__restrict__ rlen,
 __global__ void __launch_bounds__(256) ch_init_seg(const int64_t *__restrict__ rlen, const int64_t *__restrict__ rst, uint32_t n, int N,
                                                    const uint32_t *__restrict__ seg0, uint32_t K, int32_t *__restrict__ len, int32_t *__restrict__ st,
                                                    uint32_t *__restrict__ crop, uint32_t *__restrict__ gapid,
-                                                   uint32_t *__restrict__ cnt, unsigned long long *__restrict__ weight)
+                                                   uint32_t *__restrict__ cnt, unsigned long long *__restrict__ weight, ChKeyDst kd, uint32_t dead_key)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < 64) cnt[i] = 0;
+    if (i < (uint32_t)CH_CNT_WORDS) cnt[i] = 0;
     if (i >= n) return;
     weight[i] = 0;
     bool fwd = true;
     for (int g = 0; g < N; g++) { const int64_t s = rst[(size_t)i * N + g]; st[(size_t)i * N + g] = (int32_t)s; fwd &= s > 0; }
-    len[i] = fwd ? (int32_t)rlen[i] : 0;
+    const int32_t l = fwd ? (int32_t)rlen[i] : 0;
+    len[i] = l;
+    for (int g = 0; g < N; g++) ch_put_key(kd, n, i, g, (int32_t)rst[(size_t)i * N + g], l > 0, dead_key);    // (a batch starts with its non-forward matches dead)
     crop[2 * (size_t)i] = 0; crop[2 * (size_t)i + 1] = 0;
     const uint32_t p0 = (uint32_t)(rst[(size_t)i * N] > 0 ? rst[(size_t)i * N] - 1 : 0);
     uint32_t lo = 0, hi = K;                                     // last k with seg0[k] <= p0
@@ -62,26 +87,12 @@ __global__ void __launch_bounds__(256) ch_init_seg(const int64_t *__restrict__ r
     gapid[i] = lo;
 }
 
-// sort keys of genome g: left end of every alive match (dead ones sort behind everything), value = match index
-__global__ void __launch_bounds__(256) ch_keys(const int32_t *__restrict__ len, const int32_t *__restrict__ st, uint32_t n, int N, int g,
-                                               uint32_t dead_key, uint32_t *__restrict__ key, uint32_t *__restrict__ val)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const int32_t s = st[(size_t)i * N + g];
-    key[i] = len[i] > 0 ? (uint32_t)(s < 0 ? -s : s) : dead_key;
-    val[i] = i;
-}
-
 // ---- EliminateOverlaps of one genome, decomposed into overlap clusters ----------------------------
-// The passes of genome g only ever shrink intervals in g, so two matches interact only if their intervals are linked
-// through a chain of overlaps when g's turn starts: cut the (left end, index) order wherever the running maximum of
-// the right ends stays below the next left end, and the pieces -- clusters -- never see each other again: the global
-// order is the concatenation of the clusters' orders and no pair across a cut ever overlaps.  Every cluster
-// therefore runs ALL its passes on its own (sort, sweep of adjacent pairs, crops applied together, the dead leave,
-// repeat until overlap free), exactly as the whole list would, and the clusters run side by side, one thread each:
-// no pass-by-pass launches, no host round trip.  Nearly all clusters are pairs; one beyond CH_CL_MAX entries (a
-// repeat family) raises *fail and the host chains this list with chain_host.cpp instead.
+// Cut genome g's (left end, index) order wherever the running maximum of the right ends stays below the next left
+// end; the pieces are the clusters (the partition argument is above ch_cluster_pass).  The three kernels below make
+// the cuts of ALL genomes (blockIdx.y) from the list as it enters the stage.  Nearly all clusters are single entries
+// or pairs; one beyond CH_CL_MAX entries (a repeat family) raises *fail and the host chains this list with
+// chain_host.cpp instead.
 constexpr int CH_CL_MAX = 48;
 
 // right end of entry r (0 for the dead entries behind the alive ones and beyond the list)
@@ -93,11 +104,13 @@ __device__ __forceinline__ uint32_t ch_right(const int32_t *__restrict__ len, ui
     return l == dead_key ? 0u : l + (uint32_t)len[eidx[r]] - 1u;
 }
 
-// per tile: the largest right end and the number of alive entries
+// per tile: the largest right end and the number of alive entries (blockIdx.y: the genome; its order at eleft / eidx + y * n)
 __global__ void __launch_bounds__(256) cl_partial(const int32_t *__restrict__ len, uint32_t n, uint32_t dead_key, const uint32_t *__restrict__ eleft,
                                                   const uint32_t *__restrict__ eidx, uint32_t *__restrict__ bmax, uint32_t *__restrict__ balive)
 {
     __shared__ uint32_t lds[4];
+    eleft += (size_t)blockIdx.y * n; eidx += (size_t)blockIdx.y * n;
+    bmax += (size_t)blockIdx.y * gridDim.x; balive += (size_t)blockIdx.y * gridDim.x;
     const uint32_t r0 = blockIdx.x * (uint32_t)CH_TILE + threadIdx.x * 4u;
     uint32_t mx = 0, c = 0;
 #pragma unroll
@@ -114,9 +127,12 @@ __global__ void __launch_bounds__(256) cl_partial(const int32_t *__restrict__ le
 __global__ void __launch_bounds__(256) cl_flags(const int32_t *__restrict__ len, uint32_t n, uint32_t dead_key, const uint32_t *__restrict__ eleft,
                                                 const uint32_t *__restrict__ eidx, const uint32_t *__restrict__ bmax,
                                                 const uint32_t *__restrict__ balive, uint32_t nb, uint8_t *__restrict__ cflag,
-                                                uint32_t *__restrict__ cnt, uint32_t *__restrict__ bcnt, uint32_t *__restrict__ alive_out)
+                                                uint32_t *__restrict__ cnt, uint32_t *__restrict__ bcnt)
 {
     __shared__ uint32_t lds[4];
+    const int y = blockIdx.y;
+    eleft += (size_t)y * n; eidx += (size_t)y * n; cflag += (size_t)y * n;
+    bmax += (size_t)y * nb; balive += (size_t)y * nb; bcnt += (size_t)y * nb;
     const uint32_t b = blockIdx.x, r0 = b * (uint32_t)CH_TILE + threadIdx.x * 4u;
     uint32_t mb = 0;
     for (uint32_t t = threadIdx.x; t < b; t += 256) mb = max(mb, bmax[t]);
@@ -139,26 +155,26 @@ __global__ void __launch_bounds__(256) cl_flags(const int32_t *__restrict__ len,
         (void)bscan_add(nflag, &tc, lds);
         if (threadIdx.x == 0) bcnt[b] = tc;
     }
-    if (b == 0) {                                        // alive entries of the genome in turn -> cnt[5]
+    if (b == 0) {                                        // alive entries of the genome: where its last cluster ends
         uint32_t sa = 0, k;
         for (uint32_t t = threadIdx.x; t < nb; t += 256) sa += balive[t];
         (void)bscan_add(sa, &k, lds);
-        if (threadIdx.x == 0) { cnt[5] = k; *alive_out = k; }      // (alive_out: kept per genome, the domain of FinalRanks)
+        if (threadIdx.x == 0) cnt[CH_CNT_ALIVE + y] = k;
     }
 }
 
-struct ClusterStarts {                      // flagged entries -> cstart[]; cstart[J] = k
+struct ClusterStarts {                      // y = genome: flagged entries -> cstart[y][] (n + 1 words a genome); cstart[y][J] = its alive entries
     const uint8_t *cflag; uint32_t n; uint32_t *cstart; uint32_t *cnt;
     __device__ uint32_t domain(int) const { return n; }
-    __device__ bool flag(uint32_t r, int) const { return cflag[r] != 0; }
+    __device__ bool flag(uint32_t r, int y) const { return cflag[(size_t)y * n + r] != 0; }
     __device__ void each(uint32_t, uint32_t, bool, int) const {}
-    __device__ void emit(uint32_t r, uint32_t o, int) const { cstart[o] = r; }
-    __device__ void total(uint32_t J, int) const { cnt[4] = J; cstart[J] = cnt[5]; }
+    __device__ void emit(uint32_t r, uint32_t o, int y) const { cstart[(size_t)y * (n + 1) + o] = r; }
+    __device__ void total(uint32_t J, int y) const { cnt[CH_CNT_CL + y] = J; cstart[(size_t)y * (n + 1) + J] = cnt[CH_CNT_ALIVE + y]; }
 };
-struct FinalRanks {                         // y = genome: its order (as its cluster pass left it: the entries alive BEFORE that pass, those it killed marked by
-                                            // the dead key) without the matches that died then or later; rank of every survivor
+struct FinalRanks {                         // y = genome: its order (the whole segment, as its cluster pass left it: the members a pass killed marked by the
+                                            // dead key, single entries still under the key they came with) without the dead; rank of every survivor
     const int32_t *len; uint32_t n; const uint32_t *ord, *okey; uint32_t dead_key; uint32_t *ordc, *rank; uint32_t *cnt;
-    __device__ uint32_t domain(int y) const { return cnt[8 + y]; }
+    __device__ uint32_t domain(int) const { return n; }
     __device__ bool flag(uint32_t r, int y) const { return okey[(size_t)y * n + r] != dead_key && len[ord[(size_t)y * n + r]] > 0; }
     __device__ void each(uint32_t, uint32_t, bool, int) const {}
     __device__ void emit(uint32_t r, uint32_t o, int y) const { const uint32_t i = ord[(size_t)y * n + r]; ordc[(size_t)y * n + o] = i; rank[(size_t)y * n + i] = o; }
@@ -222,19 +238,37 @@ __global__ void __launch_bounds__(256) ch_links(int N, const uint32_t *__restric
     nextv[(size_t)nd * N + g] = j + 1 < K ? sq[j + 1] : -1;
 }
 
-// ch_cluster_pass: thread j runs every pass of cluster j.  Entries come back in (left end, index) order, the dead
-// behind them as dead_key; the survivors' crops are applied to the match records (all genomes) at the end.
-// all passes of one cluster (entries a .. a + s of the genome's order); the working arrays hold s entries each
+// ---- ch_cluster_pass: the elimination of genome g, thread j runs every pass of cluster j ----
+// The partition.  The clusters of every genome are cut from the list as it ENTERS the stage (cl_partial, cl_flags, ClusterStarts),
+// not from the records as they are at g's turn.  That is sound because a crop only shrinks a match's interval, in every genome,
+// and a dead match vanishes: two matches in different clusters of g did not overlap in g at the start (every original interval of
+// an earlier cluster ends left of every one of a later cluster), their current intervals lie inside the original ones, so they do
+// not overlap in g at g's turn either, nor during its passes.  The elimination of a genome decomposes over any partition in which
+// no two matches of different groups overlap: every group runs ALL its passes on its own (sort by the CURRENT (left end, index),
+// sweep of adjacent pairs, crops applied together, the dead leave, repeat until overlap free), exactly as the whole list would,
+// and the groups run side by side.  The clusters cut at g's turn would be such a partition too, only a finer one.  And since the
+// groups stay in their original left-to-right order, the concatenation of their sorted orders is the genome's order by current
+// left end: what FinalRanks needs.
+// A cluster's members come from the order made up front (eidx), their left end, length and strand from the current records -- the
+// key array is as old as the order; members that earlier genomes killed are dropped as they load (left in place, a dead entry would
+// hide the overlap of its two neighbours from the adjacent-pair sweep).  The survivors go back in (left end, index) order, the rest
+// of the cluster's slice as dead_key; the survivors' crops are applied to the match records (all genomes) at the end.
+// all passes of one cluster (entries a .. a + s0 of the genome's order); the working arrays hold s0 entries each
 __device__ __forceinline__ void ch_cluster_run(int32_t *__restrict__ len, int32_t *__restrict__ st, int N, int g, uint32_t dead_key,
-                                               uint32_t *__restrict__ eleft, uint32_t *__restrict__ eidx, uint32_t a, int s,
+                                               uint32_t *__restrict__ eleft, uint32_t *__restrict__ eidx, uint32_t a, const int s0,
                                                uint32_t *L, uint32_t *Ln, uint32_t *I, uint32_t *CF, uint32_t *CL, uint32_t *pf, uint32_t *pl, uint8_t *F)
 {
     // entry state: left end in g, length, index, forward in g, crops so far at the match's first / last column side
-    for (int q = 0; q < s; q++) {
-        L[q] = eleft[a + q]; I[q] = eidx[a + q]; Ln[q] = (uint32_t)len[I[q]]; F[q] = st[(size_t)I[q] * N + g] > 0;
-        CF[q] = 0; CL[q] = 0;
+    int s = 0;
+    for (int q = 0; q < s0; q++) {
+        const uint32_t i = eidx[a + q];
+        const int32_t ln = len[i];
+        if (ln <= 0) continue;
+        const int32_t v = st[(size_t)i * N + g];
+        L[s] = (uint32_t)(v < 0 ? -v : v); I[s] = i; Ln[s] = (uint32_t)ln; F[s] = v > 0;
+        CF[s] = 0; CL[s] = 0;
+        s++;
     }
-    const int s0 = s;
     for (;;) {
         // (left end, index) order; the entries arrive sorted and a pass of crops moves them little: insertion sort
         for (int q = 1; q < s; q++) {
@@ -288,6 +322,7 @@ __global__ void __launch_bounds__(256) ch_cluster_pass(int32_t *__restrict__ len
                                                        const uint32_t *__restrict__ cstart, const uint32_t *__restrict__ cnt_in,
                                                        uint32_t *__restrict__ fail, int leave_big, int cl_max)
 {
+    // cstart, cnt_in: the genome's cluster starts and their number, made up front.
     // Nearly every thread has a cluster of one and leaves at once; the few that work keep their arrays in LDS (a slot each,
     // handed out by a counter; sized by the cluster: 8 words per entry) instead of in scratch, whose latency was the kernel's
     // whole run time.  A block that runs out of LDS falls back to scratch for the rest.
@@ -607,22 +642,23 @@ int chain_device_graph(mauve_ctx *c, int N, int64_t maxlen_in, const uint32_t *s
     HIPCHK(c, c->ch_st.ensure((size_t)n * N * 4));
     HIPCHK(c, c->ch_crop.ensure((size_t)n * 8));
     const uint32_t nb = (n + CH_TILE - 1) / CH_TILE;
-    HIPCHK(c, c->ch_ent.ensure((size_t)n * 4 * 6 + 64 + (size_t)n + 64 + (size_t)nb * 4 * (2 + (size_t)N)));   // 2 x (key, val) for the sort, the cluster starts, flags, tile aggregates
+    const size_t sl_words = ((size_t)N * ((size_t)n + 1) + 15) & ~(size_t)15, flag_bytes = ((size_t)N * n + 63) & ~(size_t)63;
+    HIPCHK(c, c->ch_ent.ensure((size_t)n * 4 * 4 + sl_words * 4 + flag_bytes + (size_t)nb * 4 * 3 * (size_t)N + 64));   // 2 x (key, val) of chain_order_device's sort; per genome:
+                                                                  // the cluster starts, flags, tile aggregates
     HIPCHK(c, c->ch_ord.ensure((size_t)n * N * 4 * 3));           // ord[N][n], ordc[N][n], okey[N][n]: the genomes' orders and their keys as the cluster passes leave them
     HIPCHK(c, c->ch_rank.ensure((size_t)n * N * 4));
-    HIPCHK(c, c->ch_cnt.ensure(256));
+    HIPCHK(c, c->ch_cnt.ensure((size_t)CH_CNT_WORDS * 4));
     if (seg0) HIPCHK(c, c->ch_big.ensure((size_t)n * 29 + 64));   // working arrays of the big clusters
     int32_t *len = c->ch_len.as<int32_t>(), *node_of = len + n;
     uint32_t *gapid = seg0 ? reinterpret_cast<uint32_t *>(len + 3 * (size_t)n) : nullptr;
     int32_t *st = c->ch_st.as<int32_t>();
     uint32_t *crop = c->ch_crop.as<uint32_t>();
-    uint32_t *k1 = c->ch_ent.as<uint32_t>(), *v1 = k1 + n, *k2 = v1 + n, *v2 = k2 + n, *sl = v2 + n;     // sl: cluster starts (up to n + 1)
-    uint8_t *cflag = reinterpret_cast<uint8_t *>(sl + 2 * (size_t)n + 16);
-    uint32_t *bmax = reinterpret_cast<uint32_t *>(cflag + (((size_t)n + 63) & ~(size_t)63)), *balive = bmax + nb, *bcnt = balive + nb;
+    uint32_t *sl = c->ch_ent.as<uint32_t>() + 4 * (size_t)n;     // sl: cluster starts, n + 1 words a genome
+    uint8_t *cflag = reinterpret_cast<uint8_t *>(sl + sl_words);
+    uint32_t *bmax = reinterpret_cast<uint32_t *>(cflag + flag_bytes), *balive = bmax + (size_t)N * nb, *bcnt = balive + (size_t)N * nb;
     uint32_t *ord = c->ch_ord.as<uint32_t>(), *ordc = ord + (size_t)n * N, *okey = ordc + (size_t)n * N;
     uint32_t *rank = c->ch_rank.as<uint32_t>();
-    uint32_t *cnt = c->ch_cnt.as<uint32_t>();                     // [0] na, [1] K, [2] link check, [3] fail, [4] clusters, [5] alive entries of the genome in turn,
-                                                                  // [8+g] entries of genome g alive before its cluster pass (the domain of FinalRanks)
+    uint32_t *cnt = c->ch_cnt.as<uint32_t>();                     // (layout: CH_CNT_ALIVE)
     const int64_t *rlen = c->sorted_rec.as<int64_t>(), *rst = rlen + n;
     const uint32_t blocks = (n + 255) / 256;
     static const int big_max = []() { const char *e = getenv("MAUVE_CH_BIG_MAX"); const int v = e ? atoi(e) : 2048; return v < 1 ? 1 : v; }();        // cluster size the one-lane kernel still takes (tests lower it)
@@ -630,33 +666,35 @@ int chain_device_graph(mauve_ctx *c, int N, int64_t maxlen_in, const uint32_t *s
     // the graph arrays are sized for the worst case K = n
     HIPCHK(c, c->ch_graph.ensure((size_t)n * (8 + 4 + (size_t)N * 4 * 3 + 4) + 8 + (size_t)n * (8 + 4 + (size_t)N * 8) + 64));     // the arrays + their packed copy
     unsigned long long *weight = c->ch_graph.as<unsigned long long>();
-    if (seg0) hipLaunchKernelGGL(ch_init_seg, dim3(blocks), dim3(256), 0, c->stream, rlen, rst, n, N, seg0, nseg, len, st, crop, gapid, cnt, weight);
-    else hipLaunchKernelGGL(ch_init, dim3(blocks), dim3(256), 0, c->stream, rlen, rst, n, N, len, st, crop, cnt, weight);
+    // The orders of all genomes, from the list as it comes in.  Every genome's order and keys end up in (okey, ord)[g], where its cluster pass
+    // leaves them and FinalRanks compacts from at the end; ordc and rank, which FinalRanks writes, are the sort's alternate buffers until then.
+    // The radix sort ends in its alternate buffers after an odd number of passes, so the keys are written where that makes the result land in
+    // (okey, ord).  Genome 0 of the main list needs no sort: the list is in canonical order, i.e. already ordered by its left ends there (equal
+    // left ends keep their list order: every pass below breaks ties by the list index, as the host chain does), nobody is dead yet.  (A recursion
+    // batch starts with its non-forward matches dead: genome 0 is sorted like any other.)
     const int sort_passes = (pos_bits + 1 + 7) / 8;
+    const bool odd = sort_passes & 1;
+    const int g_lo = seg0 ? 0 : 1;                                // first genome the sort takes
+    const ChKeyDst kd{odd ? rank : okey, odd ? ordc : ord, seg0 && odd ? rank : okey, seg0 && odd ? ordc : ord};
+    if (seg0) hipLaunchKernelGGL(ch_init_seg, dim3(blocks), dim3(256), 0, c->stream, rlen, rst, n, N, seg0, nseg, len, st, crop, gapid, cnt, weight, kd, dead_key);
+    else hipLaunchKernelGGL(ch_init, dim3(blocks), dim3(256), 0, c->stream, rlen, rst, n, N, len, st, crop, cnt, weight, kd, dead_key);
+    if (g_lo < N) {
+        uint32_t *kk = kd.key + (size_t)g_lo * n, *vv = kd.val + (size_t)g_lo * n;
+        int rc = sort_pairs_u32_batch(c, (uint32_t)(N - g_lo), n, n, pos_bits + 1, &kk, &vv, (odd ? okey : rank) + (size_t)g_lo * n,
+                                      (odd ? ord : ordc) + (size_t)g_lo * n, MAUVE_K_MISC);
+        if (rc) return rc;
+        if (kk != okey + (size_t)g_lo * n || vv != ord + (size_t)g_lo * n) { c->err = "chain_device: the orders did not land in place"; return MAUVE_ERR_STATE; }
+    }
+    // the clusters of all genomes (partition argument: above ch_cluster_pass) ...
+    hipLaunchKernelGGL(cl_partial, dim3(nb, N), dim3(256), 0, c->stream, len, n, dead_key, okey, ord, bmax, balive);
+    hipLaunchKernelGGL(cl_flags, dim3(nb, N), dim3(256), 0, c->stream, len, n, dead_key, okey, ord, bmax, balive, nb, cflag, cnt, bcnt);
+    const ClusterStarts cs{cflag, n, sl, cnt};
+    hipLaunchKernelGGL((cmp_write<ClusterStarts>), dim3(nb, N), dim3(256), 0, c->stream, cs, bcnt);
+    // ... and the elimination, genome after genome: the one step that needs the records as the genome before left them
     for (int g = 0; g < N; g++) {
-        // The genome's order and keys stay where its cluster pass leaves them -- (okey, ord)[g] -- and FinalRanks compacts from there at the end: no
-        // compaction of the survivors per genome (two launches each).  The radix sort ends in its alternate buffers after an odd number of passes, so
-        // the buffers are handed to it the way that makes the result land there.
-        uint32_t *og = ord + (size_t)g * n, *kg = okey + (size_t)g * n;
-        // genome 0: the list is in canonical order, i.e. already ordered by its left ends there (equal left ends keep their list order: every pass
-        // below breaks ties by the list index, as the host chain does), nobody is dead yet
-        // (a recursion batch starts with its non-forward matches dead: sorted like any other genome)
-        const bool sorted = g > 0 || seg0;
-        const bool odd = sorted && (sort_passes & 1);
-        uint32_t *kk = odd ? k1 : kg, *vv = odd ? v1 : og;
-        hipLaunchKernelGGL(ch_keys, dim3(blocks), dim3(256), 0, c->stream, len, st, n, N, g, dead_key, kk, vv);
-        if (sorted) { int rc = sort_pairs_u32(c, n, pos_bits + 1, &kk, &vv, odd ? kg : k2, odd ? og : v2, MAUVE_K_MISC); if (rc) return rc; }
-        if (kk != kg || vv != og) {                               // (the sort took another number of passes than counted here: put the result in place)
-            HIPCHK(c, hipMemcpyAsync(kg, kk, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(og, vv, (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));
-            kk = kg; vv = og;
-        }
-        hipLaunchKernelGGL(cl_partial, dim3(nb), dim3(256), 0, c->stream, len, n, dead_key, kk, vv, bmax, balive);
-        hipLaunchKernelGGL(cl_flags, dim3(nb), dim3(256), 0, c->stream, len, n, dead_key, kk, vv, bmax, balive, nb, cflag, cnt, bcnt, cnt + 8 + g);
-        const ClusterStarts cs{cflag, n, sl, cnt};
-        hipLaunchKernelGGL((cmp_write<ClusterStarts>), dim3(nb), dim3(256), 0, c->stream, cs, bcnt);
-        hipLaunchKernelGGL(ch_cluster_pass, dim3(blocks), dim3(256), 0, c->stream, len, st, N, g, dead_key, kk, vv, sl, cnt + 4, cnt + 3, seg0 ? 1 : 0, cl_max);
-        if (seg0) hipLaunchKernelGGL(ch_cluster_pass_big, dim3((n + 63) / 64), dim3(64), 0, c->stream, len, st, N, g, dead_key, kk, vv, sl, cnt + 4,
+        uint32_t *og = ord + (size_t)g * n, *kg = okey + (size_t)g * n, *sg = sl + (size_t)g * ((size_t)n + 1);
+        hipLaunchKernelGGL(ch_cluster_pass, dim3(blocks), dim3(256), 0, c->stream, len, st, N, g, dead_key, kg, og, sg, cnt + CH_CNT_CL + g, cnt + 3, seg0 ? 1 : 0, cl_max);
+        if (seg0) hipLaunchKernelGGL(ch_cluster_pass_big, dim3((n + 63) / 64), dim3(64), 0, c->stream, len, st, N, g, dead_key, kg, og, sg, cnt + CH_CNT_CL + g,
                                      c->ch_big.as<uint32_t>(), n, cl_max, cnt + 3, big_max);
     }
     const FinalRanks fr{len, n, ord, okey, dead_key, ordc, rank, cnt};

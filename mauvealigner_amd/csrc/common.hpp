@@ -429,6 +429,8 @@ int seedpass_sorted_list(mauve_ctx *ctx, const GenomeSet &gs, int seq, uint64_t 
 
 int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io, uint32_t **vals_io, uint32_t *keys_alt, uint32_t *vals_alt,
                    int timer_id);
+int sort_pairs_u32_batch(mauve_ctx *ctx, uint32_t S, uint32_t n, size_t seg_stride, int key_bits, uint32_t **keys_io, uint32_t **vals_io,
+                         uint32_t *keys_alt, uint32_t *vals_alt, int timer_id);
 int sort_pairs_u64(mauve_ctx *ctx, uint32_t n, int key_bits, uint64_t **keys_io, uint32_t **vals_io, uint64_t *keys_alt, uint32_t *vals_alt,
                    int timer_id);
 // The two translation units of the seed pass: seed_pass.hip (everything that depends on the key and index widths) hands over to

@@ -1503,6 +1503,32 @@ int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io,
 {
     return sort_pairs<uint32_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
 }
+// S such sorts of n pairs each, same key_bits, segment s in the n pairs from s * seg_stride of all four buffers (chain_dev.hip: the orders of all
+// genomes): one batched small sort, or -- engine off, n beyond its range -- S sorts one after another on the same buffers.  Either way every
+// segment gets the permutation and the result-buffer parity of sort_pairs_u32; *keys_io / *vals_io point at segment 0 of the result.
+int sort_pairs_u32_batch(mauve_ctx *ctx, uint32_t S, uint32_t n, size_t seg_stride, int key_bits, uint32_t **keys_io, uint32_t **vals_io,
+                         uint32_t *keys_alt, uint32_t *vals_alt, int timer_id)
+{
+    if (S == 0 || n == 0) return MAUVE_OK;
+    if (S > 65535u || seg_stride < n) { ctx->err = "sort_pairs_u32_batch: bad segment layout"; return MAUVE_ERR_ARG; }
+    if (small_sort_on() && n <= SS_CAP) {
+        const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
+        HIPCHK(ctx, ctx->hist.ensure(ss_ws_words_batch(S, n) * sizeof(uint32_t)));
+        small_sort_batch<uint32_t>(ctx->stream, S, n, seg_stride, key_bits, 0, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
+                                   [&](bool scatter, auto &&launch) { KernelTimer t(ctx, scatter ? k_scat : k_hist, (int64_t)S * n); launch(); });
+        HIPCHK(ctx, hipGetLastError());
+        return MAUVE_OK;
+    }
+    uint32_t *k0 = *keys_io, *v0 = *vals_io;
+    for (uint32_t s = 0; s < S; s++) {
+        uint32_t *kk = *keys_io + s * seg_stride, *vv = *vals_io + s * seg_stride;
+        int rc = sort_pairs<uint32_t>(ctx, n, key_bits, &kk, &vv, keys_alt + s * seg_stride, vals_alt + s * seg_stride, false, timer_id);
+        if (rc) return rc;
+        if (s == 0) { k0 = kk; v0 = vv; }
+    }
+    *keys_io = k0; *vals_io = v0;
+    return MAUVE_OK;
+}
 // ... and of (64-bit key, 32-bit value) pairs (seed_finish.hip)
 int sort_pairs_u64(mauve_ctx *ctx, uint32_t n, int key_bits, uint64_t **keys_io, uint32_t **vals_io, uint64_t *keys_alt, uint32_t *vals_alt,
                    int timer_id)

@@ -17,6 +17,12 @@
 // zeroes slot (p + 2) % 3 (last read by pass p - 1, next added to by pass p + 1), so no memset launch is needed.
 // The permutation is the one of the tiled sort at any tile size (stable LSD), and the result lands in the buffer the
 // pass parity implies: keys_io after an even number of passes, keys_alt after an odd one.
+//
+// Batched form (small_sort_batch): S independent sorts of n pairs each, same key_bits, the segments at a fixed stride in the
+// key, value and alternate buffers (the chain's orders of all genomes, made in one go).  The segment is the grid's y
+// dimension: the kernels offset their pointers by it and every segment has histogram slots of its own, so a launch does
+// what S launches of the single sort would, to every segment exactly what small_sort does to it: the tile class comes
+// from n, not from S * n.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -147,14 +153,20 @@ inline int ss_items(uint32_t n)
 inline uint32_t ss_tiles(uint32_t n, int items) { return (n + (uint32_t)(RS_THREADS * items) - 1) / (uint32_t)(RS_THREADS * items); }
 // workspace of an n-pair sort (three histogram slots), in 32-bit words
 inline size_t ss_ws_words(uint32_t n) { return (size_t)3 * ss_tiles(n, ss_items(n)) * 256; }
+// ... of S such sorts in one batch (three slots of S x nblk x 256 words)
+inline size_t ss_ws_words_batch(uint32_t S, uint32_t n) { return (size_t)S * ss_ws_words(n); }
 
 // tile histogram of the first pass (tile-major: hist[tile * 256 + digit]); hzero (if any): this tile's row of the next slot := 0
+// blockIdx.y: the segment of a batch (keys seg_stride apart, histogram rows of its own behind those of the segments before it)
 template <typename KeyT, int ITEMS>
 __global__ void __launch_bounds__(RS_THREADS) rs_small_hist(const KeyT *__restrict__ keys, uint32_t n, int shift,
-                                                            uint32_t *__restrict__ hist, uint32_t *__restrict__ hzero)
+                                                            uint32_t *__restrict__ hist, uint32_t *__restrict__ hzero, size_t seg_stride)
 {
     __shared__ uint32_t h[256];
     const int tid = threadIdx.x;
+    keys += (size_t)blockIdx.y * seg_stride;
+    hist += (size_t)blockIdx.y * gridDim.x * 256;
+    if (hzero) hzero += (size_t)blockIdx.y * gridDim.x * 256;
     h[tid] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * (uint32_t)(RS_THREADS * ITEMS);
@@ -169,12 +181,13 @@ __global__ void __launch_bounds__(RS_THREADS) rs_small_hist(const KeyT *__restri
 }
 
 // one digit pass: hist = this pass's tile histograms (tile-major, nblk tiles); hnext: next pass's slot (added to), hzero: the
-// slot after it (this tile's row := 0); either may be null
+// slot after it (this tile's row := 0); either may be null.  blockIdx.y: the segment of a batch, as in rs_small_hist
 template <typename KeyT, int ITEMS, typename ValT = uint32_t>
 __global__ void __launch_bounds__(RS_THREADS) rs_small_scatter(const KeyT *__restrict__ keys_in, const ValT *__restrict__ vals_in,
                                                                KeyT *__restrict__ keys_out, ValT *__restrict__ vals_out,
                                                                uint32_t n, int shift, const uint32_t *__restrict__ hist, uint32_t nblk,
-                                                               uint32_t *__restrict__ hnext, uint32_t *__restrict__ hzero, int hbits)
+                                                               uint32_t *__restrict__ hnext, uint32_t *__restrict__ hzero, int hbits,
+                                                               size_t seg_stride)
 {
     constexpr int TILE = RS_THREADS * ITEMS;
     __shared__ KeyT s_keys[TILE];
@@ -185,6 +198,13 @@ __global__ void __launch_bounds__(RS_THREADS) rs_small_scatter(const KeyT *__res
     __shared__ uint32_t scan[8];
 
     const int tid = threadIdx.x;
+    {
+        const size_t so = (size_t)blockIdx.y * seg_stride, ho = (size_t)blockIdx.y * nblk * 256;
+        keys_in += so; vals_in += so; keys_out += so; vals_out += so;
+        hist += ho;
+        if (hnext) hnext += ho;
+        if (hzero) hzero += ho;
+    }
     const uint32_t blk = blockIdx.x, tile_base = blk * TILE;
     const uint32_t tile_n = min((uint32_t)TILE, n - tile_base);
 #pragma unroll
@@ -215,12 +235,13 @@ __global__ void __launch_bounds__(RS_THREADS) rs_small_scatter(const KeyT *__res
                                             tstart, scan, hnext, LOG2, hbits);
 }
 
+// S segments seg_stride elements apart (S = 1: the single sort)
 template <typename KeyT, int ITEMS, typename ValT, typename Book>
 inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT *kin, ValT *vin, KeyT *kout, ValT *vout,
-                   uint32_t *ws, Book &book)
+                   uint32_t *ws, Book &book, uint32_t S = 1, size_t seg_stride = 0)
 {
     const uint32_t nblk = ss_tiles(n, ITEMS);
-    const size_t slot = (size_t)nblk * 256;
+    const size_t slot = (size_t)S * nblk * 256;
     int hbits = 8;                                      // bits of a histogram counter index: digit, tile number
     while ((1u << (hbits - 8)) < nblk) hbits++;
     int p = 0;
@@ -229,10 +250,10 @@ inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT 
         uint32_t *hnext = shift + 8 < key_bits ? ws + ((p + 1) % 3) * slot : nullptr;
         uint32_t *hzero = shift + 16 < key_bits ? ws + ((p + 2) % 3) * slot : nullptr;
         if (p == 0)
-            book(false, [&] { hipLaunchKernelGGL((rs_small_hist<KeyT, ITEMS>), dim3(nblk), dim3(RS_THREADS), 0, st, kin, n, shift, h, hnext); });
+            book(false, [&] { hipLaunchKernelGGL((rs_small_hist<KeyT, ITEMS>), dim3(nblk, S), dim3(RS_THREADS), 0, st, kin, n, shift, h, hnext, seg_stride); });
         book(true, [&] {
-            hipLaunchKernelGGL((rs_small_scatter<KeyT, ITEMS, ValT>), dim3(nblk), dim3(RS_THREADS), 0, st, kin, vin, kout, vout, n, shift, h, nblk,
-                               hnext, hzero, hbits);
+            hipLaunchKernelGGL((rs_small_scatter<KeyT, ITEMS, ValT>), dim3(nblk, S), dim3(RS_THREADS), 0, st, kin, vin, kout, vout, n, shift, h, nblk,
+                               hnext, hzero, hbits, seg_stride);
         });
         KeyT *tk = kin; kin = kout; kout = tk;
         ValT *tv = vin; vin = vout; vout = tv;
@@ -243,17 +264,25 @@ inline void ss_run(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT 
 // point at the buffers holding the result (the alternates after an odd number of passes).  ws: ss_ws_words(n) words of
 // device memory, contents irrelevant.  book(scatter, launch): calls launch() once (a place to time it); scatter = false
 // for the histogram launch.
+// small_sort_batch: S such sorts at once (1 <= S <= 65535), segment s in the seg_stride elements from s * seg_stride of every
+// buffer (seg_stride >= n); *keys_io / *vals_io point at segment 0 of the result.  ws: ss_ws_words_batch(S, n) words.
+template <typename KeyT, typename ValT, typename Book>
+inline void small_sort_batch(hipStream_t st, uint32_t S, uint32_t n, size_t seg_stride, int key_bits, int shift_lo, KeyT **keys_io,
+                             ValT **vals_io, KeyT *keys_alt, ValT *vals_alt, uint32_t *ws, Book &&book)
+{
+    KeyT *kin = *keys_io; ValT *vin = *vals_io;
+    switch (ss_items(n)) {
+    case 1: ss_run<KeyT, 1, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book, S, seg_stride); break;
+    case 2: ss_run<KeyT, 2, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book, S, seg_stride); break;
+    case 4: ss_run<KeyT, 4, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book, S, seg_stride); break;
+    default: ss_run<KeyT, 8, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book, S, seg_stride); break;
+    }
+    const int passes = key_bits > shift_lo ? (key_bits - shift_lo + 7) / 8 : 0;
+    if (passes & 1) { *keys_io = keys_alt; *vals_io = vals_alt; }
+}
 template <typename KeyT, typename ValT, typename Book>
 inline void small_sort(hipStream_t st, uint32_t n, int key_bits, int shift_lo, KeyT **keys_io, ValT **vals_io, KeyT *keys_alt,
                        ValT *vals_alt, uint32_t *ws, Book &&book)
 {
-    KeyT *kin = *keys_io; ValT *vin = *vals_io;
-    switch (ss_items(n)) {
-    case 1: ss_run<KeyT, 1, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    case 2: ss_run<KeyT, 2, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    case 4: ss_run<KeyT, 4, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    default: ss_run<KeyT, 8, ValT>(st, n, key_bits, shift_lo, kin, vin, keys_alt, vals_alt, ws, book); break;
-    }
-    const int passes = key_bits > shift_lo ? (key_bits - shift_lo + 7) / 8 : 0;
-    if (passes & 1) { *keys_io = keys_alt; *vals_io = vals_alt; }
+    small_sort_batch<KeyT, ValT>(st, 1, n, 0, key_bits, shift_lo, keys_io, vals_io, keys_alt, vals_alt, ws, book);
 }
