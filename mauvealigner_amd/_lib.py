@@ -877,6 +877,18 @@ class Context:
                                                    _p(res, C.c_int64), _p(dfn, C.c_uint32), _p(iv, C.c_int64)), "mauve_translate_positions")
         return res, dfn, iv
 
+    def _range_args(self, ranges, who):
+        """ranges = (iv, col, len) arrays or None (every interval whole) -> (n_range, the four ctypes range arguments)"""
+        if ranges is None:
+            return self.coord_index_size()[1], (C.c_int64(0), None, None, None)
+        arrs = [np.ascontiguousarray(x, np.int64) for x in ranges]
+        n = len(arrs[0])
+        if not (n == len(arrs[1]) == len(arrs[2])):
+            raise ValueError("%s: the range arrays differ in length" % who)
+        if n == 0:                                               # (a pointer the library may look at: it reads none of it)
+            arrs = [np.zeros(1, np.int64)] * 3
+        return n, (C.c_int64(n),) + tuple(_p(a, C.c_int64) for a in arrs)
+
     # ---- alignment columns as a base matrix (DESIGN.md S15) ----
     def extract_select(self, keep=None, require=0, drop_empty=False, polymorphic=False, ranges=None):
         """mauve_extract_select: choose the columns (ranges = (iv, col, len) arrays as backbone()'s seg_iv / seg_col / seg_len, None = every
@@ -893,17 +905,9 @@ class Context:
                 p.keep[k] = g
         p.require, p.drop_empty, p.polymorphic = int(require), int(bool(drop_empty)), int(bool(polymorphic))
         n = C.c_int64(0)
-        if ranges is None:
-            rc = self.L.mauve_extract_select(self.h, C.byref(p), C.c_int64(0), None, None, None, C.byref(n))
-        else:
-            iv, col, ln = (np.ascontiguousarray(x, np.int64) for x in ranges)
-            if not (len(iv) == len(col) == len(ln)):
-                raise ValueError("extract: the range arrays differ in length")
-            z = np.zeros(1, np.int64)
-            rc = self.L.mauve_extract_select(self.h, C.byref(p), C.c_int64(len(iv)), _p(iv if len(iv) else z, C.c_int64), _p(col if len(iv) else z, C.c_int64),
-                                             _p(ln if len(iv) else z, C.c_int64), C.byref(n))
-        self._chk(rc, "mauve_extract_select")
-        self._ex_shape = (p.n_keep, n.value, self.coord_index_size()[1] if ranges is None else len(iv))
+        n_range, args_r = self._range_args(ranges, "extract")
+        self._chk(self.L.mauve_extract_select(self.h, C.byref(p), *args_r, C.byref(n)), "mauve_extract_select")
+        self._ex_shape = (p.n_keep, n.value, n_range)
         return n.value
 
     def extract_fetch(self, out=None, lists=True):
@@ -950,14 +954,7 @@ class Context:
             if pa.ndim != 1 or pa.shape != pb.shape:
                 raise ValueError("pair_stats: the pair arrays differ in length")
             n_pair, args_p = len(pa), (C.c_int64(len(pa)), _p(pa if len(pa) else z4, C.c_int32), _p(pb if len(pa) else z4, C.c_int32))
-        if ranges is None:
-            n_range, args_r = self.coord_index_size()[1], (C.c_int64(0), None, None, None)
-        else:
-            iv, col, ln = (np.ascontiguousarray(x, np.int64) for x in ranges)
-            if not (len(iv) == len(col) == len(ln)):
-                raise ValueError("pair_stats: the range arrays differ in length")
-            n_range = len(iv)
-            args_r = (C.c_int64(n_range), _p(iv if n_range else z8, C.c_int64), _p(col if n_range else z8, C.c_int64), _p(ln if n_range else z8, C.c_int64))
+        n_range, args_r = self._range_args(ranges, "pair_stats")
         shape = (n_range, n_pair, PAIR_STATS_WORDS) if per_range else (n_pair, PAIR_STATS_WORDS)
         if n_pair > 1024 or n_pair * (n_range if per_range else 1) > 1 << 24:
             # the library refuses these before it writes a record: nothing to allocate, and its error comes before any word about `out`

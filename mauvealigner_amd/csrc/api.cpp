@@ -233,7 +233,7 @@ void mauve_ctx_destroy(mauve_ctx *c)
                       &c->dp_score, &c->dp_cols, &c->dp_rows, &c->rp_wcnt, &c->rp_mult, &c->pf_mums, &c->co_index, &c->co_q, &c->ex_work, &c->ex_bits, &c->ex_sel, &c->ex_mat, &c->ps_work, &c->ps_out, &c->co_truth_index, &c->sc_out};
     for (DevBuf *b : bufs) b->release();
     coord_index_release(c);
-    c->pin_genomes.release(); c->pin_tail.release(); c->pin_ext.release(); c->pin_chain.release(); c->pin_mask.release(); c->pin_bb.release(); c->pin_asm.release(); c->pin_tab.release(); c->pin_cols.release(); c->pin_anch.release(); c->pin_dcols.release(); c->pin_meta.release(); c->pin_seed.release(); c->pin_dp_in.release(); c->shard_pin.release(); c->pin_coord.release(); c->pin_ex.release(); c->pin_ps.release(); c->pin_sc.release();
+    c->pin_genomes.release(); c->pin_tail.release(); c->pin_ext.release(); c->pin_chain.release(); c->pin_mask.release(); c->pin_bb.release(); c->pin_asm.release(); c->pin_tab.release(); c->pin_cols.release(); c->pin_anch.release(); c->pin_dcols.release(); c->pin_meta.release(); c->pin_seed.release(); c->pin_dp_in.release(); c->shard_pin.release(); c->pin_stage.release();
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);

@@ -11,6 +11,7 @@
 #include "host_chain.hpp"
 #include <chrono>
 #include <algorithm>
+#include <cstring>
 
 #include "../../include/mauve_hip.h"
 
@@ -23,6 +24,8 @@
             return MAUVE_ERR_HIP;                                                                 \
         }                                                                                         \
     } while (0)
+
+inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }       // the next multiple of 64: parts of a work area start on one
 
 struct DevBuf {
     void *p = nullptr;
@@ -267,12 +270,14 @@ struct mauve_ctx {
     // genomes nor res_cols once built, so later passes leave it alone; replaced by the next mauve_coord_index*, freed with the context
     struct CoordIndex { bool valid = false; int N = 0; int64_t n_iv = 0, n_cols = 0; uint64_t genome_gen = 0; struct ::CoordDev *dev = nullptr; } co;     // dev: the kernels' view of the index, owned by coord_dev.hip (coord_index_release)
     DevBuf co_index, co_q;               // the index; one chunk of queries and their answers
-    PinnedBuf pin_coord;                 // ... on their way from / to pageable caller arrays, and the error flag
+    // the staging of the stages that query the index (S14 to S17): queries, ranges and pairs on their way in, the error flag and counts coming
+    // back, pageable results on their way out (copy_to_caller).  The stages do not run concurrently on a context and keep nothing here between
+    // calls; the one thing that outlives a call, the selection of S15, is device memory (ex_sel below)
+    PinnedBuf pin_stage;
     // scoring against a correct alignment (score_dev.hip): a second index, of the correct alignment, read-only beside the one in
     // force; replaced by the next mauve_score_truth, untouched by mauve_coord_index*, alignments and genome uploads
     CoordIndex co_truth;
     DevBuf co_truth_index, sc_out;       // that index; the error flag and the records
-    PinnedBuf pin_sc;                    // the error flag coming back, staging of pageable records
     // column extraction (extract_dev.hip): the selection a fetch turns into letters -- the selected columns as (interval, column)
     // in ex_sel, with the request; it belongs to the index and the genomes it was made on (an index call clears `valid`, genome_gen tells an upload)
     struct ExtractSel {
@@ -280,12 +285,9 @@ struct mauve_ctx {
         int64_t n_sel = 0, n_range = 0;
         int n_keep = 0; int32_t keep[MAUVE_MAX_SEQ] = {0};
     } ex;
-    DevBuf ex_work, ex_bits, ex_sel, ex_mat;   // ranges and their scan; flag words and their scan; sel_iv | sel_col | range_off; the matrix (padded pitch)
-    PinnedBuf pin_ex;                    // ranges on their way in, counts and the error flag coming back, staging of pageable outputs
+    DevBuf ex_work, ex_bits, ex_sel, ex_mat;   // the flag word, ranges and their scan; selection words and their scan; sel_iv | sel_col | range_off; the matrix (padded pitch)
     // pairwise column statistics (pairstat_dev.hip): no state between calls, work buffers apart from the selection's
-    DevBuf ps_work, ps_out;              // flag words, ranges, their units' scan, the pair lists; the records
-    PinnedBuf pin_ps;                    // ranges and pairs on their way in, the unit count and the error flag coming back; pageable records are
-                                         // staged through pin_ex (ex_copy_out), where the extract stage keeps nothing between calls
+    DevBuf ps_work, ps_out;              // the flag word, ranges, their units' scan, the pair lists; the records
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them
     DevBuf rec_genomes, rec_seg;         // recursive anchoring: gap sub-sequences + segment table
@@ -536,6 +538,22 @@ bool fetch_compact_direct(mauve_ctx *c, int col_bytes, int32_t *mum_length, int3
 int prefetch_tables_enqueue(mauve_ctx *c, int N, int64_t na, const int32_t *alen, const int32_t *ast, const int32_t *alcb);
 bool fetch_tables_direct(mauve_ctx *c, int64_t *mum_length, int64_t *mum_start, int64_t *anchor_length, int64_t *anchor_start, int64_t *anchor_lcb, int *rc_out);
 bool host_pointer_is_pinned(const void *p);
+// device -> caller on the context's stream: a page-locked destination directly (queued: the caller synchronises), a pageable one through `pin`
+// in pieces of 64 MiB, each waited for
+inline int copy_to_caller(mauve_ctx *c, PinnedBuf &pin, void *dst, const void *src, size_t bytes)
+{
+    if (!bytes) return MAUVE_OK;
+    if (host_pointer_is_pinned(dst)) { HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); return MAUVE_OK; }
+    const size_t piece = (size_t)64 << 20;
+    HIPCHK(c, pin.ensure(std::min(bytes, piece)));
+    for (size_t o = 0; o < bytes; o += piece) {
+        const size_t n = std::min(piece, bytes - o);
+        HIPCHK(c, hipMemcpyAsync(pin.p, static_cast<const char *>(src) + o, n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        memcpy(static_cast<char *>(dst) + o, pin.p, n);
+    }
+    return MAUVE_OK;
+}
 int host_genomes(mauve_ctx *c);
 int seed_matches_to_host(mauve_ctx *ctx);
 int dp_fetch_picked(mauve_ctx *ctx, int64_t n_pick, const int64_t *pick, const int64_t *col_off, uint32_t *out, int64_t *out_off);

@@ -12,7 +12,9 @@
 //                  fewer residues than lie between two samples, so the bracket is nearly always one or two blocks wide)
 //   coord_build    one wave per block: seven coalesced 256-byte loads, a ballot per genome and word, lane g keeps genome g's words
 //   coord_finish   ranks from the scanned block counts (dev_scan.hpp), the samples;  coord_iv_rows  the interval rows
-//   coord_positions / coord_select   the queries: a thread per (query, genome) resp. per query; every index they form is checked first
+//   coord_positions / coord_select   the queries: a thread per (query, genome) resp. per query; every index they form is checked first.
+//                  Column -> position is co_column / co_residue, position -> column co_find (coord_index.hpp, shared with S15 to S17);
+//                  a thread that finds something wrong sets a bit of the flag word, which co_flag_read turns into the call's result
 #include "common.hpp"
 #include "coord_index.hpp"
 #include "dev_scan.hpp"
@@ -113,15 +115,10 @@ __global__ void __launch_bounds__(256) coord_positions(CoordDev D, int64_t n, co
     }
     int64_t pos = 0; bool present = false;
     if (live && i >= 0) {
-        const CoordIv I = D.ivt[(size_t)i * D.N + g];
-        if (I.left) {
-            const int64_t b = x / CO_BLOCK;
-            const CoordRec r = D.rec[(size_t)b * D.N + g];
-            const int64_t k = co_rank(r, (int)(x - b * CO_BLOCK), &present) - I.base;
-            if (present || nearest) {
-                const int64_t o = present ? k : (k > 0 ? k - 1 : 0);        // gapped here: the residue before the column, else the first one
-                pos = (I.col0_rev & 1) ? -(I.right - o) : I.left + o;
-            }
+        CoordIv I; int64_t k;
+        if (co_column(D, i, x, g, &I, &present, &k) && (present || nearest)) {
+            const int64_t p = co_residue(I, present ? k : (k > 0 ? k - 1 : 0));   // gapped here: the residue before the column, else the first one
+            pos = (I.col0_rev & 1) ? -p : p;
         }
     }
     const uint64_t B = __ballot(present);
@@ -145,8 +142,6 @@ __global__ void __launch_bounds__(256) coord_select(CoordDev D, int64_t n, const
     else { iv_out[q] = -1; col_out[q] = -1; }
     if (bad) atomicOr(flag, bad);
 }
-
-inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 // the kernels turn column offsets into block indices: they ascend from 0 (checked before anything is sized by them)
 int coord_check_offsets(mauve_ctx *c, const char *who, int64_t n_iv, const int64_t *col_off)
@@ -247,7 +242,7 @@ int coord_build_index(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, D
 enum { CO_COLUMNS = 0, CO_SELECT = 1, CO_TRANSLATE = 2 };
 
 // One batch of queries: in chunks through ctx->co_q (inputs | outputs), page-locked caller arrays copied directly, pageable ones through
-// ctx->pin_coord.  a / b / s: the 64-bit and 32-bit query arrays of the kind; o_pos [n*N], o_def [n], o_iv [n], o_col [n]: outputs, any may be NULL.
+// ctx->pin_stage.  a / b / s: the 64-bit and 32-bit query arrays of the kind; o_pos [n*N], o_def [n], o_iv [n], o_col [n]: outputs, any may be NULL.
 int coord_run(mauve_ctx *c, int kind, int64_t n, const int64_t *a, const int64_t *b, const int32_t *s, int nearest, int64_t *o_pos, uint32_t *o_def, int64_t *o_iv,
               int64_t *o_col)
 {
@@ -270,8 +265,10 @@ int coord_run(mauve_ctx *c, int kind, int64_t n, const int64_t *a, const int64_t
     const bool in_direct = host_pointer_is_pinned(a) && host_pointer_is_pinned(kind == CO_COLUMNS ? (const void *)b : (const void *)s);
     const bool out_direct = (!o_pos || host_pointer_is_pinned(o_pos)) && (!o_def || host_pointer_is_pinned(o_def)) && (!o_iv || host_pointer_is_pinned(o_iv)) &&
                             (!o_col || host_pointer_is_pinned(o_col));
-    HIPCHK(c, c->pin_coord.ensure(in_direct && out_direct ? 64 : r_end));
-    char *hb = c->pin_coord.as<char>();
+    HIPCHK(c, c->pin_stage.ensure(in_direct && out_direct ? 64 : r_end));
+    char *hb = c->pin_stage.as<char>();
+    // the outputs: the caller's array (NULL: not wanted), its place in a chunk, bytes per query
+    const struct { void *dst; size_t off, per; } outs[4] = {{o_pos, r_pos, (size_t)N * 8}, {o_def, r_def, 4}, {o_iv, r_iv, 8}, {o_col, r_col, 8}};
     HIPCHK(c, hipMemsetAsync(qd, 0, 64, c->stream));          // the error flag
     uint32_t *flag = reinterpret_cast<uint32_t *>(qd);
     for (int64_t q0 = 0; q0 < n; q0 += (int64_t)m) {
@@ -298,31 +295,13 @@ int coord_run(mauve_ctx *c, int kind, int64_t n, const int64_t *a, const int64_t
         else
             hipLaunchKernelGGL(coord_select, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, c->stream, D, (int64_t)nq, d_s, d_a, d_iv, d_col, flag);
         HIPCHK(c, hipGetLastError());
-        if (out_direct) {
-            if (o_pos) HIPCHK(c, hipMemcpyAsync(o_pos + (size_t)q0 * N, qd + r_pos, nq * N * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o_def) HIPCHK(c, hipMemcpyAsync(o_def + q0, qd + r_def, nq * 4, hipMemcpyDeviceToHost, c->stream));
-            if (o_iv) HIPCHK(c, hipMemcpyAsync(o_iv + q0, qd + r_iv, nq * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o_col) HIPCHK(c, hipMemcpyAsync(o_col + q0, qd + r_col, nq * 8, hipMemcpyDeviceToHost, c->stream));
-        } else {
-            if (o_pos) HIPCHK(c, hipMemcpyAsync(hb + r_pos, qd + r_pos, nq * N * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o_def) HIPCHK(c, hipMemcpyAsync(hb + r_def, qd + r_def, nq * 4, hipMemcpyDeviceToHost, c->stream));
-            if (o_iv) HIPCHK(c, hipMemcpyAsync(hb + r_iv, qd + r_iv, nq * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o_col) HIPCHK(c, hipMemcpyAsync(hb + r_col, qd + r_col, nq * 8, hipMemcpyDeviceToHost, c->stream));
-        }
+        for (const auto &o : outs)
+            if (o.dst) HIPCHK(c, hipMemcpyAsync(out_direct ? static_cast<char *>(o.dst) + (size_t)q0 * o.per : hb + o.off, qd + o.off, nq * o.per, hipMemcpyDeviceToHost, c->stream));
         if (!in_direct || !out_direct) HIPCHK(c, hipStreamSynchronize(c->stream));     // the staging is reused by the next chunk
-        if (!out_direct) {
-            if (o_pos) memcpy(o_pos + (size_t)q0 * N, hb + r_pos, nq * N * 8);
-            if (o_def) memcpy(o_def + q0, hb + r_def, nq * 4);
-            if (o_iv) memcpy(o_iv + q0, hb + r_iv, nq * 8);
-            if (o_col) memcpy(o_col + q0, hb + r_col, nq * 8);
-        }
+        if (!out_direct)
+            for (const auto &o : outs) if (o.dst) memcpy(static_cast<char *>(o.dst) + (size_t)q0 * o.per, hb + o.off, nq * o.per);
     }
-    HIPCHK(c, hipMemcpyAsync(hb, qd, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint32_t f = *reinterpret_cast<const uint32_t *>(hb);
-    if (f & CO_BAD_ARG) { c->err = "coord query: a query lies outside the alignment (interval id, column, genome index or a position below 1)"; return MAUVE_ERR_ARG; }
-    if (f & CO_BAD_INDEX) { c->err = "coord query: the index is inconsistent with its interval table"; return MAUVE_ERR_STATE; }
-    return MAUVE_OK;
+    return co_flag_read(c, flag, "coord query", "a query lies outside the alignment (interval id, column, genome index or a position below 1)");
 }
 
 }  // namespace

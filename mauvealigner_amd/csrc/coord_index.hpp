@@ -1,7 +1,10 @@
 // coord_index.hpp -- the coordinate index as its kernels see it: shared by coord_dev.hip, which builds and queries it,
 // extract_dev.hip and pairstat_dev.hip, which read ranks from it, and score_dev.hip, which looks bases up in it (S17).
+// The one column -> position rule (co_column, co_residue), the one position -> column rule (co_find), and the one error flag of the four
+// stages: a word with the bits CO_BAD_ARG and CO_BAD_INDEX, set with atomicOr by a thread that found something, read by co_flag_result.
 #pragma once
 #include "common.hpp"
+#include <string>
 
 constexpr int CO_WORDS = 7;                       // 64-column words per block record (with the rank: 64 bytes)
 constexpr int CO_BLOCK = CO_WORDS * 64;           // columns per block
@@ -39,6 +42,27 @@ __device__ __forceinline__ int64_t co_rank(const CoordRec &r, int off, bool *pre
     *present = p;
     return n;
 }
+
+// rule 1, first half: column x (whole array) of interval i in genome g.  false: the genome has no row in the interval (I.left == 0); else
+// *present: the genome's bit of that column, *k: residues of the row in front of the column (rank - base).  The caller has checked i and x.
+// The first form takes the column as block b and offset in it, for a caller that asks about many genomes at one column.
+__device__ __forceinline__ bool co_column(const CoordDev &D, int64_t i, int64_t b, int off, int g, CoordIv *I, bool *present, int64_t *k)
+{
+    *I = D.ivt[(size_t)i * D.N + g];
+    *present = false; *k = 0;
+    if (!I->left) return false;
+    const CoordRec r = D.rec[(size_t)b * D.N + g];
+    *k = co_rank(r, off, present) - I->base;
+    return true;
+}
+__device__ __forceinline__ bool co_column(const CoordDev &D, int64_t i, int64_t x, int g, CoordIv *I, bool *present, int64_t *k)
+{
+    const int64_t b = x / CO_BLOCK;
+    return co_column(D, i, b, (int)(x - b * CO_BLOCK), g, I, present, k);
+}
+
+// rule 1, second half: the position of residue k of an interval row (unsigned; the caller checks k and the result as its stage requires)
+__device__ __forceinline__ int64_t co_residue(const CoordIv &I, int64_t k) { return (I.col0_rev & 1) ? I.right - k : I.left + k; }
 
 // position of the k-th (0-based) set bit of x; x holds more than k
 __device__ __forceinline__ int co_select64(uint64_t x, int k)
@@ -79,4 +103,22 @@ __device__ __forceinline__ uint32_t co_find(const CoordDev &D, int64_t g, int64_
     if (wk < 0) { *bad = CO_BAD_INDEX; return 2; }
     *iv = i; *x = lo * CO_BLOCK + wk * 64 + co_select64(ww, (int)rem); *col0 = I.col0_rev >> 1;
     return 0;
+}
+
+// the flag word a stage read back -> the result of its call.  outside: the stage's sentence for CO_BAD_ARG (nullptr: the stage takes nothing
+// from the caller that a kernel checks, any bit speaks of an index); which: whose index CO_BAD_INDEX speaks of
+inline int co_flag_result(mauve_ctx *c, uint32_t f, const char *who, const char *outside, const char *which = "the index")
+{
+    if (outside && (f & CO_BAD_ARG)) { c->err = std::string(who) + ": " + outside; return MAUVE_ERR_ARG; }
+    if (f & (outside ? CO_BAD_INDEX : ~0u)) { c->err = std::string(who) + ": " + which + " is inconsistent with its interval table"; return MAUVE_ERR_STATE; }
+    return MAUVE_OK;
+}
+
+// the flag word fetched from the device through the staging (one synchronise) and judged
+inline int co_flag_read(mauve_ctx *c, const uint32_t *d_flag, const char *who, const char *outside, const char *which = "the index")
+{
+    HIPCHK(c, c->pin_stage.ensure(64));
+    HIPCHK(c, hipMemcpyAsync(c->pin_stage.p, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return co_flag_result(c, *c->pin_stage.as<uint32_t>(), who, outside, which);
 }

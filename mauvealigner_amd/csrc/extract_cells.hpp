@@ -1,9 +1,11 @@
 // extract_cells.hpp -- what the stages that read letters through the coordinate index share: extract_dev.hip and
-// pairstat_dev.hip (S16).  The cell rule, the resident genomes as a kernel argument, the range check with its flag words, the state check
-// and the copy-out.  Internal linkage: every stage compiles its own copy.
+// pairstat_dev.hip (S16).  The cell rule, the resident genomes as a kernel argument, the state check, and the range front end (ex_front): the
+// caller's ranges checked against the index on the device and a count per range scanned, up to the stage's first own kernel.  Errors go
+// through the flag word of coord_index.hpp.  Internal linkage: every stage compiles its own copy.
 #pragma once
 #include "common.hpp"
 #include "coord_index.hpp"
+#include "dev_scan.hpp"
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -12,12 +14,9 @@ namespace {
 
 // the resident genomes: 2-bit codes and the ambiguity bitmap (inv == nullptr: none)
 struct ExGenomes { const uint64_t *words, *inv; uint64_t word_off[MAUVE_MAX_SEQ], mask_off[MAUVE_MAX_SEQ]; int64_t len[MAUVE_MAX_SEQ]; };
-struct ExLen { const int64_t *v; __device__ int64_t value(uint32_t i) const { return v[i]; } };
 
-inline size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
-
-// flag words: [0] a range outside the alignment or an interval end beyond its genome (MAUVE_ERR_ARG), [1] an index that contradicts itself
-__device__ __forceinline__ void ex_report(uint32_t *flag, uint32_t bad) { if (bad & CO_BAD_ARG) flag[0] = 1u; if (bad & CO_BAD_INDEX) flag[1] = 1u; }
+// CO_BAD_ARG in these stages
+constexpr const char *EX_OUTSIDE = "a range lies outside the alignment (interval id, column, length) or an interval of the index ends beyond its resident genome";
 
 __global__ void __launch_bounds__(256) ex_ranges(CoordDev D, ExGenomes G, int64_t R, const int64_t *__restrict__ r_iv, const int64_t *__restrict__ r_col,
                                                  const int64_t *__restrict__ r_len, int64_t *__restrict__ gstart, int64_t *__restrict__ clen, uint32_t *__restrict__ flag)
@@ -38,22 +37,17 @@ __global__ void __launch_bounds__(256) ex_ranges(CoordDev D, ExGenomes G, int64_
         const CoordIv I = D.ivt[t];
         if (I.left && I.right > G.len[t % D.N]) bad |= CO_BAD_ARG;
     }
-    if (bad) ex_report(flag, bad);
+    if (bad) atomicOr(flag, bad);
 }
 
 // the letter of column x (whole array) of interval i in genome g (S15 cell rule); *code: 0..3 for a letter of ACGT, else -1
 __device__ __forceinline__ char ex_cell(const CoordDev &D, const ExGenomes &G, int64_t i, int64_t x, int g, int *code, uint32_t *bad)
 {
     *code = -1;
-    const CoordIv I = D.ivt[(size_t)i * D.N + g];
-    if (!I.left) return '-';
-    const int64_t b = x / CO_BLOCK;
-    const CoordRec r = D.rec[(size_t)b * D.N + g];
-    bool present;
-    const int64_t k = co_rank(r, (int)(x - b * CO_BLOCK), &present) - I.base;
-    if (!present) return '-';
+    CoordIv I; bool present; int64_t k;
+    if (!co_column(D, i, x, g, &I, &present, &k) || !present) return '-';
     const bool rev = I.col0_rev & 1;
-    const int64_t p = rev ? I.right - k : I.left + k;
+    const int64_t p = co_residue(I, k);
     if (k < 0 || p < 1 || p > G.len[g]) { *bad |= CO_BAD_INDEX; return '-'; }
     const int64_t q = p - 1;
     if (G.inv && (G.inv[G.mask_off[g] + (uint64_t)(q >> 6)] >> (q & 63) & 1)) return 'N';
@@ -84,13 +78,6 @@ ExGenomes ex_genomes(const mauve_ctx *c)
     return G;
 }
 
-int ex_flag_result(mauve_ctx *c, const uint32_t *f, const char *who)
-{
-    if (f[0]) { c->err = std::string(who) + ": a range lies outside the alignment (interval id, column, length) or an interval of the index ends beyond its resident genome"; return MAUVE_ERR_ARG; }
-    if (f[1]) { c->err = std::string(who) + ": the index is inconsistent with its interval table"; return MAUVE_ERR_STATE; }
-    return MAUVE_OK;
-}
-
 // the index and the genomes a selection or a fetch works on
 int ex_check_state(mauve_ctx *c, const char *who)
 {
@@ -101,20 +88,64 @@ int ex_check_state(mauve_ctx *c, const char *who)
     return MAUVE_OK;
 }
 
-// device -> caller: page-locked destinations directly, pageable ones through ctx->pin_ex in pieces
-int ex_copy_out(mauve_ctx *c, void *dst, const void *src, size_t bytes)
+// what the range front end hands to its stage
+struct ExFront {
+    int64_t R;                                    // ranges (the caller's, or every interval whole)
+    ExGenomes G;
+    const int64_t *d_iv;                          // the ranges' intervals (nullptr: range r is interval r)
+    int64_t *gstart, *clen, *off;                 // first column (whole array) and length of every range; the scan of the stage's count [R + 1]
+    int64_t total;                                // off[R]
+    char *tail;                                   // the stage's bytes behind the ranges
+    uint32_t *flag;                               // the error flag, first word of the work area
+};
+
+// The front end of a stage that works on column ranges: the range arguments checked, the ranges and `tail_bytes` of the stage's own (`tail`)
+// packed and uploaded into `work`, ex_ranges, the scan of F::of(gstart, clen) over the ranges, the flag and the total read back and the flag
+// judged.  One synchronise.  It leaves ctx->pin_stage at least 256 bytes long.
+template <class F>
+int ex_front(mauve_ctx *c, const char *who, DevBuf &work, int64_t n_range, const int64_t *range_iv, const int64_t *range_col, const int64_t *range_len,
+             const void *tail, size_t tail_bytes, ExFront *out)
 {
-    if (!bytes) return MAUVE_OK;
-    if (host_pointer_is_pinned(dst)) { HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); return MAUVE_OK; }
-    const size_t piece = (size_t)64 << 20;
-    HIPCHK(c, c->pin_ex.ensure(std::min(bytes, piece)));
-    for (size_t o = 0; o < bytes; o += piece) {
-        const size_t n = std::min(piece, bytes - o);
-        HIPCHK(c, hipMemcpyAsync(c->pin_ex.p, static_cast<const char *>(src) + o, n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        memcpy(static_cast<char *>(dst) + o, c->pin_ex.p, n);
-    }
-    return MAUVE_OK;
+    const int64_t R = range_iv ? n_range : c->co.n_iv;
+    if (R < 0 || (range_iv && R && (!range_col || !range_len))) { c->err = std::string(who) + ": missing range arrays"; return MAUVE_ERR_ARG; }
+    if (R >= ((int64_t)1 << 31)) { c->err = std::string(who) + ": too many ranges"; return MAUVE_ERR_LIMIT; }
+    const CoordDev &D = *c->co.dev;
+    out->R = R; out->G = ex_genomes(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    // work area: flag | the caller's ranges | the tail | first column and length of every range | the scan | its tile sums
+    const size_t nR = (size_t)R, n_ivg = (size_t)(D.n_iv * D.N);
+    const uint32_t tilesR = (uint32_t)((nR + devscan::TILE - 1) / devscan::TILE);
+    const size_t w_iv = 64, w_col = w_iv + up64(nR * 8), w_len = w_col + up64(nR * 8), w_tail = w_len + up64(nR * 8), w_gs = w_tail + up64(tail_bytes),
+                 w_cl = w_gs + up64(nR * 8), w_off = w_cl + up64(nR * 8), w_bs = w_off + up64((nR + 1) * 8), w_total = w_bs + up64((size_t)tilesR * 8 + 8);
+    HIPCHK(c, work.ensure(w_total));
+    HIPCHK(c, c->pin_stage.ensure(std::max<size_t>(w_gs, 256)));
+    char *wk = work.as<char>(), *hb = c->pin_stage.as<char>();
+    HIPCHK(c, hipMemsetAsync(wk, 0, 64, c->stream));
+    const bool own = range_iv && R;
+    if (own) { memcpy(hb + w_iv, range_iv, nR * 8); memcpy(hb + w_col, range_col, nR * 8); memcpy(hb + w_len, range_len, nR * 8); }
+    if (tail_bytes) memcpy(hb + w_tail, tail, tail_bytes);
+    const size_t up0 = own ? w_iv : w_tail;
+    if (w_gs > up0) HIPCHK(c, hipMemcpyAsync(wk + up0, hb + up0, w_gs - up0, hipMemcpyHostToDevice, c->stream));
+    out->flag = reinterpret_cast<uint32_t *>(wk);
+    out->d_iv = range_iv ? reinterpret_cast<const int64_t *>(wk + w_iv) : nullptr;
+    out->tail = wk + w_tail;
+    out->gstart = reinterpret_cast<int64_t *>(wk + w_gs); out->clen = reinterpret_cast<int64_t *>(wk + w_cl); out->off = reinterpret_cast<int64_t *>(wk + w_off);
+    int64_t *bsum = reinterpret_cast<int64_t *>(wk + w_bs);
+    const size_t n_chk = std::max(nR, n_ivg);
+    if (n_chk)
+        hipLaunchKernelGGL(ex_ranges, dim3((uint32_t)((n_chk + 255) / 256)), dim3(256), 0, c->stream, D, out->G, R, out->d_iv, reinterpret_cast<const int64_t *>(wk + w_col),
+                           reinterpret_cast<const int64_t *>(wk + w_len), out->gstart, out->clen, out->flag);
+    if (R) {
+        const F in = F::of(out->gstart, out->clen);
+        hipLaunchKernelGGL((devscan::vscan_partial<int64_t, F>), dim3(tilesR), dim3(256), 0, c->stream, in, (uint32_t)R, bsum);
+        hipLaunchKernelGGL((devscan::vscan_write<int64_t, F>), dim3(tilesR), dim3(256), 0, c->stream, in, (uint32_t)R, bsum, out->off, (int64_t *)nullptr);
+    } else HIPCHK(c, hipMemsetAsync(out->off, 0, 8, c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hb, wk, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb + 64, out->off + R, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->total = *reinterpret_cast<const int64_t *>(hb + 64);
+    return co_flag_result(c, *reinterpret_cast<const uint32_t *>(hb), who, EX_OUTSIDE);
 }
 
 }  // namespace

@@ -9,10 +9,9 @@
 //   ex_compact  the scanned word counts give every selected column its slot: (interval, column) lists, and range_off from the same scan
 //   ex_fill     a thread per 4 consecutive selected columns of one row: rank from the block record, the base from the packed genome,
 //               one dword store; rows have a pitch of their own (a multiple of 16 bytes), the copy-out is 2-D
-// Every index formed from caller data is checked before it is used; the kernels report through flag words written with plain stores.
+// Every index formed from caller data is checked before it is used; the kernels report through the flag word of coord_index.hpp.  The
+// selection (ex_sel, device memory) is what the stage keeps between a select and its fetches; the staging holds nothing between calls.
 #include "common.hpp"
-#include "coord_index.hpp"
-#include "dev_scan.hpp"
 #include "extract_cells.hpp"
 #include <algorithm>
 #include <cstring>
@@ -22,6 +21,7 @@ namespace {
 // the request as the kernels see it
 struct ExReq { int n_keep; int32_t keep[MAUVE_MAX_SEQ]; uint32_t require, keepmask; int drop_empty, polymorphic; };
 
+struct ExLen { const int64_t *v; static ExLen of(const int64_t *, const int64_t *cl) { return ExLen{cl}; } __device__ int64_t value(uint32_t i) const { return v[i]; } };
 struct ExPop { const uint64_t *w; __device__ int64_t value(uint32_t i) const { return __popcll(w[i]); } };
 
 __global__ void __launch_bounds__(256) ex_flags(CoordDev D, ExGenomes G, ExReq Q, int64_t R, int64_t n_cand, const int64_t *__restrict__ r_iv, const int64_t *__restrict__ gstart,
@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(256) ex_flags(CoordDev D, ExGenomes G, ExReq Q
     }
     const uint64_t B = __ballot(sel);
     if ((threadIdx.x & 63) == 0 && (t >> 6) < n_words) words[t >> 6] = B;
-    if (bad) ex_report(flag, bad);
+    if (bad) atomicOr(flag, bad);
 }
 
 __global__ void __launch_bounds__(256) ex_compact(CoordDev D, int64_t R, int64_t n_cand, const int64_t *__restrict__ r_iv, const int64_t *__restrict__ gstart,
@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(256) ex_fill(CoordDev D, ExGenomes G, ExReq Q,
         out |= (uint32_t)(uint8_t)ch << (8 * k);
     }
     mat[(size_t)blockIdx.y * (size_t)pitch4 + (size_t)t] = out;
-    if (bad) ex_report(flag, bad);
+    if (bad) atomicOr(flag, bad);
 }
 
 ExReq ex_request(const mauve_ctx::ExtractSel &S, uint32_t require, int drop_empty, int polymorphic)
@@ -128,48 +128,17 @@ int mauve_extract_select(mauve_ctx *c, const mauve_extract_params *p, int64_t n_
         keepmask |= 1u << g;
     }
     if (N < 32 && (p->require >> N)) { c->err = "extract_select: a require bit at or above nseq"; return MAUVE_ERR_ARG; }
-    const int64_t R = range_iv ? n_range : c->co.n_iv;
-    if (R < 0 || (range_iv && R && (!range_col || !range_len))) { c->err = "extract_select: missing range arrays"; return MAUVE_ERR_ARG; }
-    if (R >= ((int64_t)1 << 31)) { c->err = "extract_select: too many ranges"; return MAUVE_ERR_LIMIT; }
-    S.n_keep = p->n_keep; S.n_range = R; S.n_sel = 0;
+    S.n_keep = p->n_keep; S.n_sel = 0;
     for (int k = 0; k < p->n_keep; k++) S.keep[k] = p->keep[k];
-    const CoordDev &D = *c->co.dev;
-    const ExGenomes G = ex_genomes(c);
-    const ExReq Q = ex_request(S, p->require, p->drop_empty != 0, p->polymorphic != 0);
-    HIPCHK(c, hipSetDevice(c->device));
-    // work area: flag words | the caller's ranges | first column and length of every range | the scan of the lengths | its tile sums
-    const size_t nR = (size_t)R, n_ivg = (size_t)(D.n_iv * D.N);
-    const uint32_t tilesR = (uint32_t)((nR + devscan::TILE - 1) / devscan::TILE);
-    const size_t w_iv = 64, w_col = w_iv + up64(nR * 8), w_len = w_col + up64(nR * 8), w_gs = w_len + up64(nR * 8), w_cl = w_gs + up64(nR * 8), w_co = w_cl + up64(nR * 8),
-                 w_bs = w_co + up64((nR + 1) * 8), w_total = w_bs + up64((size_t)tilesR * 8 + 8);
-    HIPCHK(c, c->ex_work.ensure(w_total));
-    HIPCHK(c, c->pin_ex.ensure(std::max<size_t>(w_gs, 256)));
-    HIPCHK(c, c->ex_sel.ensure(up64((nR + 1) * 8)));
-    char *wk = c->ex_work.as<char>(), *hb = c->pin_ex.as<char>();
-    uint32_t *flag = reinterpret_cast<uint32_t *>(wk);
-    HIPCHK(c, hipMemsetAsync(wk, 0, 64, c->stream));
-    if (range_iv && R) {
-        memcpy(hb + w_iv, range_iv, nR * 8); memcpy(hb + w_col, range_col, nR * 8); memcpy(hb + w_len, range_len, nR * 8);
-        HIPCHK(c, hipMemcpyAsync(wk + w_iv, hb + w_iv, w_gs - w_iv, hipMemcpyHostToDevice, c->stream));
-    }
-    const int64_t *d_iv = range_iv ? reinterpret_cast<const int64_t *>(wk + w_iv) : nullptr, *d_col = reinterpret_cast<const int64_t *>(wk + w_col),
-                  *d_len = reinterpret_cast<const int64_t *>(wk + w_len);
-    int64_t *gstart = reinterpret_cast<int64_t *>(wk + w_gs), *clen = reinterpret_cast<int64_t *>(wk + w_cl), *cand_off = reinterpret_cast<int64_t *>(wk + w_co),
-            *bsum = reinterpret_cast<int64_t *>(wk + w_bs);
-    const size_t n_chk = std::max(nR, n_ivg);
-    if (n_chk) hipLaunchKernelGGL(ex_ranges, dim3((uint32_t)((n_chk + 255) / 256)), dim3(256), 0, c->stream, D, G, R, d_iv, d_col, d_len, gstart, clen, flag);
-    if (R) {
-        const ExLen in{clen};
-        hipLaunchKernelGGL((devscan::vscan_partial<int64_t, ExLen>), dim3(tilesR), dim3(256), 0, c->stream, in, (uint32_t)R, bsum);
-        hipLaunchKernelGGL((devscan::vscan_write<int64_t, ExLen>), dim3(tilesR), dim3(256), 0, c->stream, in, (uint32_t)R, bsum, cand_off, (int64_t *)nullptr);
-    } else HIPCHK(c, hipMemsetAsync(cand_off, 0, 8, c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hb, wk, 64, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hb + 64, cand_off + R, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (const int rf = ex_flag_result(c, reinterpret_cast<const uint32_t *>(hb), "extract_select")) return rf;
-    const int64_t n_cand = *reinterpret_cast<const int64_t *>(hb + 64);
+    ExFront F;                                               // the candidates are the columns of the ranges one after another: the scan of the lengths
+    if (const int rf = ex_front<ExLen>(c, "extract_select", c->ex_work, n_range, range_iv, range_col, range_len, nullptr, 0, &F)) return rf;
+    const int64_t R = S.n_range = F.R, n_cand = F.total, *d_iv = F.d_iv, *gstart = F.gstart, *cand_off = F.off;
     if (n_cand >= ((int64_t)1 << 34)) { c->err = "extract_select: the ranges hold 2^34 columns or more"; return MAUVE_ERR_LIMIT; }
+    const CoordDev &D = *c->co.dev;
+    const ExReq Q = ex_request(S, p->require, p->drop_empty != 0, p->polymorphic != 0);
+    const size_t nR = (size_t)R;
+    char *hb = c->pin_stage.as<char>();
+    HIPCHK(c, c->ex_sel.ensure(up64((nR + 1) * 8)));
     int64_t *range_off = c->ex_sel.as<int64_t>();
     int64_t ns = 0;
     if (n_cand == 0) HIPCHK(c, hipMemsetAsync(range_off, 0, (nR + 1) * 8, c->stream));
@@ -183,7 +152,7 @@ int mauve_extract_select(mauve_ctx *c, const mauve_extract_params *p, int64_t n_
         uint64_t *words = reinterpret_cast<uint64_t *>(bb);
         int64_t *pre = reinterpret_cast<int64_t *>(bb + b_pre), *bsw = reinterpret_cast<int64_t *>(bb + b_bs);
         const uint32_t blocks = (uint32_t)((n_cand + 255) / 256);
-        hipLaunchKernelGGL(ex_flags, dim3(blocks), dim3(256), 0, c->stream, D, G, Q, R, n_cand, d_iv, gstart, cand_off, words, n_words, flag);
+        hipLaunchKernelGGL(ex_flags, dim3(blocks), dim3(256), 0, c->stream, D, F.G, Q, R, n_cand, d_iv, gstart, cand_off, words, n_words, F.flag);
         const ExPop in{words};
         hipLaunchKernelGGL((devscan::vscan_partial<int64_t, ExPop>), dim3(tilesW), dim3(256), 0, c->stream, in, (uint32_t)n_words, bsw);
         hipLaunchKernelGGL((devscan::vscan_write<int64_t, ExPop>), dim3(tilesW), dim3(256), 0, c->stream, in, (uint32_t)n_words, bsw, pre, (int64_t *)nullptr);
@@ -198,9 +167,7 @@ int mauve_extract_select(mauve_ctx *c, const mauve_extract_params *p, int64_t n_
         hipLaunchKernelGGL(ex_compact, dim3((uint32_t)((std::max<int64_t>(n_cand, R + 1) + 255) / 256)), dim3(256), 0, c->stream, D, R, n_cand, d_iv, gstart, cand_off, words, pre, n_words,
                            reinterpret_cast<int64_t *>(sb + s_iv), reinterpret_cast<int64_t *>(sb + s_col), range_off);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(hb, wk, 64, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (const int rf = ex_flag_result(c, reinterpret_cast<const uint32_t *>(hb), "extract_select")) return rf;
+        if (const int rf = co_flag_read(c, F.flag, "extract_select", EX_OUTSIDE)) return rf;
     }
     S.n_sel = ns; S.genome_gen = c->genome_gen; S.valid = true;
     if (n_sel) *n_sel = ns;
@@ -236,8 +203,8 @@ int mauve_extract_fetch(mauve_ctx *c, char *rows, int64_t row_stride, int64_t *s
         else {
             // pieces of whole columns, 16-byte aligned in the device rows, through the staging
             const size_t wmax = std::max<size_t>(16, (((size_t)64 << 20) / (size_t)S.n_keep) & ~(size_t)15);
-            HIPCHK(c, c->pin_ex.ensure(std::min(wmax, pitch) * (size_t)S.n_keep + 256));
-            char *hb = c->pin_ex.as<char>() + 256;
+            HIPCHK(c, c->pin_stage.ensure(std::min(wmax, pitch) * (size_t)S.n_keep + 256));
+            char *hb = c->pin_stage.as<char>() + 256;
             for (size_t c0 = 0; c0 < ns; c0 += wmax) {
                 const size_t w = std::min(wmax, ns - c0);
                 HIPCHK(c, hipMemcpy2DAsync(hb, w, mat + c0, pitch, w, (size_t)S.n_keep, hipMemcpyDeviceToHost, c->stream));
@@ -245,14 +212,11 @@ int mauve_extract_fetch(mauve_ctx *c, char *rows, int64_t row_stride, int64_t *s
                 for (int k = 0; k < S.n_keep; k++) memcpy(rows + (size_t)k * (size_t)row_stride + c0, hb + (size_t)k * w, w);
             }
         }
-        HIPCHK(c, c->pin_ex.ensure(256));
-        HIPCHK(c, hipMemcpyAsync(c->pin_ex.p, flag, 64, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (const int rf = ex_flag_result(c, c->pin_ex.as<uint32_t>(), "extract_fetch")) return rf;
+        if (const int rf = co_flag_read(c, flag, "extract_fetch", EX_OUTSIDE)) return rf;
     }
-    if (sel_iv) if (const int rc = ex_copy_out(c, sel_iv, sb + s_iv, ns * 8)) return rc;
-    if (sel_col) if (const int rc = ex_copy_out(c, sel_col, sb + s_col, ns * 8)) return rc;
-    if (range_off) if (const int rc = ex_copy_out(c, range_off, sb, (nR + 1) * 8)) return rc;
+    if (sel_iv) if (const int rc = copy_to_caller(c, c->pin_stage, sel_iv, sb + s_iv, ns * 8)) return rc;
+    if (sel_col) if (const int rc = copy_to_caller(c, c->pin_stage, sel_col, sb + s_col, ns * 8)) return rc;
+    if (range_off) if (const int rc = copy_to_caller(c, c->pin_stage, range_off, sb, (nR + 1) * 8)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MAUVE_OK;
 }

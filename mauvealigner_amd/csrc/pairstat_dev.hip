@@ -3,8 +3,8 @@
 // of IdentityMatrix (mauveAligner.cpp:784-800, calculateBackboneCoverage.cpp:106-127), BackboneIdentityMatrix (pairCompare.cpp:57-60,77,
 // calculateBackboneCoverage2.cpp:98-121), the pairwise loop of gappiness.cpp:33-50 and computeSPScore (multiEVD.cpp:41-46, repeatoire.cpp:2527).
 // It reads the coordinate index in force (S14) and the resident genomes; a cell is the S15 cell (extract_cells.hpp).
-//   ex_ranges   (extract_cells.hpp) the ranges against their intervals, the interval ends against the resident genomes
-//   scan        a unit of work is one range x one 64-column word of the index that overlaps it: units per range, scanned (dev_scan.hpp)
+//   ex_front    (extract_cells.hpp) the ranges against their intervals, the interval ends against the resident genomes; a unit of work is
+//               one range x one 64-column word of the index that overlaps it: units per range (PsUnits), scanned
 //   ps_count    a workgroup takes a span of consecutive chunks of PS_UNITS units.  Phase 1, a wave per unit and a lane per column: the cell of
 //               every genome, five ballots per genome = the bit-sliced letter masks, to LDS.  Phase 2, a thread per pair (strided over the
 //               workgroup above 256 pairs) walks the chunk's units: popcounts of mask intersections into 30 counters in registers; the gap
@@ -15,8 +15,6 @@
 // are empty for the pair, so the spans they belong to look back at nothing: every word is looked back at by at most one span.
 // All counts are integers and no result depends on the tiling.
 #include "common.hpp"
-#include "coord_index.hpp"
-#include "dev_scan.hpp"
 #include "extract_cells.hpp"
 #include <algorithm>
 #include <cstring>
@@ -33,6 +31,7 @@ constexpr int PS_W = MAUVE_PAIR_STATS_WORDS;
 // the 64-column words of the index a range overlaps
 struct PsUnits {
     const int64_t *gs, *cl;
+    static PsUnits of(const int64_t *gs, const int64_t *cl) { return PsUnits{gs, cl}; }
     __device__ int64_t value(uint32_t r) const { const int64_t n = cl[r]; return n ? ((gs[r] + n - 1) >> 6) - (gs[r] >> 6) + 1 : 0; }
 };
 
@@ -145,7 +144,7 @@ __global__ void __launch_bounds__(256) ps_count(CoordDev D, ExGenomes G, int64_t
         }
         __syncthreads();
     }
-    if (bad) ex_report(flag, bad);
+    if (bad) atomicOr(flag, bad);
 }
 
 }  // namespace
@@ -158,73 +157,41 @@ int mauve_pair_stats(mauve_ctx *c, int64_t n_pair, const int32_t *pair_a, const 
     if (!c) return MAUVE_ERR_ARG;
     if (const int rs = ex_check_state(c, "pair_stats")) return rs;
     const int N = c->nseq;
-    std::vector<int32_t> pa, pb;
+    std::vector<int32_t> pairs;                              // the a of every pair, then the b
     if (!pair_a) {
-        for (int a = 0; a < N; a++) for (int b = a + 1; b < N; b++) { pa.push_back(a); pb.push_back(b); }
+        for (int a = 0; a < N; a++) for (int b = a + 1; b < N; b++) pairs.push_back(a);
+        for (int a = 0; a < N; a++) for (int b = a + 1; b < N; b++) pairs.push_back(b);
     } else {
         if (n_pair < 1 || n_pair > PS_MAX_PAIRS || !pair_b) { c->err = "pair_stats: n_pair outside [1, 1024] or pair_b missing"; return MAUVE_ERR_ARG; }
         for (int64_t k = 0; k < n_pair; k++) {
             const int32_t a = pair_a[k], b = pair_b[k];
             if (a < 0 || a >= N || b < 0 || b >= N || a == b) { c->err = "pair_stats: pair " + std::to_string(k) + " holds an id outside [0, nseq) or one genome twice"; return MAUVE_ERR_ARG; }
         }
-        pa.assign(pair_a, pair_a + n_pair); pb.assign(pair_b, pair_b + n_pair);
+        pairs.assign(pair_a, pair_a + n_pair); pairs.insert(pairs.end(), pair_b, pair_b + n_pair);
     }
-    const int P = (int)pa.size();
+    const int P = (int)(pairs.size() / 2);
+    // the record checks come before any device work; range arguments that ex_front will refuse are left to it: that refusal comes first
     const int64_t R = range_iv ? n_range : c->co.n_iv;
-    if (R < 0 || (range_iv && R && (!range_col || !range_len))) { c->err = "pair_stats: missing range arrays"; return MAUVE_ERR_ARG; }
-    if (R >= ((int64_t)1 << 31)) { c->err = "pair_stats: too many ranges"; return MAUVE_ERR_LIMIT; }
-    const int64_t n_rec = per_range ? R * (int64_t)P : (int64_t)P;
-    if (n_rec > PS_MAX_RECORDS) { c->err = "pair_stats: more than 2^24 records"; return MAUVE_ERR_LIMIT; }
-    if (n_rec && !stats) { c->err = "pair_stats: stats is NULL"; return MAUVE_ERR_ARG; }
-    const CoordDev &D = *c->co.dev;
-    const ExGenomes G = ex_genomes(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    // work area: flag words | the caller's ranges | first column and length of every range | the scan of their units | its tile sums | the pairs
-    const size_t nR = (size_t)R, nP = (size_t)P, n_ivg = (size_t)(D.n_iv * D.N);
-    const uint32_t tilesR = (uint32_t)((nR + devscan::TILE - 1) / devscan::TILE);
-    const size_t w_iv = 64, w_col = w_iv + up64(nR * 8), w_len = w_col + up64(nR * 8), w_pa = w_len + up64(nR * 8), w_pb = w_pa + up64(nP * 4), w_gs = w_pb + up64(nP * 4),
-                 w_cl = w_gs + up64(nR * 8), w_uo = w_cl + up64(nR * 8), w_bs = w_uo + up64((nR + 1) * 8), w_total = w_bs + up64((size_t)tilesR * 8 + 8);
-    HIPCHK(c, c->ps_work.ensure(w_total));
-    HIPCHK(c, c->pin_ps.ensure(std::max<size_t>(w_gs, 256)));
-    HIPCHK(c, c->ps_out.ensure((size_t)n_rec * PS_W * 8 + 64));
-    char *wk = c->ps_work.as<char>(), *hb = c->pin_ps.as<char>();
-    uint32_t *flag = reinterpret_cast<uint32_t *>(wk);
-    unsigned long long *out = c->ps_out.as<unsigned long long>();
-    HIPCHK(c, hipMemsetAsync(wk, 0, 64, c->stream));
-    if (n_rec) HIPCHK(c, hipMemsetAsync(out, 0, (size_t)n_rec * PS_W * 8, c->stream));
-    const bool own = range_iv && R;
-    if (own) { memcpy(hb + w_iv, range_iv, nR * 8); memcpy(hb + w_col, range_col, nR * 8); memcpy(hb + w_len, range_len, nR * 8); }
-    if (P) { memcpy(hb + w_pa, pa.data(), nP * 4); memcpy(hb + w_pb, pb.data(), nP * 4); }
-    const size_t up0 = own ? w_iv : w_pa;
-    if (w_gs > up0) HIPCHK(c, hipMemcpyAsync(wk + up0, hb + up0, w_gs - up0, hipMemcpyHostToDevice, c->stream));
-    const int64_t *d_iv = range_iv ? reinterpret_cast<const int64_t *>(wk + w_iv) : nullptr, *d_col = reinterpret_cast<const int64_t *>(wk + w_col),
-                  *d_len = reinterpret_cast<const int64_t *>(wk + w_len);
-    int64_t *gstart = reinterpret_cast<int64_t *>(wk + w_gs), *clen = reinterpret_cast<int64_t *>(wk + w_cl), *unit_off = reinterpret_cast<int64_t *>(wk + w_uo),
-            *bsum = reinterpret_cast<int64_t *>(wk + w_bs);
-    const size_t n_chk = std::max(nR, n_ivg);
-    if (n_chk) hipLaunchKernelGGL(ex_ranges, dim3((uint32_t)((n_chk + 255) / 256)), dim3(256), 0, c->stream, D, G, R, d_iv, d_col, d_len, gstart, clen, flag);
-    if (R) {
-        const PsUnits in{gstart, clen};
-        hipLaunchKernelGGL((devscan::vscan_partial<int64_t, PsUnits>), dim3(tilesR), dim3(256), 0, c->stream, in, (uint32_t)R, bsum);
-        hipLaunchKernelGGL((devscan::vscan_write<int64_t, PsUnits>), dim3(tilesR), dim3(256), 0, c->stream, in, (uint32_t)R, bsum, unit_off, (int64_t *)nullptr);
-    } else HIPCHK(c, hipMemsetAsync(unit_off, 0, 8, c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hb, wk, 64, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hb + 64, unit_off + R, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (const int rf = ex_flag_result(c, reinterpret_cast<const uint32_t *>(hb), "pair_stats")) return rf;
-    const int64_t n_units = *reinterpret_cast<const int64_t *>(hb + 64);
+    const bool r_ok = R >= 0 && R < ((int64_t)1 << 31) && !(range_iv && R && (!range_col || !range_len));
+    const int64_t n_rec = per_range && r_ok ? R * (int64_t)P : (int64_t)P;
+    if (r_ok && n_rec > PS_MAX_RECORDS) { c->err = "pair_stats: more than 2^24 records"; return MAUVE_ERR_LIMIT; }
+    if (r_ok && n_rec && !stats) { c->err = "pair_stats: stats is NULL"; return MAUVE_ERR_ARG; }
+    ExFront F;                                               // the pair lists travel behind the ranges
+    if (const int rf = ex_front<PsUnits>(c, "pair_stats", c->ps_work, n_range, range_iv, range_col, range_len, pairs.data(), pairs.size() * 4, &F)) return rf;
+    const int64_t n_units = F.total;
     if (n_units >= ((int64_t)1 << 28)) { c->err = "pair_stats: the ranges hold 2^34 columns or more"; return MAUVE_ERR_LIMIT; }
+    HIPCHK(c, c->ps_out.ensure((size_t)n_rec * PS_W * 8 + 64));
+    unsigned long long *out = c->ps_out.as<unsigned long long>();
+    if (n_rec) HIPCHK(c, hipMemsetAsync(out, 0, (size_t)n_rec * PS_W * 8, c->stream));
     if (n_units && P) {
         const int64_t n_chunks = (n_units + PS_UNITS - 1) / PS_UNITS, cps = (n_chunks + PS_MAX_SPANS - 1) / PS_MAX_SPANS, spans = (n_chunks + cps - 1) / cps;
-        hipLaunchKernelGGL(ps_count, dim3((uint32_t)spans), dim3(256), 0, c->stream, D, G, R, d_iv, gstart, clen, unit_off, n_units, cps, P,
-                           reinterpret_cast<const int32_t *>(wk + w_pa), reinterpret_cast<const int32_t *>(wk + w_pb), per_range != 0, out, flag);
+        const int32_t *d_pairs = reinterpret_cast<const int32_t *>(F.tail);
+        hipLaunchKernelGGL(ps_count, dim3((uint32_t)spans), dim3(256), 0, c->stream, *c->co.dev, F.G, R, F.d_iv, F.gstart, F.clen, F.off, n_units, cps, P, d_pairs, d_pairs + P,
+                           per_range != 0, out, F.flag);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(hb, wk, 64, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (const int rf = ex_flag_result(c, reinterpret_cast<const uint32_t *>(hb), "pair_stats")) return rf;
+        if (const int rf = co_flag_read(c, F.flag, "pair_stats", EX_OUTSIDE)) return rf;
     }
-    if (const int rc = ex_copy_out(c, stats, out, (size_t)n_rec * PS_W * 8)) return rc;
+    if (const int rc = copy_to_caller(c, c->pin_stage, stats, out, (size_t)n_rec * PS_W * 8)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MAUVE_OK;
 }

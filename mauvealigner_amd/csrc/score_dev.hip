@@ -2,7 +2,7 @@
 // (scoreAlignment.cpp:99-457) for every ordered genome pair, from two coordinate indices (S14) -- the correct alignment T in the context's
 // second slot (mauve_score_truth) and the calculated alignment C, the index in force.  No genome data is read.
 //   sc_count   a wave per 64-column word of T, a lane per column.  The lane finds its interval of T (binary search of T's col_off) and keeps
-//              T's position of every genome at its column in LDS (one co_rank per genome on T's block record).  Then for every genome i with
+//              T's position of every genome at its column in LDS (co_column per genome on T's block record).  Then for every genome i with
 //              a residue there: co_find on C for that base, and for every j != i C's presence and rank of j at the found column against T's
 //              position of j -> one of six classes; a ballot and a popcount per class go into an LDS table [N][N][6] of 32-bit counters.
 //              The table leaves with one 64-bit integer atomic per non-zero counter at the workgroup's end.
@@ -44,15 +44,10 @@ __global__ void __launch_bounds__(256) sc_count(CoordDev T, CoordDev Cx, int64_t
         for (int g = 0; g < N; g++) {
             uint32_t p = 0;
             if (ok) {
-                const CoordIv I = T.ivt[(size_t)a * N + g];
-                if (I.left) {
-                    const CoordRec r = T.rec[(size_t)b * N + g];
-                    bool present;
-                    const int64_t k = co_rank(r, (int)(x - b * CO_BLOCK), &present) - I.base;
-                    if (present) {
-                        const int64_t q = (I.col0_rev & 1) ? I.right - k : I.left + k;
-                        if (k < 0 || q < I.left || q > I.right || q >= SC_MAX_POS) bad |= CO_BAD_INDEX; else p = (uint32_t)q;
-                    }
+                CoordIv I; bool present; int64_t k;
+                if (co_column(T, a, x, g, &I, &present, &k) && present) {
+                    const int64_t q = co_residue(I, k);
+                    if (k < 0 || q < I.left || q > I.right || q >= SC_MAX_POS) bad |= CO_BAD_INDEX; else p = (uint32_t)q;
                 }
             }
             s_pos[g * 64 + lane] = p;                          // (a lane reads back only what it wrote itself)
@@ -78,21 +73,16 @@ __global__ void __launch_bounds__(256) sc_count(CoordDev T, CoordDev Cx, int64_t
                     int64_t pj = 0;
                     bool inside = false;
                     if (found) {
-                        const CoordIv J = Cx.ivt[(size_t)civ * N + j];
-                        inside = J.left != 0;
-                        if (inside) {
-                            const CoordRec r = Cx.rec[(size_t)cb * N + j];
-                            bool present;
-                            const int64_t k = co_rank(r, coff, &present) - J.base;
-                            if (present) {
-                                pj = (J.col0_rev & 1) ? J.right - k : J.left + k;
-                                if (k < 0 || pj < J.left || pj > J.right) { bad |= CO_BAD_INDEX; pj = 0; }
-                            }
+                        CoordIv J; bool present; int64_t k;
+                        inside = co_column(Cx, civ, cb, coff, j, &J, &present, &k);
+                        if (present) {
+                            pj = co_residue(J, k);
+                            if (k < 0 || pj < J.left || pj > J.right) { bad |= CO_BAD_INDEX; pj = 0; }
                         }
                     }
                     cls = tj ? (pj ? (pj == tj ? 0 : 1) : (inside ? 2 : 3)) : (pj ? 4 : 5);
                 }
-                uint32_t mine = 0;
+                uint32_t mine = 0;                             // (the popcount of a ballot is one scalar instruction: it stays ahead of the lane's choice)
 #pragma unroll
                 for (int l = 0; l < SC_CLASSES; l++) { const uint64_t m = __ballot(cls == l); if (lane == l) mine = (uint32_t)__popcll(m); }
                 if (lane < SC_CLASSES && mine) atomicAdd(&s_tab[(i * N + j) * SC_CLASSES + lane], mine);
@@ -136,9 +126,7 @@ int mauve_score_alignment(mauve_ctx *c, int64_t *records)
     const size_t bytes = (size_t)N * N * SC_W * 8;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, c->sc_out.ensure(64 + bytes));
-    const bool direct = host_pointer_is_pinned(records);
-    HIPCHK(c, c->pin_sc.ensure(64 + (direct ? 0 : bytes)));
-    char *d = c->sc_out.as<char>(), *hb = c->pin_sc.as<char>();
+    char *d = c->sc_out.as<char>();
     HIPCHK(c, hipMemsetAsync(d, 0, 64 + bytes, c->stream));
     const int64_t n_cols = XT.n_cols, n_words = (n_cols + 63) / 64;
     if (n_words) {
@@ -150,12 +138,11 @@ int mauve_score_alignment(mauve_ctx *c, int64_t *records)
                            reinterpret_cast<uint32_t *>(d));
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpyAsync(hb, d, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(direct ? (void *)records : (void *)(hb + 64), d + 64, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (*reinterpret_cast<const uint32_t *>(hb)) { c->err = "score_alignment: an index is inconsistent with its interval table"; return MAUVE_ERR_STATE; }
-    if (!direct) memcpy(records, hb + 64, bytes);
-    return MAUVE_OK;
+    // page-locked records are queued in front of the flag's one synchronise; pageable ones are written only once the flag is judged
+    const bool direct = host_pointer_is_pinned(records);
+    if (direct) if (const int rc = copy_to_caller(c, c->pin_stage, records, d + 64, bytes)) return rc;
+    if (const int rf = co_flag_read(c, reinterpret_cast<const uint32_t *>(d), "score_alignment", nullptr, "an index")) return rf;
+    return direct ? MAUVE_OK : copy_to_caller(c, c->pin_stage, records, d + 64, bytes);
 }
 
 }  // extern "C"

@@ -314,6 +314,41 @@ def test_extract_errors_and_state(ctx):
     assert ctx.extract_select(require=5) == 22
 
 
+def test_one_range_list_through_both_front_end_callers(ctx):
+    """extract_select and pair_stats share the range front end: the same range list through both, on the hand case.  Every column of a range
+    is selected once (every genome kept, no rule) and is counted once for every pair (a letter pair, a one-sided column or an empty one);
+    a range one column too long is refused by both, and the refused select leaves no selection; the records come out the same through the
+    staging and straight into page-locked memory, right after the coordinate stage used the staging"""
+    from mauvealigner_amd import _lib
+    gs = [_codes(s) for s in HAND_GENOMES]
+    ctx.set_genomes(gs)
+    _index(ctx, HAND)
+    # an empty range, one that starts inside a 64-column word, the whole interval, two ranges of the same interval (overlapping)
+    iv, col, ln = [0, 0, 0, 0, 0], [7, 5, 0, 2, 9], [0, 9, 20, 3, 8]
+    assert ctx.extract_select(ranges=(iv, col, ln)) == sum(ln)
+    rows, siv, scol, roff = ctx.extract_fetch()
+    st = ctx.pair_stats(ranges=(iv, col, ln), per_range=True)
+    assert st.shape == (len(ln), 3, 32)
+    for r in range(len(ln)):
+        assert roff[r + 1] - roff[r] == ln[r]
+        assert scol[roff[r]:roff[r + 1]].tolist() == list(range(col[r], col[r] + ln[r]))
+        for p in range(3):
+            assert st[r, p, :25].sum() + st[r, p, 25] + st[r, p, 26] + st[r, p, 29] == ln[r], (r, p)
+    long = (iv + [0], col + [15], ln + [6])                   # columns 15 .. 20 of an interval of 20
+    with pytest.raises(RuntimeError, match=r"\(-1\)"):
+        ctx.extract_select(ranges=long)
+    with pytest.raises(RuntimeError, match=r"\(-5\)"):
+        ctx.extract_fetch()
+    with pytest.raises(RuntimeError, match=r"\(-1\)"):
+        ctx.pair_stats(ranges=long, per_range=True)
+    # one staging buffer: pageable and page-locked records straight after an index call and a query of the coordinate stage
+    _index(ctx, HAND)
+    assert ctx.column_positions([0], [19])[0].tolist() == [[20, 115, -201]]
+    pageable = ctx.pair_stats(ranges=(iv, col, ln), per_range=True, out=np.empty((len(ln), 3, 32), np.int64))
+    pinned = ctx.pair_stats(ranges=(iv, col, ln), per_range=True, out=_lib.pinned_empty((len(ln), 3, 32), np.int64))
+    assert np.array_equal(pageable, pinned) and np.array_equal(pageable, st)
+
+
 def test_extract_full_size_c3(ctx):
     """the C3 configuration of bench.py (5 x 5 Mbp) aligned once: all columns of all genomes, then the polymorphic core columns --
     both equal to the restatement, every byte"""
