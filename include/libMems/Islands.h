@@ -10,13 +10,46 @@
 //                               intervals (or before the first one).
 // Text layouts (libMems' own are not in the reference tree): backbone rows "left<TAB>right" per sequence, signed;
 // island rows  "seq<TAB>left<TAB>right<TAB>other_seq<TAB>interval";  between-LCB rows  "seq<TAB>left<TAB>right".
+// Also the per-column pair scores evd and multiEVD walk (evd.cpp:28-31, multiEVD.cpp:41-46): INVALID_SCORE, computeMatchScores,
+// computeGapScores, in the frozen form of DESIGN.md S18 -- together they are computeSPScore of the two rows, column by column
+// (PairwiseScoringScheme.h), and the columns in which both rows have a gap stay INVALID_SCORE.  The device form of the walk over them
+// is HipExcursions (Excursions.h).
 #ifndef MAUVE_HIP_ISLANDS_H
 #define MAUVE_HIP_ISLANDS_H
 
+#include <limits>
 #include "Backbone.h"
 #include "GappedAlignment.h"
+#include "PairwiseScoringScheme.h"
 
 namespace mems {
+
+static const score_t INVALID_SCORE = (std::numeric_limits<score_t>::max)();
+
+// scores[c] = matrix[a][b] where both rows have a residue (bases outside ACGT score as A), INVALID_SCORE in every other column
+inline void computeMatchScores(const std::string &seq1, const std::string &seq2, const PairwiseScoringScheme &scoring, std::vector<score_t> &scores)
+{
+    auto code = [](char ch) { switch (ch) { case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return 0; } };
+    scores.assign(seq1.size(), INVALID_SCORE);
+    for (size_t c = 0; c < seq1.size() && c < seq2.size(); c++)
+        if (seq1[c] != '-' && seq2[c] != '-') scores[c] = scoring.matrix[code(seq1[c])][code(seq2[c])];
+}
+
+// ... and the columns in which one row alone has a residue: gap_open where the column opens a run of that row's gap, gap_extend where it
+// continues one (two gaps neither score nor interrupt a run, two residues end it); the other columns of `scores` are left as they are
+inline void computeGapScores(const std::string &seq1, const std::string &seq2, const PairwiseScoringScheme &scoring, std::vector<score_t> &scores)
+{
+    scores.resize(seq1.size(), INVALID_SCORE);
+    int open = 0;                                          // 1: a run with seq1 gapped is open, 2: seq2 gapped
+    for (size_t c = 0; c < seq1.size() && c < seq2.size(); c++) {
+        const bool g1 = seq1[c] == '-', g2 = seq2[c] == '-';
+        if (g1 && g2) continue;
+        if (!g1 && !g2) { open = 0; continue; }
+        const int side = g1 ? 1 : 2;
+        scores[c] = open == side ? scoring.gap_extend : scoring.gap_open;
+        open = side;
+    }
+}
 
 inline void simpleFindBackbone(IntervalList &il, uint backbone_size, uint max_gap_size, std::vector<GappedAlignment> &backbone_data)
 {

@@ -485,6 +485,42 @@ int mauve_pair_stats(mauve_ctx *ctx, int64_t n_pair, const int32_t *pair_a, cons
                      int per_range, int64_t *stats);
 void mauve_pair_stats_identity(const int64_t *stats, int64_t n_rec, double *identity);
 void mauve_pair_stats_sp_score(const int64_t *stats, int64_t n_rec, const mauve_scoring *sc, int64_t *score);
+/* ---- excursions of the column scores: the state machine of getLocalRecordHeights in evd and multiEVD (evd.cpp:12-66, multiEVD.cpp:29-79),
+        whose sorted heights are the thresholds libMems' backbone detection is calibrated with, as a scan on the coordinate index in force
+        and the resident genomes.  Frozen form DESIGN.md S18.  The cell of a genome in a column is the S15 cell, the letter codes are those
+        of S16, N scores as A; sc == NULL: mauve_default_scoring.  All sums are int64_t.
+        A stream is the columns of one range, ascending, that one set keeps, each with a score s:
+          pair stream (ordered pair (a, b)): the columns in which a or b has a residue; s = matrix[x'][y'] where both have one, else gap_open
+            where the column opens a run by S16's rule (slots 27 / 28: the nearest earlier column of the same range that is not `neither`
+            is missing or of another kind), else gap_extend;
+          core stream (genome mask m of at least two genomes): the columns in which every genome of m has a residue (S15's require = m); s =
+            the sum over the pairs g < h of m of matrix[x'_g][x'_h].  A genome of m that is absent from the interval makes the stream empty.
+        The walk: v = -s, x = 0, h = 0; per column the first rule that matches: (1) x > 0 and x + v < 0: the record (h, this column), then
+        x = 0, h = 0; (2) x == 0 and v > 0: x = v, h = max(h, x); (3) x > 0: x += v, h = max(h, x); (4) nothing.  Nothing is recorded at the
+        stream's end; (x, h) there is the stream's tail.  An excursion that returns to exactly 0 is not ended: its height carries into the
+        next rise (the tool's loop).
+        Pairs and ranges: as for mauve_pair_stats.  group_mask == NULL: one group of every genome (n_group is not read); else
+        1 <= n_group <= 1024 masks.  Streams are numbered range-major: stream = r * n_set + k.
+        The first two calls compute everything, keep it in the context and tell the number of records; mauve_excursions_fetch writes
+        height[n_exc], end_col[n_exc] (the column inside the range's interval, in the form mauve_column_positions takes), stream_off
+        [n_stream + 1] and tail[n_stream][2] = (x, h).  Within a stream the records come in column order.  Any output pointer may be NULL;
+        page-locked ones (mauve_host_alloc) are copied directly.  Records are placed by scanned offsets and nothing depends on the tiling:
+        two calls return identical bytes.  The calls neither need nor disturb the extract selection in force.
+        MAUVE_ERR_ARG: n_pair or n_group outside [1, 1024], a == b or an id outside [0, nseq), a mask of fewer than two genomes or with a
+        bit at or above nseq, and the range errors of mauve_extract_select; MAUVE_ERR_LIMIT: more than 2^24 streams, or sets x chunks of 2^31 or more; MAUVE_ERR_STATE: as
+        for mauve_extract_select; a fetch without a result -- the next excursions call, mauve_coord_index* or mauve_set_genomes* ends it.
+        Work is cut into chunks of MAUVE_EXCURSION_CHUNK columns, counted from the 64-column word of the index that holds a range's first
+        column; the figure is public for tests and sizing only, no result depends on it.
+        mauve_excursion_thresholds, on the host and without a context: for the fractions .95, .99, .999 and .9999 of the sorted heights
+        threshold[q] = the height at index min((size_t)(n * f), n - 1) and above[q] = n minus that index (evd.cpp:108-126, in double);
+        zeros for n = 0. ---- */
+#define MAUVE_EXCURSION_CHUNK 512
+int mauve_excursions_pairs(mauve_ctx *ctx, const mauve_scoring *sc, int64_t n_pair, const int32_t *pair_a, const int32_t *pair_b,
+                           int64_t n_range, const int64_t *range_iv, const int64_t *range_col, const int64_t *range_len, int64_t *n_exc);
+int mauve_excursions_core(mauve_ctx *ctx, const mauve_scoring *sc, int64_t n_group, const uint32_t *group_mask,
+                          int64_t n_range, const int64_t *range_iv, const int64_t *range_col, const int64_t *range_len, int64_t *n_exc);
+int mauve_excursions_fetch(mauve_ctx *ctx, int64_t *height, int64_t *end_col, int64_t *stream_off, int64_t *tail /* n_stream*2 */);
+void mauve_excursion_thresholds(const int64_t *height, int64_t n, int64_t threshold[4], int64_t above[4]);
 /* ---- an alignment scored against a correct one: scoreAlignment <correct alignment> <calculated alignment> (scoreAlignment.cpp:99-457),
         counted on two coordinate indices.  Frozen form DESIGN.md S17.  T is the correct alignment, loaded by the first call below; C, the
         calculated one, is the coordinate index in force (S14); both are over the same nseq genomes and follow S14's position rule.  No
@@ -532,7 +568,11 @@ int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_
 #define MAUVE_K_RUNS 7
 #define MAUVE_K_CANON 8           /* canonical order on the device: key build, its (small) radix sort, gather */
 #define MAUVE_K_MISC 9            /* the small sorts of the device chain and of the DP front end */
-#define MAUVE_K_COUNT 10
+#define MAUVE_K_EXC_MAPS 10       /* excursions (S18): the chunks' maps */
+#define MAUVE_K_EXC_SCAN 11       /* ... the scans along the streams (two launches each, and the scan of the streams' counts) */
+#define MAUVE_K_EXC_COUNT 12      /* ... emission counts and carried maxima */
+#define MAUVE_K_EXC_WRITE 13      /* ... the records */
+#define MAUVE_K_COUNT 14
 int mauve_profile_enable(mauve_ctx *ctx, int on);
 int mauve_profile_reset(mauve_ctx *ctx);
 int mauve_profile_get(mauve_ctx *ctx, int kernel, double *total_ms, int64_t *launches, int64_t *units);

@@ -16,7 +16,8 @@ CODING_SEED, SOLID_SEED = 3, 0x7FFFFFFF
 MAX_GENOME_LEN, MAX_TOTAL_LEN = 1 << 31, (1 << 32) - (1 << 20)             # mauve_set_genomes* limits (MAUVE_MAX_GENOME_LEN, MAUVE_MAX_TOTAL_LEN)
 REPEAT_PENALTY_OFF, REPEAT_PENALTY_NEGATIVE, REPEAT_PENALTY_ZERO = 0, 1, 2    # DESIGN.md S11d (progressiveMauve --repeat-penalty)
 K_EXTRACT, K_SORT_HIST, K_SORT_SCAN, K_SORT_SCATTER, K_JOIN, K_EXTEND, K_DP, K_RUNS = range(8)
-KERNEL_NAMES = ["seed_extract", "rs_hist", "rs_rowscan", "rs_scatter", "mum_join", "mum_extend", "dp_step", "mum_runs", "canon_sort", "misc_sort"]
+KERNEL_NAMES = ["seed_extract", "rs_hist", "rs_rowscan", "rs_scatter", "mum_join", "mum_extend", "dp_step", "mum_runs", "canon_sort", "misc_sort",
+                "exc_maps", "exc_scan", "exc_count", "exc_write"]
 
 # every symbol include/mauve_hip.h declares (checked by tests/test_abi.py without a GPU)
 EXPORTS = [
@@ -36,6 +37,7 @@ EXPORTS = [
     "mauve_default_extract_params", "mauve_extract_select", "mauve_extract_fetch",
     "mauve_pair_stats", "mauve_pair_stats_identity", "mauve_pair_stats_sp_score",
     "mauve_score_truth", "mauve_score_alignment", "mauve_score_totals_from",
+    "mauve_excursions_pairs", "mauve_excursions_core", "mauve_excursions_fetch", "mauve_excursion_thresholds",
 ]
 
 
@@ -242,6 +244,20 @@ def pair_stats_sp_score(stats, scoring=None):
     if out.size:
         L.mauve_pair_stats_sp_score(_p(st, C.c_int64), C.c_int64(out.size), C.byref(sc), _p(out, C.c_int64))
     return out
+
+
+EXCURSION_CHUNK = 512                 # MAUVE_EXCURSION_CHUNK: columns per chunk of the excursion scan; no result depends on it
+
+
+def excursion_thresholds(height):
+    """mauve_excursion_thresholds (host entry, no context): heights -> (threshold[4], above[4]) for the fractions .95, .99, .999, .9999 of
+    the sorted heights, by evd's index arithmetic; zeros for no height"""
+    h = np.ascontiguousarray(height, np.int64).reshape(-1)
+    thr, above = np.zeros(4, np.int64), np.zeros(4, np.int64)
+    L = load()
+    L.mauve_excursion_thresholds.restype = None
+    L.mauve_excursion_thresholds(_p(h if h.size else np.zeros(1, np.int64), C.c_int64), C.c_int64(h.size), _p(thr, C.c_int64), _p(above, C.c_int64))
+    return thr, above
 
 
 SCORE_WORDS = 8                       # MAUVE_SCORE_WORDS: int64 per ordered genome pair (DESIGN.md S17)
@@ -963,6 +979,53 @@ class Context:
         st = self._co_out((out,), 0, shape, np.int64) if out is not None else np.zeros(shape, np.int64)
         self._chk(self.L.mauve_pair_stats(self.h, *args_p, *args_r, C.c_int(int(bool(per_range))), _p(st if st.size else z8, C.c_int64)), "mauve_pair_stats")
         return st
+
+    # ---- excursions of the column scores ----
+    def _excursions(self, fn, name, scoring, args_set, n_set, ranges):
+        n_range, args_r = self._range_args(ranges, name)
+        n = C.c_int64(0)
+        self._exc_shape = None
+        self._chk(fn(self.h, C.byref(scoring) if scoring is not None else None, *args_set, *args_r, C.byref(n)), "mauve_" + name)
+        self._exc_shape = (n.value, n_range * n_set)
+        return n.value
+
+    def excursions_pairs(self, pairs=None, ranges=None, scoring=None):
+        """mauve_excursions_pairs: the excursions of the negated column scores of genome pairs -> the number of records, kept in the context
+        for excursions_fetch.  pairs, ranges as for pair_stats; scoring: a Scoring (None = the default).  Streams: range-major."""
+        N = self.coord_index_size()[0]
+        z4 = np.zeros(1, np.int32)
+        if pairs is None:
+            n_pair, args_p = N * (N - 1) // 2, (C.c_int64(0), None, None)
+        else:
+            pa, pb = (np.ascontiguousarray(x, np.int32) for x in pairs)
+            if pa.ndim != 1 or pa.shape != pb.shape:
+                raise ValueError("excursions_pairs: the pair arrays differ in length")
+            n_pair, args_p = len(pa), (C.c_int64(len(pa)), _p(pa if len(pa) else z4, C.c_int32), _p(pb if len(pa) else z4, C.c_int32))
+        return self._excursions(self.L.mauve_excursions_pairs, "excursions_pairs", scoring, args_p, n_pair, ranges)
+
+    def excursions_core(self, groups=None, ranges=None, scoring=None):
+        """mauve_excursions_core: the excursions over the columns in which every genome of a group has a residue; groups: genome masks
+        (ints) or lists of genome ids, None = one group of every genome"""
+        self.coord_index_size()
+        if groups is None:
+            n_group, args_g = 1, (C.c_int64(0), None)
+        else:
+            gm = np.ascontiguousarray([g if isinstance(g, (int, np.integer)) else sum(1 << int(t) for t in g) for g in groups], np.uint32).reshape(-1)
+            n_group, args_g = len(gm), (C.c_int64(len(gm)), _p(gm if len(gm) else np.zeros(1, np.uint32), C.c_uint32))
+        return self._excursions(self.L.mauve_excursions_core, "excursions_core", scoring, args_g, n_group, ranges)
+
+    def excursions_fetch(self, out=None, want=(True, True, True, True)):
+        """mauve_excursions_fetch of the result in force -> (height[n_exc], end_col[n_exc], stream_off[n_stream + 1], tail[n_stream, 2]);
+        out = the four arrays (e.g. from pinned_empty: copied without staging); want: which of the four to copy (the others: None)"""
+        shape = getattr(self, "_exc_shape", None)
+        if shape is None:                                        # no result: the library says so (nothing is written)
+            self._chk(self.L.mauve_excursions_fetch(self.h, None, None, None, None), "mauve_excursions_fetch")
+            raise RuntimeError("mauve_excursions_fetch ran without a result")
+        ne, ns = shape
+        shapes = ((ne,), (ne,), (ns + 1,), (ns, 2))
+        arrs = [self._co_out(out, q, shapes[q], np.int64) if want[q] else None for q in range(4)]
+        self._chk(self.L.mauve_excursions_fetch(self.h, *[_p(a, C.c_int64) if a is not None and a.size else None for a in arrs]), "mauve_excursions_fetch")
+        return tuple(arrs)
 
     # ---- an alignment scored against a correct one (DESIGN.md S17) ----
     def score_truth(self, aln):

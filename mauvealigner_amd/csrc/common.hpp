@@ -288,6 +288,10 @@ struct mauve_ctx {
     DevBuf ex_work, ex_bits, ex_sel, ex_mat;   // the flag word, ranges and their scan; selection words and their scan; sel_iv | sel_col | range_off; the matrix (padded pitch)
     // pairwise column statistics (pairstat_dev.hip): no state between calls, work buffers apart from the selection's
     DevBuf ps_work, ps_out;              // the flag word, ranges, their units' scan, the pair lists; the records
+    // excursions of the column scores (excursion_dev.hip): the result of the last call stays for its fetches; it belongs to the
+    // index and the genomes it was made on (an index call clears `valid`, genome_gen tells an upload)
+    struct Excursions { bool valid = false; uint64_t genome_gen = 0; int64_t n_stream = 0, n_exc = 0; } exc;
+    DevBuf exc_work, exc_tmp, exc_meta, exc_rec;   // the flag word, ranges, their chunks' scan, the sets; per-chunk arrays; stream_off | tail; height | end_col
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them
     DevBuf rec_genomes, rec_seg;         // recursive anchoring: gap sub-sequences + segment table

@@ -330,7 +330,7 @@ extern "C" {
 int mauve_coord_index(mauve_ctx *c)
 {
     if (!c) return MAUVE_ERR_ARG;
-    c->co.valid = false; c->ex.valid = false;               // (a selection, DESIGN.md S15, belongs to the index it was made on)
+    c->co.valid = false; c->ex.valid = false; c->exc.valid = false;      // (a selection, DESIGN.md S15, and an excursion result, S18, belong to the index they were made on)
     AlignResult &R = c->res;
     if (R.stale) { c->err = "coord_index: the genomes were replaced after this alignment was made"; return MAUVE_ERR_STATE; }
     const int64_t n_iv = R.sz.n_iv;
@@ -352,7 +352,7 @@ int mauve_coord_index(mauve_ctx *c)
 int mauve_coord_index_alignment(mauve_ctx *c, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)
 {
     if (!c) return MAUVE_ERR_ARG;
-    c->co.valid = false; c->ex.valid = false;               // (a selection, DESIGN.md S15, belongs to the index it was made on)
+    c->co.valid = false; c->ex.valid = false; c->exc.valid = false;      // (a selection, DESIGN.md S15, and an excursion result, S18, belong to the index they were made on)
     return coord_index_arrays(c, "coord_index", c->co, c->co_index, nseq, n_iv, left, right, reverse, col_off, cols);
 }
 

@@ -1,5 +1,5 @@
-// extract_cells.hpp -- what the stages that read letters through the coordinate index share: extract_dev.hip and
-// pairstat_dev.hip (S16).  The cell rule, the resident genomes as a kernel argument, the state check, and the range front end (ex_front): the
+// extract_cells.hpp -- what the stages that read letters through the coordinate index share: extract_dev.hip,
+// pairstat_dev.hip (S16) and excursion_dev.hip (S18).  The cell rule, the run rule of two rows (ps_run_mask, ps_look_back), the resident genomes as a kernel argument, the state check, and the range front end (ex_front): the
 // caller's ranges checked against the index on the device and a count per range scanned, up to the stage's first own kernel.  Errors go
 // through the flag word of coord_index.hpp.  Internal linkage: every stage compiles its own copy.
 #pragma once
@@ -63,6 +63,42 @@ __device__ __forceinline__ int64_t ex_range_of(const int64_t *__restrict__ cand_
     int64_t a = 0, e = R;
     while (e - a > 1) { const int64_t mid = (a + e) >> 1; if (cand_off[mid] <= t) a = mid; else e = mid; }
     return a;
+}
+
+// ---- the run rule of S16, shared with the excursions of S18 (excursion_dev.hip) ----
+// the columns of X that open a run, for X = the columns where one genome alone has a residue and Y = the columns where either has one.
+// "The previous occupied column was an X column" is a carry chain -- X generates, an unoccupied column propagates, any other kills -- so one add
+// gives the state in front of all 64 columns; cin: the state in front of the word, replaced by the state behind it.
+__device__ __forceinline__ uint64_t ps_run_mask(uint64_t X, uint64_t Y, uint32_t &cin)
+{
+    const uint64_t a = X | ~Y, s = a + X, t = s + cin;
+    const uint64_t into = t ^ a ^ X;
+    cin = (uint32_t)((s < a) | (t < s));
+    return X & ~into;
+}
+__device__ __forceinline__ uint32_t ps_runs(uint64_t X, uint64_t Y, uint32_t &cin) { return (uint32_t)__popcll(ps_run_mask(X, Y, cin)); }
+
+// the presence word w (whole array) of genome g, which interval i holds (has) or not
+__device__ __forceinline__ uint64_t ps_word(const CoordDev &D, bool has, int g, int64_t w)
+{
+    if (!has) return 0;
+    const int64_t b = w / CO_WORDS;
+    return D.rec[(size_t)b * D.N + g].w[w - b * CO_WORDS];
+}
+
+// the run state in front of word aw for the pair (a, b) in a range of interval i that starts at column gs: from the nearest earlier occupied
+// column of the range, none open when there is none
+__device__ __forceinline__ void ps_look_back(const CoordDev &D, int64_t i, int a, int b, int64_t gs, int64_t aw, uint32_t &ca, uint32_t &cb)
+{
+    const bool ha = D.ivt[(size_t)i * D.N + a].left != 0, hb = D.ivt[(size_t)i * D.N + b].left != 0;
+    const int64_t w0 = gs >> 6;
+    ca = cb = 0;
+    for (int64_t w = aw - 1; w >= w0; w--) {
+        uint64_t qa = ps_word(D, ha, a, w), qb = ps_word(D, hb, b, w);
+        if (w == w0) { const uint64_t m = ~co_below((int)(gs & 63)); qa &= m; qb &= m; }
+        const uint64_t y = qa | qb;
+        if (y) { const int h = 63 - __clzll((long long)y); ca = (uint32_t)((qa & ~qb) >> h & 1); cb = (uint32_t)((qb & ~qa) >> h & 1); return; }
+    }
 }
 
 // the resident genomes as a kernel argument
