@@ -58,6 +58,24 @@ extern "C" {
 
 typedef struct mauve_ctx mauve_ctx;
 
+/* The domain of a scoring scheme.
+   (1) Every entry -- gap_open, gap_extend and the 16 of the matrix -- lies within +-MAUVE_SCORING_MAX, and gap_open <= 0: every state of the
+       DP may follow every state, so a rewarded gap opening could be collected in every column.  (gap_extend may be positive.)
+   (2) The gapped DP runs in int32 with -2^29 as minus infinity; its first boundary row is analytic and not clamped and
+       aligned columns add up without an upper clamp, so a scheme must also fit the lengths it is used on.  Every progressive step is a DP
+       of its own that starts at 0.  For an interval of k sequences with L bases together, the longest of n:
+           2 k |gap_open| + (L + k n) |gap_extend| + k max|matrix|   <  MAUVE_DP_SCORE_MAX    (the all-gap path bounds every cell from below)
+           k n max(matrix, 0) + (L + k n) max(gap_extend, 0)         <  MAUVE_DP_SCORE_MAX    (n aligned columns of k rows, and gap columns that
+                                                                                               face L + k n residues at most, bound it from above)
+       Inside this the result is the frozen definition bit for bit; outside it a sum could wrap, and the call is refused instead.
+   mauve_dp_batch[_banded] check (1) and, interval by interval, (2).  mauve_align*, mauve_progressive_align* check (1) and, when `gapped` is set,
+   (2) for the largest interval the parameters admit: k = the resident genomes, n = max(max_gapped_len, max_banded_len), L = k n.  For the
+   default scheme the second line decides: n <= 5 368 709 / k, that is max_banded_len up to 2 684 354 for two genomes, 671 088 for eight, 167 772
+   for 32 (the default lengths need 8e7 of the 5.4e8 at 32 genomes).  mauve_match_sp_scores[_repeat] add in 64 bits and check (1) only.  A refusal
+   is MAUVE_ERR_ARG and the message names the limit. */
+#define MAUVE_SCORING_MAX (1 << 20)
+#define MAUVE_DP_SCORE_MAX (1 << 29)
+
 typedef struct {
     int32_t gap_open;             /* PairwiseScoringScheme.gap_open  (progressiveMauve.cpp:666-687) */
     int32_t gap_extend;           /* PairwiseScoringScheme.gap_extend */

@@ -166,6 +166,77 @@ int refuse_past_2g(mauve_ctx *c, const char *what)
     return MAUVE_ERR_LIMIT;
 }
 
+// The domain of a scoring scheme (mauve_hip.h).  (1) Every entry within +-MAUVE_SCORING_MAX -- the sum-of-pairs scorers add in
+// 64 bits, and one cell of the DP adds at most MAUVE_MAX_SEQ x |entry| = 2^25 to a value clamped at -2^29 -- and gap_open not positive: every
+// state may follow every state, so a path that alternates X and Y opens a gap in every column, and a reward for that has no bound worth checking.
+int refuse_scoring(mauve_ctx *c, const mauve_scoring *sc, const char *what)
+{
+    int64_t worst = std::max(std::llabs((int64_t)sc->gap_open), std::llabs((int64_t)sc->gap_extend));
+    for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) worst = std::max(worst, (int64_t)std::llabs((int64_t)sc->matrix[a][b]));
+    if (worst > MAUVE_SCORING_MAX) {
+        c->err = std::string(what) + ": scoring scheme holds an entry of magnitude " + std::to_string(worst) + ", above the limit of " +
+                 std::to_string(MAUVE_SCORING_MAX) + " (MAUVE_SCORING_MAX, 2^20) for gap_open, gap_extend and the substitution matrix";
+        return MAUVE_ERR_ARG;
+    }
+    if (sc->gap_open > 0) {
+        c->err = std::string(what) + ": gap_open is " + std::to_string(sc->gap_open) + "; a positive gap_open is outside the domain of a scoring scheme (the limit is 0)";
+        return MAUVE_ERR_ARG;
+    }
+    return MAUVE_OK;
+}
+// (2) ... and against the lengths it is used on.  The DP of a step runs in int32; the first boundary row is analytic and not clamped and M has no
+// upper clamp (kernels and oracle alike), so outside this condition a sum can wrap.  For k sequences of `total` bases together, the longest of n
+// (gap_open <= 0 by (1)): the all-gap path bounds every cell of every step from below by -(2 k |open| + (total + k n) |extend| + k max|S|); n
+// aligned columns of k rows bound it from above by k n max(S, 0), plus (total + k n) extend where extend is positive (the gap columns of a path
+// face at most total + k n residues).  Both must stay inside +-MAUVE_DP_SCORE_MAX = 2^29.
+struct DpSchemeBounds {
+    __int128 smax = 0, sabs = 0, go, ge; bool ge_pos;
+    explicit DpSchemeBounds(const mauve_scoring *sc) : go(std::llabs((int64_t)sc->gap_open)), ge(std::llabs((int64_t)sc->gap_extend)), ge_pos(sc->gap_extend > 0)
+    {
+        for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) {
+            smax = std::max<__int128>(smax, sc->matrix[a][b]); sabs = std::max<__int128>(sabs, std::llabs((int64_t)sc->matrix[a][b]));
+        }
+    }
+    bool fits(int64_t k, int64_t total, int64_t n, int64_t *need) const
+    {
+        const __int128 faced = (__int128)total + (__int128)k * n;
+        const __int128 down = 2 * (__int128)k * go + faced * ge + (__int128)k * sabs;
+        const __int128 up = (__int128)k * n * smax + (ge_pos ? faced * ge : 0);
+        const __int128 worst = std::max(down, up), cap = (__int128)1 << 62;
+        *need = (int64_t)std::min(worst, cap);
+        return worst < (__int128)MAUVE_DP_SCORE_MAX;
+    }
+};
+static int refuse_text(mauve_ctx *c, const char *what, int64_t k, int64_t total, int64_t n, int64_t need)
+{
+    c->err = std::string(what) + ": the scoring scheme does not fit the 32-bit DP at these lengths: " + std::to_string(k) + " sequences of " +
+             std::to_string(total) + " bases together, the longest " + std::to_string(n) + ", can reach a score of magnitude " + std::to_string(need) +
+             ", and the limit is " + std::to_string((int64_t)MAUVE_DP_SCORE_MAX) + " (MAUVE_DP_SCORE_MAX, 2^29; mauve_hip.h at mauve_scoring)";
+    return MAUVE_ERR_ARG;
+}
+// the intervals of a mauve_dp_batch call
+int refuse_scoring_batch(mauve_ctx *c, const mauve_scoring *sc, int nseq, int64_t n_iv, const int64_t *seq_off, const char *what)
+{
+    { const int rs = refuse_scoring(c, sc, what); if (rs) return rs; }
+    const DpSchemeBounds B(sc);
+    for (int64_t iv = 0; iv < n_iv; iv++) {
+        int64_t n = 0, need;
+        for (int g = 0; g < nseq; g++) n = std::max(n, seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g]);
+        const int64_t total = seq_off[(iv + 1) * nseq] - seq_off[iv * nseq];
+        if (!B.fits(nseq, total, n, &need)) return refuse_text(c, what, nseq, total, n, need);
+    }
+    return MAUVE_OK;
+}
+// a whole-path call: any interval the parameters let the DP align -- every resident genome with max(max_gapped_len, max_banded_len) bases in it
+int refuse_scoring_params(mauve_ctx *c, const mauve_params *p, const char *what)
+{
+    { const int rs = refuse_scoring(c, &p->scoring, what); if (rs) return rs; }
+    const int64_t k = c->nseq, n = std::min<int64_t>(dp_len_limit(p), (int64_t)1 << 40);     // (any length that large is refused; k n stays in 64 bits)
+    int64_t need;
+    if (!p->gapped || k < 2 || n < 1 || DpSchemeBounds(&p->scoring).fits(k, k * n, n, &need)) return MAUVE_OK;
+    return refuse_text(c, what, k, k * n, n, need);
+}
+
 extern "C" {
 
 // The second stream carries the one-wave launch of the DP (dp_step2: thousands of small workgroups) while the workgroup launches -- the tail of

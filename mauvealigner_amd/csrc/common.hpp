@@ -425,6 +425,9 @@ GenomeSet main_genome_set(mauve_ctx *ctx);
 bool seedpass_wide(int64_t total_windows);
 // genome sets of 2^31 bases or more: the seed-pass entry points take them; the alignment path behind them refuses them
 // (MAUVE_ERR_LIMIT, `what` named) until it is verified at that size
+int refuse_scoring(mauve_ctx *c, const mauve_scoring *sc, const char *what);   // an entry beyond +-MAUVE_SCORING_MAX: MAUVE_ERR_ARG
+int refuse_scoring_batch(mauve_ctx *c, const mauve_scoring *sc, int nseq, int64_t n_iv, const int64_t *seq_off, const char *what);   // ... or a scheme that does not fit the 32-bit DP at these intervals' lengths
+int refuse_scoring_params(mauve_ctx *c, const mauve_params *p, const char *what);                                                    // ... or at the lengths the parameters admit
 int refuse_past_2g(mauve_ctx *c, const char *what);      // 64-bit window indices for a pass of this many windows
 int seedpass_run(mauve_ctx *ctx, const GenomeSet &gs, uint64_t pattern, int mode, uint64_t mask, int extend,
                  const uint32_t *seg_dev, uint32_t nseg, int64_t *n_matches);

@@ -1790,7 +1790,7 @@ static bool dp_wide_on() { static const bool o = getenv("MAUVE_DP_NO_WIDE") == n
 // the DP launches: the workgroup-per-interval kernels (dp_step_wide, dp_step_big) beside dp_step2 (wave / sub-wave per interval),
 // over the positions [a, b) of the launch list [workgroup | one wave | G = 16 | G = 8 | G = 4]; tb_base is
 // subtracted from the traceback offsets (rounds, below)
-static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64_t n_big, const DpClasses &full, const int64_t *d_seq_off,
+static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64_t n_big, int64_t big_len, const DpClasses &full, const int64_t *d_seq_off,
                            const int64_t *d_tb_off, const int64_t *d_rows_off, const DpScoring &sc, int64_t tb_base, int64_t band_from)
 {
     auto clip = [&](int64_t first, int64_t n, int64_t &f2, int64_t &n2) { f2 = std::max(first, a); n2 = std::max<int64_t>(0, std::min(first + n, b) - f2); };
@@ -1841,8 +1841,11 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
                                ctx->dp_list.as<int64_t>() + bf + (first), DP_STEP_ARGS, band_from, (int)(K), flags)
         if (wide) { if (n_cl) DPW_LAUNCH(0, n_cl, DPW_KMAX); if (bn > n_cl) DPW_LAUNCH(n_cl, bn - n_cl, 1); }
 #undef DPW_LAUNCH
-        // (the stripe pipeline: every entry without the wide sweep; with it, only where banded intervals or an inadmissible scoring scheme can occur)
-        if (!wide || band_from != INT64_MAX || !dp3_admissible(1, nseq, sc.ge, sc.go))
+        // (the stripe pipeline: every entry without the wide sweep; with it, only where dp_takes_wide can reject an entry -- banded intervals, or the
+        // longest workgroup entry of the batch, big_len bases, is not admitted under this scheme: admission falls with the length, so no shorter one
+        // is rejected while that one is let in, and an admissible batch pays no launch for it)
+        // (bn > 0 here, so big_len >= 1 on both front ends unless every workgroup entry is empty; the floor of 1 then asks about the scheme alone)
+        if (!wide || band_from != INT64_MAX || !dp3_admissible(std::max<int64_t>(big_len, 1), nseq, sc.ge, sc.go))
             hipLaunchKernelGGL(dp_step_big, dim3((uint32_t)bn), dim3(64 * DP_MW_WAVES), 0, ctx->stream, nseq, ctx->dp_list.as<int64_t>() + bf, DP_STEP_ARGS,
                                band_from, wide ? 1 : 0);
     }
@@ -1861,7 +1864,7 @@ static int64_t dp_tb_budget()
     static const int64_t b = getenv("MAUVE_DP_TB_BUDGET") ? atoll(getenv("MAUVE_DP_TB_BUDGET")) : (8LL << 30);
     return std::max<int64_t>(b, 1 << 16);
 }
-static int dp_launch_rounds(mauve_ctx *ctx, int nseq, int64_t n_iv, int64_t n_big, const DpClasses &cl, const int64_t *d_seq_off,
+static int dp_launch_rounds(mauve_ctx *ctx, int nseq, int64_t n_iv, int64_t n_big, int64_t big_len, const DpClasses &cl, const int64_t *d_seq_off,
                             const int64_t *d_tb_off, const int64_t *d_rows_off, const DpScoring &sc, const int64_t *tb_list, int *rounds_out,
                             int64_t band_from)
 {
@@ -1873,7 +1876,7 @@ static int dp_launch_rounds(mauve_ctx *ctx, int nseq, int64_t n_iv, int64_t n_bi
             if (tb_list[a + 1] - tb_list[a] > budget) { ctx->err = "dp: one interval needs more traceback than MAUVE_DP_TB_BUDGET allows"; return MAUVE_ERR_LIMIT; }
             while (b < n_iv && tb_list[b + 1] - tb_list[a] <= budget) b++;
         } else b = n_iv;
-        int rc = dp_launch_steps(ctx, nseq, a, b, n_big, cl, d_seq_off, d_tb_off, d_rows_off, sc, tb_list ? tb_list[a] : 0, band_from);
+        int rc = dp_launch_steps(ctx, nseq, a, b, n_big, big_len, cl, d_seq_off, d_tb_off, d_rows_off, sc, tb_list ? tb_list[a] : 0, band_from);
         if (rc) return rc;
         rounds++;
         a = b;
@@ -1988,6 +1991,9 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
         for (int64_t k = 0; k < n_iv; k++) { const int64_t iv = lst[(size_t)k]; tmp[(size_t)pos[klass(iv)]++] = iv; }
         lst.swap(tmp);
     }
+    // bases of the longest workgroup entry: whether dp_step_wide can leave one of them to dp_step_big under this scheme (dp_launch_steps)
+    int64_t big_len = 0;
+    for (int64_t k = 0; k < n_big; k++) { const int64_t iv = lst[(size_t)k]; big_len = std::max(big_len, seq_off[(iv + 1) * nseq] - seq_off[iv * nseq]); }
     // traceback offsets follow the launch list, so that a round of the list uses one contiguous piece of the buffer
     std::vector<int64_t> &tb_list = H.tb_list; tb_list.resize((size_t)n_iv + 1);
     tbt = 0;
@@ -2028,7 +2034,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     memcpy(pin_list, lst.data(), (size_t)n_iv * 8);
     HIPCHK(ctx, hipMemcpyAsync(ctx->dp_list.p, pin_list, (size_t)n_iv * 8, hipMemcpyHostToDevice, ctx->stream));
     int rounds = 1;
-    { int rcl = dp_launch_rounds(ctx, nseq, n_iv, n_big, cl, d_seq_off, d_tb_off, d_rows_off, sc, one_round ? nullptr : tb_list.data(), &rounds, band_from); if (rcl) return rcl; }
+    { int rcl = dp_launch_rounds(ctx, nseq, n_iv, n_big, big_len, cl, d_seq_off, d_tb_off, d_rows_off, sc, one_round ? nullptr : tb_list.data(), &rounds, band_from); if (rcl) return rcl; }
     HIPCHK(ctx, hipGetLastError());
     if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // host work while the DP kernels run
     HIPCHK(ctx, ctx->pin_meta.ensure((size_t)n_iv * sizeof(DpMeta)));
@@ -2093,6 +2099,7 @@ using namespace devscan;
 
 struct DpFrontTotals {                       // device block read back once
     int64_t codes, tb, rows, est, n_dp, first_med, first_s32, first_s16, cols, cells, first_c, err;
+    unsigned long long big_len;              // bases of the longest workgroup entry (dpf_list)
 };
 
 __device__ __forceinline__ void dpf_gap(const int32_t *__restrict__ alen, const int32_t *__restrict__ ast, int N, uint32_t k, int g,
@@ -2198,12 +2205,17 @@ struct DpBigPick {
     __device__ void emit(uint32_t, uint32_t, int) const {}
     __device__ void total(uint32_t, int) const {}
 };
-// list for the kernels (int64 slots) and the class boundaries of the class-sorted keys
+// list for the kernels (int64 slots), the class boundaries of the class-sorted keys, and the bases of the longest workgroup entry (the totals
+// block was cleared in front of the sizing kernel)
 __global__ void __launch_bounds__(256) dpf_list(const uint32_t *__restrict__ key2, const uint32_t *__restrict__ order, DpFrontTotals *__restrict__ tot,
-                                                int64_t *__restrict__ list)
+                                                int64_t *__restrict__ list, const int64_t *__restrict__ seq_off, int N)
 {
     const uint32_t n = (uint32_t)tot->n_dp, j = blockIdx.x * 256u + threadIdx.x;
-    if (j < n) list[j] = order[j];
+    if (j < n) {
+        const uint32_t s = order[j];
+        list[j] = s;
+        if (key2[j] == 0) atomicMax(&tot->big_len, (unsigned long long)(seq_off[((size_t)s + 1) * N] - seq_off[(size_t)s * N]));
+    }
     if (j < 4) {                                              // first index with key >= j + 1
         uint32_t lo = 0, hi = n;
         while (lo < hi) { const uint32_t mid = (lo + hi) / 2; if (key2[mid] >= j + 1) hi = mid; else lo = mid + 1; }
@@ -2281,7 +2293,7 @@ static int dpf_run(mauve_ctx *ctx, const DpFrontWork &W, int N, uint32_t n_dp, c
     uint32_t *ck = fk, *cv = ov;
     rc = sort_pairs_u32(ctx, n_dp, 3, &ck, &cv, W.k3, fv, MAUVE_K_MISC);
     if (rc) return rc;
-    hipLaunchKernelGGL(dpf_list, dim3(blk_d), dim3(256), 0, ctx->stream, ck, cv, tot, ctx->dp_list.as<int64_t>());
+    hipLaunchKernelGGL(dpf_list, dim3(blk_d), dim3(256), 0, ctx->stream, ck, cv, tot, ctx->dp_list.as<int64_t>(), W.d_seq_off, N);
     // traceback offsets in list order (a round of the list then uses one contiguous piece of the buffer)
     int64_t *tb_list_dev = W.d_col_off;                                 // scratch until the results need it
     hipLaunchKernelGGL((vscan_partial<int64_t, ListVal>), dim3(nbd), dim3(256), 0, ctx->stream, ListVal{W.need, cv}, n_dp, W.bsum2);
@@ -2307,7 +2319,7 @@ static int dpf_run(mauve_ctx *ctx, const DpFrontWork &W, int N, uint32_t n_dp, c
     }
     dp_launch_gather_codes(ctx, W.d_seq_off, (int64_t)n_dp * N);
     R.rounds = 1;
-    rc = dp_launch_rounds(ctx, N, n_dp, R.n_big, cl, W.d_seq_off, W.d_tb_off, W.d_rows_off, sc, tb_list.empty() ? nullptr : tb_list.data(), &R.rounds, ctx->dp_band_from);
+    rc = dp_launch_rounds(ctx, N, n_dp, R.n_big, (int64_t)ht->big_len, cl, W.d_seq_off, W.d_tb_off, W.d_rows_off, sc, tb_list.empty() ? nullptr : tb_list.data(), &R.rounds, ctx->dp_band_from);
     if (rc) return rc;
     // results: column offsets, scores and the cell count by scans over the per-interval records; the columns compacted
     const DpMeta *meta = ctx->dp_meta.as<DpMeta>();
@@ -2668,6 +2680,7 @@ extern "C" int mauve_dp_batch(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint
     if (nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !seq_off || !sc || !col_off || (n_iv && !cols)) {
         ctx->err = "dp_batch: bad argument"; return MAUVE_ERR_ARG;
     }
+    { const int rs = refuse_scoring_batch(ctx, sc, nseq, n_iv, seq_off, "dp_batch"); if (rs) return rs; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->dp_band_from = INT64_MAX;          // the GappedAligner seam aligns what it is given in full
     return dp_batch_run(ctx, nseq, n_iv, codes, seq_off, sc, cols, col_off, score, nullptr);
@@ -2680,6 +2693,7 @@ extern "C" int mauve_dp_batch_banded(mauve_ctx *ctx, int nseq, int64_t n_iv, con
     if (nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !seq_off || !sc || !col_off || (n_iv && !cols) || band_from < 0) {
         ctx->err = "dp_batch_banded: bad argument"; return MAUVE_ERR_ARG;
     }
+    { const int rs = refuse_scoring_batch(ctx, sc, nseq, n_iv, seq_off, "dp_batch_banded"); if (rs) return rs; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->dp_band_from = band_from;
     return dp_batch_run(ctx, nseq, n_iv, codes, seq_off, sc, cols, col_off, score, nullptr);

@@ -810,6 +810,7 @@ int mauve_align(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
 static int align_whole(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *sizes)
 {
     { const int rg = refuse_past_2g(c, "align"); if (rg) return rg; }
+    { const int rs = refuse_scoring_params(c, p, "align"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     static const bool host_front = getenv("MAUVE_HOST_DP_FRONT") != nullptr;      // A/B switch
@@ -840,6 +841,7 @@ int mauve_align_lcbs(mauve_ctx *c, const mauve_params *p, int64_t n, const int64
 {
     if (!c || !p || !sizes) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "align_lcbs"); if (rg) return rg; }
+    { const int rs = refuse_scoring_params(c, p, "align_lcbs"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "align_lcbs: at least two genomes required"; return MAUVE_ERR_STATE; }
     if (n < 0 || (n && (!length || !start || !lcb))) { c->err = "align_lcbs: bad anchor list"; return MAUVE_ERR_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -898,6 +900,7 @@ int mauve_match_sp_scores(mauve_ctx *c, int64_t n, const int64_t *length, const 
 {
     if (!c || !sc || n < 0 || (n && (!length || !start || !scores))) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "match_sp_scores"); if (rg) return rg; }
+    { const int rs = refuse_scoring(c, sc, "match_sp_scores"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "match_sp_scores: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->nseq;
@@ -915,6 +918,7 @@ int mauve_match_sp_scores_repeat(mauve_ctx *c, uint64_t pattern, int mode, int64
 {
     if (!c || !sc || n < 0 || (n && (!length || !start || !scores))) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "match_sp_scores_repeat"); if (rg) return rg; }
+    { const int rs = refuse_scoring(c, sc, "match_sp_scores_repeat"); if (rs) return rs; }
     if (mode != MAUVE_REPEAT_PENALTY_OFF && mode != MAUVE_REPEAT_PENALTY_NEGATIVE && mode != MAUVE_REPEAT_PENALTY_ZERO) { c->err = "match_sp_scores_repeat: unknown mode"; return MAUVE_ERR_ARG; }
     SeedShape sh;
     if (!make_seed_shape(pattern, &sh)) { c->err = "seed pattern must be palindromic, span <= 49, weight <= 31"; return MAUVE_ERR_ARG; }
@@ -933,6 +937,7 @@ int mauve_align_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const in
 {
     if (!c || !p || !sizes) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "align_matches"); if (rg) return rg; }
+    { const int rs = refuse_scoring_params(c, p, "align_matches"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     MatchVec mv;
@@ -948,6 +953,7 @@ int mauve_align_begin_matches(mauve_ctx *c, const mauve_params *p, int64_t n, co
 {
     if (!c || !p || !n_dp) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "align_begin_matches"); if (rg) return rg; }
+    { const int rs = refuse_scoring_params(c, p, "align_begin_matches"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     MatchVec mv;
@@ -979,6 +985,7 @@ int mauve_align_begin(mauve_ctx *c, const mauve_params *p, int64_t *n_dp, int64_
 {
     if (!c || !p || !n_dp) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "align_begin"); if (rg) return rg; }
+    { const int rs = refuse_scoring_params(c, p, "align_begin"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
     int rc = align_begin(c, p);

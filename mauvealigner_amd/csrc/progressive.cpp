@@ -595,6 +595,7 @@ int mauve_progressive_align(mauve_ctx *c, const mauve_params *p, mauve_align_siz
 {
     if (!c) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "progressive_align"); if (rg) return rg; }
+    if (p) { const int rs = refuse_scoring_params(c, p, "progressive_align"); if (rs) return rs; }
     return progressive_core(c, p, sizes, nullptr, nullptr, tree_left, tree_right, dist);
 }
 
@@ -605,6 +606,7 @@ int mauve_progressive_align_tree(mauve_ctx *c, const mauve_params *p, mauve_alig
 {
     if (!c || !tree_left || !tree_right) return MAUVE_ERR_ARG;
     { const int rg = refuse_past_2g(c, "progressive_align_tree"); if (rg) return rg; }
+    if (p) { const int rs = refuse_scoring_params(c, p, "progressive_align_tree"); if (rs) return rs; }
     const int N = c->nseq, M = 2 * N - 1;
     if (N < 2) { c->err = "progressive_align: at least two genomes required"; return MAUVE_ERR_STATE; }
     std::vector<char> used((size_t)M, 0);

@@ -8,6 +8,7 @@ import pytest
 
 from mauvealigner_amd import synth
 from oracle import pyoracle as O
+from tests.align_helpers import long_gap_pair as _long_gap_pair, whole_compare
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -286,17 +287,6 @@ def _check_dp_banded(ctx, intervals, band_from):
         assert int(s) == es
 
 
-def _long_gap_pair(rng, L, shift, div=0.05):
-    """Two related sequences whose optimal alignment leaves the band: `shift` extra bases early in b, `shift` bases
-    dropped later (the lengths stay close, so the band does not widen with them)."""
-    a = rng.integers(0, 4, L, dtype=np.uint8)
-    b = a.copy()
-    mut = rng.random(L) < div
-    b[mut] = (b[mut] + 1) % 4
-    b = np.concatenate([b[:L // 6], rng.integers(0, 4, shift, dtype=np.uint8), b[L // 6:L // 2], b[L // 2 + shift:]])
-    return [a, b]
-
-
 def test_dp_banded(ctx):
     """Banded steps against the oracle's banded DP: a path that the band cuts (the result differs from the
     full DP, so the band is what is being tested), unequal lengths, three sequences, the smallest shapes with every
@@ -434,23 +424,7 @@ def _same_align(ctx, gs, **kw):
     names = ["g%d" % i for i in range(len(gs))]
     r = ctx.align(_lib.default_params(**kw), names=names, want_xmfa=True)
     e = O.align(gs, O.default_params(**kw), names=names, want_xmfa=True)
-    N = len(gs)
-    eml, ems = O.multiplicity_filter(e["mums"][0], e["mums"][1], N)
-    assert np.array_equal(r["mum_length"], eml) and np.array_equal(r["mum_start"], ems)
-    assert r["n_lcb"] == e["lcbs"]["n_lcb"]
-    assert np.array_equal(r["lcb_weight"], e["lcbs"]["weight"])
-    a = e["aln"]
-    assert np.array_equal(r["anchor_length"], a["anchor_length"])
-    assert np.array_equal(r["anchor_start"], a["anchor_start"])
-    assert np.array_equal(r["anchor_lcb"], a["anchor_lcb"])
-    assert r["n_iv"] == a["n_iv"]
-    assert np.array_equal(r["left"], a["left"]) and np.array_equal(r["right"], a["right"])
-    assert np.array_equal(r["reverse"], a["reverse"])
-    assert np.array_equal(r["col_off"], a["col_off"])
-    assert np.array_equal(r["cols"], a["cols"])
-    assert np.array_equal(r["dp_score"], a["dp_score"])
-    assert r["n_gap_dp"] == a["n_gap_dp"] and r["n_dp_cells"] == a["n_dp_cells"]
-    assert r["xmfa"] == e["xmfa"]
+    whole_compare(r, e, "align", len(gs))
     return r
 
 
@@ -676,15 +650,7 @@ def _same_progressive(ctx, gs, tree=None, **kw):
     names = ["g%d" % i for i in range(len(gs))]
     r = ctx.progressive_align(_lib.default_params(**kw), names=names, want_xmfa=True, tree=tree)
     e = O.progressive_align(gs, O.default_params(**kw), names=names, want_xmfa=True, tree=tree)
-    if tree is None:
-        assert np.array_equal(r["dist"], e["dist"])
-    assert np.array_equal(r["tree"][0], e["tree"][0]) and np.array_equal(r["tree"][1], e["tree"][1])
-    a = e["aln"]
-    assert r["n_iv"] == a["n_iv"]
-    for k in ("left", "right", "reverse", "col_off", "cols", "dp_score"):
-        assert np.array_equal(r[k], a[k]), k
-    assert r["n_gap_dp"] == a["n_gap_dp"] and r["n_dp_cells"] == a["n_dp_cells"]
-    assert r["xmfa"] == e["xmfa"]
+    whole_compare(r, e, "progressive", len(gs), dist=tree is None)
     return r
 
 
@@ -995,17 +961,9 @@ from mauvealigner_amd import _lib, synth
 from oracle import pyoracle as O
 rng = np.random.default_rng(21)
 ctx = _lib.Context(0)
+from tests.align_helpers import seqs as _seqs
 def seqs(lens, div=0.15):
-    base = rng.integers(0, 4, max(max(lens), 1), dtype=np.uint8)
-    out = []
-    for L in lens:
-        if L == 0:
-            out.append(np.zeros(0, np.uint8)); continue
-        x = synth.mutate(base, div, rng, indel_frac=0.3)[:L]
-        if len(x) < L:
-            x = np.concatenate([x, rng.integers(0, 4, L - len(x), dtype=np.uint8)])
-        out.append(x)
-    return out
+    return _seqs(rng, lens, div)
 def check(ivs):
     cols, score = ctx.dp_batch(ivs)
     for iv, c, s in zip(ivs, cols, score):
@@ -1047,17 +1005,9 @@ from mauvealigner_amd import _lib, synth
 from oracle import pyoracle as O
 rng = np.random.default_rng(33)
 ctx = _lib.Context(0)
+from tests.align_helpers import seqs as _seqs
 def seqs(lens, div=0.15):
-    base = rng.integers(0, 4, max(max(lens), 1), dtype=np.uint8)
-    out = []
-    for L in lens:
-        if L == 0:
-            out.append(np.zeros(0, np.uint8)); continue
-        x = synth.mutate(base, div, rng, indel_frac=0.3)[:L]
-        if len(x) < L:
-            x = np.concatenate([x, rng.integers(0, 4, L - len(x), dtype=np.uint8)])
-        out.append(x)
-    return out
+    return _seqs(rng, lens, div)
 def check(ivs):
     cols, score = ctx.dp_batch(ivs)
     for iv, c, s in zip(ivs, cols, score):
