@@ -822,8 +822,9 @@ def test_progressive_refinement(ctx):
 
 def test_homology_pass_before_the_backbone(ctx):
     """DESIGN.md S12b (detectAndApplyBackbone's homology HMM, progressiveMauve.cpp:226-243,319-322): the two-state Viterbi path per
-    interval and genome pair -- one wave per (interval, pair), 64 columns per step as a max-plus matrix scan, the way back on two
-    ballot words per step -- and the re-split columns equal the oracle's, bit for bit: on a clean alignment nothing moves; a
+    interval and genome pair -- one wave per (interval, pair, 4096-column segment) composing the clamp functions x -> clamp(x + t, lo, hi)
+    of its columns 64 lanes at a time, the host chaining the segments, the way back as a second scan over two-bit state maps -- and
+    the re-split columns equal the oracle's, bit for bit: on a clean alignment nothing moves; a
     stretch of unrelated sequence that the gapped aligner forced into columns is taken apart again; reverse-strand intervals,
     a progressive alignment with absent genomes, other scores; the backbone afterwards is the oracle's backbone of the new columns."""
     from mauvealigner_amd import _lib
