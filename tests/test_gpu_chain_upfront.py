@@ -3,7 +3,9 @@ of all genomes are cut from the list as it enters the stage, and a genome's elim
 those of the oracle's whole-list elimination.
 
 Random dense lists -- N = 2..4 genomes, 2..119 matches, lengths 1..59, starts in [1, span) with span 200..4000, 40 % reverse
-components in genomes >= 1, lists with tied genome-0 starts dropped -- go through ctx.align_matches (recursive=0, gapped=0,
+components in genomes >= 1, lists with tied genome-0 starts kept and every list handed over in canonical order (the index that
+decides among equal left ends is the caller's order for the oracle and the canonical one for the product:
+tests/test_chain_cpu.py) -- go through ctx.align_matches (recursive=0, gapped=0,
 extend_lcbs=0, lcb_weight=0: every LCB stays), which puts a caller's list where the seed pass leaves its own when
 MAUVE_CANON_DEVICE_MIN=1, so chain_device_graph chains it.  The switches are read once per process: every variant runs in a
 process of its own -- the default, MAUVE_CH_CL_MAX=2 (clusters of three and more hand the list back to the host chain) and
@@ -22,8 +24,10 @@ import sys, numpy as np
 sys.path.insert(0, %(root)r)
 from mauvealigner_amd import _lib
 from oracle import pyoracle as O
+from tests import chain_ref
 rng = np.random.default_rng(1)
 cases = []
+tied = 0
 for _ in range(400):
     N = int(rng.integers(2, 5)); n = int(rng.integers(2, 120)); span = int(rng.integers(200, 4001))
     ln = rng.integers(1, 60, n).astype(np.int64)
@@ -31,8 +35,10 @@ for _ in range(400):
     rev = rng.random((n, N)) < 0.4
     rev[:, 0] = False
     st[rev] = -st[rev]
-    if len(np.unique(st[:, 0])) == n:
-        cases.append((span, ln, st))
+    tied += len(np.unique(st[:, 0])) < n
+    ln, st = chain_ref.canonicalise(ln, st)
+    cases.append((span, np.asarray(ln, np.int64), np.asarray(st, np.int64)))
+assert tied > 0
 print("lists", len(cases), "small", sum(len(c[1]) <= 48 for c in cases))
 assert len(cases) >= 100
 ctx = _lib.Context(0)
