@@ -1314,6 +1314,9 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
                 kmin = max(kmin, a); kmax = min(kmax, b);
             }
             const bool masks = vmask || cmask;
+            const uint32_t revset = (uint32_t)__ballot(lane < nc && comp[lane].rev != 0u);
+            const int rev_at = revset ? __builtin_amdgcn_readfirstlane((int)comp[__ffs(revset) - 1].g) : -1;      // a component on the other strand, if there is one
+            const uint32_t ap_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)ap); const int anchor_s = __builtin_amdgcn_readfirstlane(anchor);
             // the first round of either walk: offsets -64 .. -1 and 1 .. 64, fetched together
             uint64_t M2[2][4];
             { const int64_t jj[2] = {-64, 1}; ext_mismatch<2>(comp, nc, sh.span, jj, lane, M2); }
@@ -1332,7 +1335,20 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
                 const bool hh = a && hm == mask;
                 const uint64_t A = __ballot(a), H = __ballot(hh);
                 const int p = walk_round(A, sh.span, done);                          // offsets consumed in this round
-                if (H & (p >= 64 ? ~0ULL : ((1ULL << p) - 1ULL))) { leftmost = false; done = true; }      // a same-mask hit among the visited offsets
+                // A same-mask hit among the visited offsets sits on this diagonal's windows (its offset agrees, and every component genome holds
+                // the mer once), but it is a hit OF this diagonal (S4) only with the candidate's strand relations.  They can differ in one way: the
+                // mer is its own reverse complement (even weight) -- it agrees on a reverse diagonal and is a forward hit, of another cluster --
+                // and then in every component, so one reversed component of the candidate decides.  Wave-uniform: scalar loads, no vector register.
+                uint64_t Hv = H & (p >= 64 ? ~0ULL : ((1ULL << p) - 1ULL));
+                if (Hv && rev_at >= 0) {
+                    bool met = false;
+                    for (; Hv && !met; Hv &= Hv - 1) {
+                        const uint32_t *rq = tpos + ((size_t)ap_s + (size_t)cur - (size_t)__ffsll((unsigned long long)Hv)) * (size_t)N;
+                        met = ((rq[rev_at] ^ rq[anchor_s]) >> 31) != 0u;
+                    }
+                    Hv = met;
+                }
+                if (Hv) { leftmost = false; done = true; }
                 cur -= p;
                 if (p == 0) done = true;                   // (p == 0 only happens with done set; keeps cur != 0 a valid "not the first round" test)
             }
