@@ -72,6 +72,34 @@ inline void ComputeLCBs_v2(MatchList &ml, const std::vector<gnSeqI> &breakpoints
     }
 }
 
+// The two over a vector of any match type (projectAndStrip.cpp:110-112 over GappedAlignment*; projectIntervalList over
+// MatchProjectionAdapter*): the matches come sorted by their left end in sequence 0; only left ends and strands decide (DESIGN.md S19
+// rule 3: S5's rule on records of length 1), so gapped matches chain like ungapped ones
+template <class MatchT>
+void IdentifyBreakpoints(std::vector<MatchT *> &ml, std::vector<gnSeqI> &breakpoints)
+{
+    breakpoints.clear();
+    if (ml.empty()) return;
+    const uint N = ml[0]->SeqCount(); const int64_t n = (int64_t)ml.size();
+    std::sort(ml.begin(), ml.end(), MatchStartComparator<MatchT>(0));
+    std::vector<int64_t> len((size_t)n, 1), st((size_t)n * N), lcb((size_t)n);
+    for (int64_t i = 0; i < n; i++) for (uint g = 0; g < N; g++) st[(size_t)i * N + g] = ml[(size_t)i]->Start(g);
+    int64_t K = 0;
+    if (mauve_lcb_chain((int)N, n, len.data(), st.data(), 0, 0, lcb.data(), &K, nullptr, nullptr, nullptr, nullptr, nullptr) != MAUVE_OK)
+        throw genome::gnException("IdentifyBreakpoints: N-way matches required");
+    for (int64_t i = 0; i < n; i++) if (i + 1 == n || lcb[(size_t)i] != lcb[(size_t)i + 1]) breakpoints.push_back((gnSeqI)i);
+}
+template <class MatchT>
+void ComputeLCBs_v2(const std::vector<MatchT *> &ml, const std::vector<gnSeqI> &breakpoints, std::vector<std::vector<MatchT *>> &lcb_list)
+{
+    lcb_list.clear();
+    size_t cur = 0;
+    for (gnSeqI bp : breakpoints) {
+        lcb_list.push_back(std::vector<MatchT *>());
+        for (; cur <= (size_t)bp && cur < ml.size(); cur++) lcb_list.back().push_back(ml[cur]);
+    }
+}
+
 // adjacency table of the LCBs (toGrimmFormat.cpp:51-79): ends signed by orientation, neighbours by left end per sequence
 inline void computeLCBAdjacencies_v2(std::vector<MatchList> &lcb_list, const std::vector<int64> &weights, std::vector<LCB> &adjacencies)
 {

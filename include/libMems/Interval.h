@@ -50,12 +50,20 @@ public:
     void CalculateOffset() {}                                  // extractSubalignments.cpp:24: the ranges are always current here
     const std::vector<uint32_t> &Columns() const { return cols_; }
     // SetMatches(vector&) STEALS the vector's contents (MatchRecord.h:338-339; getAlignmentWindows.cpp:64,71): the
-    // matches, in order, become the block's columns -- the block keeps them (GetMatches / StealMatches give them back).
+    // matches, in order, become the block's columns, with the bases between two collinear ones as columns of their sequence alone
+    // (rebuild) -- the block keeps them (GetMatches / StealMatches give them back).
     void SetMatches(std::vector<AbstractMatch *> &matches)
     {
         for (AbstractMatch *m : matches_) m->Free();
         matches_.swap(matches); matches.clear();
         rebuild();
+    }
+    // ... over a vector of any match type (projectAndStrip.cpp:122 GappedAlignment*, alignmentProjector.cpp:75 MatchProjectionAdapter*)
+    template <class MatchT> void SetMatches(std::vector<MatchT *> &matches)
+    {
+        std::vector<AbstractMatch *> v(matches.begin(), matches.end());
+        matches.clear();
+        SetMatches(v);
     }
     const std::vector<AbstractMatch *> &GetMatches() const { return matches_; }
     void StealMatches(std::vector<AbstractMatch *> &out) { out.swap(matches_); matches_.clear(); }
@@ -139,7 +147,17 @@ private:
         const uint N = matches_[0]->SeqCount();
         left_.assign(N, 0); right_.assign(N, 0); rev_.assign(N, 0);
         std::vector<gnSeqI> pos; std::vector<bool> col;
+        const AbstractMatch *prev = nullptr;
         for (const AbstractMatch *m : matches_) {
+            // the bases a sequence has strictly between two consecutive matches that it runs through in order (projectIntervalList's
+            // collinear pieces, DESIGN.md S19 rule 4) become columns of that sequence alone, sequence after sequence: the block then holds
+            // RightEnd - LeftEnd + 1 residues of it, and GetAlignment and GetColumn find every piece's bases where they are
+            for (uint g = 0; prev && g < N && g < m->SeqCount() && g < prev->SeqCount(); g++) {
+                if (m->Start(g) == NO_MATCH || prev->Start(g) == NO_MATCH || (m->Start(g) < 0) != (prev->Start(g) < 0)) continue;
+                const int64 d = m->Start(g) < 0 ? (int64)prev->LeftEnd(g) - (int64)m->RightEnd(g) - 1 : (int64)m->LeftEnd(g) - (int64)prev->RightEnd(g) - 1;
+                if (d > 0) cols_.insert(cols_.end(), (size_t)d, 1u << g);
+            }
+            prev = m;
             for (uint g = 0; g < N && g < m->SeqCount(); g++) {
                 if (m->Start(g) == NO_MATCH) continue;
                 const int64 le = (int64)m->LeftEnd(g), re = (int64)m->RightEnd(g);

@@ -5,6 +5,7 @@
 
 #include "Aligner.h"
 #include "GuideTree.h"
+#include "MatchProjectionAdapter.h"
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -121,6 +122,53 @@ private:
     std::vector<int32_t> tree_left_, tree_right_;
     std::string input_tree_fn_, output_tree_fn_;
 };
+
+// projectIntervalList (alignmentProjector.cpp:68-70, multiEVD.cpp:142-172, bbBreakOnGenes.cpp:54) on the host, rules 1 to 3 of DESIGN.md
+// S19: the intervals in which every sequence of `projection` is present, each as a MatchProjectionAdapter onto those sequences (the
+// adapter owns a copy of the interval), inverted where the first projected sequence runs backwards, sorted by their left end in it and
+// grouped into maximal collinear runs; projected_adjs receives the runs' signed ends, adjacencies and weights (the residues of their
+// pieces).  The caller owns the adapters (Interval::SetMatches takes them over, and lays the bases between the pieces of a run out as
+// columns of their sequence alone: rule 4).  This is the brute-force check of HipProjection (Projection.h).
+inline void projectIntervalList(IntervalList &iv_list, std::vector<uint> &projection, std::vector<std::vector<MatchProjectionAdapter *>> &LCB_list, std::vector<LCB> &projected_adjs)
+{
+    LCB_list.clear(); projected_adjs.clear();
+    const std::vector<size_t> seq_map(projection.begin(), projection.end());
+    std::vector<MatchProjectionAdapter *> kept;
+    for (Interval &iv : iv_list) {
+        bool all = !projection.empty();
+        for (uint g : projection) all = all && g < iv.SeqCount() && iv.LeftEnd(g) != NO_MATCH;
+        if (!all) continue;
+        kept.push_back(new MatchProjectionAdapter(iv.Copy(), seq_map));
+        if (kept.back()->Orientation(0) == AbstractMatch::reverse) kept.back()->Invert();
+    }
+    std::vector<gnSeqI> bps;
+    IdentifyBreakpoints(kept, bps);
+    ComputeLCBs_v2(kept, bps, LCB_list);
+    const size_t K = LCB_list.size(); const uint N = (uint)projection.size();
+    projected_adjs.assign(K, LCB());
+    for (size_t l = 0; l < K; l++) {
+        LCB &b = projected_adjs[l];
+        b.lcb_id = (int)l;
+        b.left_end.assign(N, 0); b.right_end.assign(N, 0); b.left_adjacency.assign(N, NO_ADJACENCY); b.right_adjacency.assign(N, NO_ADJACENCY);
+        for (const MatchProjectionAdapter *m : LCB_list[l])
+            for (uint g = 0; g < N; g++) {
+                const int64 le = (int64)m->LeftEnd(g), re = (int64)m->RightEnd(g);
+                const bool rev = m->Start(g) < 0;
+                if (!b.left_end[g] || le < std::llabs(b.left_end[g])) b.left_end[g] = rev ? -le : le;
+                if (!b.right_end[g] || re > std::llabs(b.right_end[g])) b.right_end[g] = rev ? -re : re;
+                b.weight += (double)m->Length(g);
+            }
+    }
+    std::vector<size_t> idx(K);
+    for (uint g = 0; g < N; g++) {
+        for (size_t l = 0; l < K; l++) idx[l] = l;
+        std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return std::llabs(projected_adjs[a].left_end[g]) < std::llabs(projected_adjs[b].left_end[g]); });
+        for (size_t r = 0; r < K; r++) {
+            projected_adjs[idx[r]].left_adjacency[g] = r > 0 ? (int64)idx[r - 1] : NO_ADJACENCY;
+            projected_adjs[idx[r]].right_adjacency[g] = r + 1 < K ? (int64)idx[r + 1] : NO_ADJACENCY;
+        }
+    }
+}
 
 }  // namespace mems
 #endif

@@ -539,6 +539,48 @@ int mauve_excursions_core(mauve_ctx *ctx, const mauve_scoring *sc, int64_t n_gro
                           int64_t n_range, const int64_t *range_iv, const int64_t *range_col, const int64_t *range_len, int64_t *n_exc);
 int mauve_excursions_fetch(mauve_ctx *ctx, int64_t *height, int64_t *end_col, int64_t *stream_off, int64_t *tail /* n_stream*2 */);
 void mauve_excursion_thresholds(const int64_t *height, int64_t n, int64_t threshold[4], int64_t above[4]);
+/* ---- the alignment projected onto a subset of the genomes, what becomes collinear coalesced into new intervals: libMems'
+        projectIntervalList (alignmentProjector.cpp:58-77, multiEVD.cpp:142-172, bbBreakOnGenes.cpp:54) and the loop projectAndStrip writes
+        out by hand (projectAndStrip.cpp:75-122), on the coordinate index in force.  Frozen form DESIGN.md S19.  No genome data is read.
+        Request: proj[0..n_proj) distinct genome ids, 1 <= n_proj <= nseq of the index (P = their set); drop_empty.
+        (1) An interval is kept iff every genome of P is present in it; the others are dropped.  (2) A kept interval whose row proj[0] is
+        reversed is flipped: its columns are taken in descending order and the strand of every row of P is toggled, the ends stay, so by
+        S14's rule every column keeps its positions with the sign changed.  (3) The kept intervals are ordered by their left end in
+        proj[0]; two consecutive ones A, B are collinear iff for every other g of P they have the same strand in g (after 2) and, among
+        the kept intervals ordered by left end in g, B follows A directly (forward) or precedes it directly (reversed): the match_lcb
+        labels of mauve_lcb_chain(n_proj, K, 1..., the signed left ends in proj order, 0, 0).  An output interval is a maximal collinear
+        run; with n_proj = 1 everything kept is one run.  (4) Between two consecutive pieces A, B of a run, for k = 0..n_proj-1 in that
+        order, genome proj[k] receives one run of d filler columns with its bit alone, d = its bases strictly between A and B (contig
+        tables are not consulted): the output interval's ends are the least left and the greatest right end of its pieces and its columns
+        hold right - left + 1 residues of every genome of P.  (5) The output keeps the wide form: bit g of a column is bit g of the source
+        column for g in P, else 0; genomes outside P are absent from every output interval (left = right = 0).  With drop_empty the source
+        columns in which no genome of P has a residue are left out, else they stay as zero masks.  The projection is thus an alignment of
+        the same nseq: it can become the index in force and S14 to S18 run on it unchanged.  (6) Provenance: output interval o is made of
+        the source intervals src_iv[src_off[o] .. src_off[o+1]) in column order, src_flip[] tells which were flipped; src_col[] is every
+        output column's source column in the whole column array of the index, -1 for a filler column.
+        mauve_project computes the projection into device buffers of the context and keeps the small tables on the host; *sz (may be NULL):
+        output intervals, columns, source pieces (entries of src_iv), filler columns.  No kept interval, or an index of no intervals:
+        n_iv = 0, MAUVE_OK.
+        mauve_project_fetch writes it in the arrays of mauve_align_fetch: left / right / reverse [n_iv * nseq], col_off [n_iv + 1], cols
+        [n_cols], and src_off [n_iv + 1], src_iv / src_flip [n_src], src_col [n_cols].  With compact != 0 left / right / reverse are
+        [n_iv * n_proj] in proj order and bit k of a column is genome proj[k] (alignmentProjector's output).  Any pointer may be NULL;
+        page-locked destinations (mauve_host_alloc) are copied directly.  Nothing depends on the tiling: two calls return identical bytes.
+        mauve_project_index makes the projection the index in force without a column crossing the host link; it ends the extract selection
+        and the excursion result, as mauve_coord_index does; the projection stays fetchable.
+        MAUVE_ERR_ARG: n_proj outside [1, nseq], an id outside [0, nseq) or repeated.  MAUVE_ERR_STATE: no index; a fetch or
+        mauve_project_index without a projection; mauve_project_index when the projection is of another nseq than the context's or the
+        genomes were replaced after its index was built.  A call refused for these reasons leaves the index usable; once
+        mauve_project_index has begun the build, a failure of the build itself (MAUVE_ERR_LIMIT: the projection is too large for an index;
+        MAUVE_ERR_HIP) leaves the context without an index, as a failed mauve_coord_index* does.  A later mauve_project ends the earlier
+        projection whether it succeeds or not.  src_col is made by the first fetch that asks for it (from what the projection left on the
+        device: the index may have been replaced since); a caller who never asks never pays for it. ---- */
+typedef struct { int32_t n_proj; int32_t proj[MAUVE_MAX_SEQ]; int32_t drop_empty; } mauve_project_params;
+typedef struct { int64_t n_iv, n_cols, n_src, n_fill; } mauve_project_sizes;
+void mauve_default_project_params(int nseq, mauve_project_params *p);   /* every genome in order, drop_empty = 1 */
+int mauve_project(mauve_ctx *ctx, const mauve_project_params *p, mauve_project_sizes *sz);
+int mauve_project_fetch(mauve_ctx *ctx, int compact, int64_t *left, int64_t *right, int8_t *reverse, int64_t *col_off,
+                        uint32_t *cols, int64_t *src_off, int64_t *src_iv, int8_t *src_flip, int64_t *src_col);
+int mauve_project_index(mauve_ctx *ctx);
 /* ---- an alignment scored against a correct one: scoreAlignment <correct alignment> <calculated alignment> (scoreAlignment.cpp:99-457),
         counted on two coordinate indices.  Frozen form DESIGN.md S17.  T is the correct alignment, loaded by the first call below; C, the
         calculated one, is the coordinate index in force (S14); both are over the same nseq genomes and follow S14's position rule.  No

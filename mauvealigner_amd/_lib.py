@@ -38,6 +38,7 @@ EXPORTS = [
     "mauve_pair_stats", "mauve_pair_stats_identity", "mauve_pair_stats_sp_score",
     "mauve_score_truth", "mauve_score_alignment", "mauve_score_totals_from",
     "mauve_excursions_pairs", "mauve_excursions_core", "mauve_excursions_fetch", "mauve_excursion_thresholds",
+    "mauve_default_project_params", "mauve_project", "mauve_project_fetch", "mauve_project_index",
 ]
 
 
@@ -62,6 +63,14 @@ class HmmParams(C.Structure):
 
 class ExtractParams(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("keep", C.c_int32 * 32), ("require", C.c_uint32), ("drop_empty", C.c_int32), ("polymorphic", C.c_int32)]
+
+
+class ProjectParams(C.Structure):
+    _fields_ = [("n_proj", C.c_int32), ("proj", C.c_int32 * 32), ("drop_empty", C.c_int32)]
+
+
+class ProjectSizes(C.Structure):
+    _fields_ = [("n_iv", C.c_int64), ("n_cols", C.c_int64), ("n_src", C.c_int64), ("n_fill", C.c_int64)]
 
 
 class AlignSizes(C.Structure):
@@ -103,6 +112,15 @@ def load():
     L.mauve_align_prefetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
     return L
+
+
+def default_project_params(nseq):
+    """mauve_default_project_params (host only): every genome in order, drop_empty = 1"""
+    p = ProjectParams()
+    L = load()
+    L.mauve_default_project_params.restype = None
+    L.mauve_default_project_params(C.c_int(nseq), C.byref(p))
+    return p
 
 
 def _p(a, t):
@@ -1026,6 +1044,61 @@ class Context:
         arrs = [self._co_out(out, q, shapes[q], np.int64) if want[q] else None for q in range(4)]
         self._chk(self.L.mauve_excursions_fetch(self.h, *[_p(a, C.c_int64) if a is not None and a.size else None for a in arrs]), "mauve_excursions_fetch")
         return tuple(arrs)
+
+    # ---- projection onto a genome subset ----
+    def project(self, proj=None, drop_empty=True):
+        """mauve_project: the index in force projected onto the genomes proj (None = every genome in order), collinear intervals coalesced;
+        the result stays in the context for project_fetch / project_index.  -> dict(n_iv, n_cols, n_src, n_fill)"""
+        N = self.coord_index_size()[0]
+        p = default_project_params(N)
+        if proj is not None:
+            proj = [int(g) for g in proj]
+            if len(proj) > 32:
+                raise ValueError("project: at most 32 genomes")
+            p.n_proj = len(proj)
+            for k, g in enumerate(proj):
+                p.proj[k] = g
+        p.drop_empty = int(bool(drop_empty))
+        sz = ProjectSizes()
+        self._pj_shape = None
+        self._chk(self.L.mauve_project(self.h, C.byref(p), C.byref(sz)), "mauve_project")
+        self._pj_shape = (N, p.n_proj, sz.n_iv, sz.n_cols, sz.n_src)
+        return {k: getattr(sz, k) for k, _ in ProjectSizes._fields_}
+
+    PROJECT_ARRAYS = ("left", "right", "reverse", "col_off", "cols", "src_off", "src_iv", "src_flip", "src_col")
+
+    def project_fetch(self, compact=False, out=None, want=None):
+        """mauve_project_fetch of the projection in force -> dict of left, right, reverse [n_iv, nseq] (compact: [n_iv, n_proj], bit k of a
+        column = genome proj[k]), col_off, cols, src_off, src_iv, src_flip, src_col; out = dict of destination arrays (e.g. from
+        pinned_empty: copied without staging); want: the names to copy (None = all; the others are None)"""
+        shape = getattr(self, "_pj_shape", None)
+        if shape is None:                                        # no result: the library says so (nothing is written)
+            self._chk(self.L.mauve_project_fetch(self.h, 0, *([None] * 9)), "mauve_project_fetch")
+            raise RuntimeError("mauve_project_fetch ran without a projection")
+        N, npj, n_iv, n_cols, n_src = shape
+        w = npj if compact else N
+        spec = {"left": ((n_iv, w), np.int64), "right": ((n_iv, w), np.int64), "reverse": ((n_iv, w), np.int8), "col_off": ((n_iv + 1,), np.int64),
+                "cols": ((n_cols,), np.uint32), "src_off": ((n_iv + 1,), np.int64), "src_iv": ((n_src,), np.int64), "src_flip": ((n_src,), np.int8),
+                "src_col": ((n_cols,), np.int64)}
+        res, args = {}, []
+        for name in self.PROJECT_ARRAYS:
+            shp, dt = spec[name]
+            if want is not None and name not in want:
+                res[name] = None
+                args.append(None)
+                continue
+            a = out[name] if out is not None and name in out else np.zeros(shp, dt)
+            if a.dtype != np.dtype(dt) or a.shape != shp or not a.flags.c_contiguous:
+                raise ValueError("project_fetch: out[%r] must be a contiguous %s array of shape %s" % (name, np.dtype(dt).name, shp))
+            res[name] = a
+            args.append(C.c_void_p(a.ctypes.data) if a.size else None)
+        self.L.mauve_project_fetch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        self._chk(self.L.mauve_project_fetch(self.h, int(bool(compact)), *args), "mauve_project_fetch")
+        return res
+
+    def project_index(self):
+        """mauve_project_index: the projection in force becomes the index in force (its columns stay on the device)"""
+        self._chk(self.L.mauve_project_index(self.h), "mauve_project_index")
 
     # ---- an alignment scored against a correct one (DESIGN.md S17) ----
     def score_truth(self, aln):

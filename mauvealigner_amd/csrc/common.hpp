@@ -292,6 +292,18 @@ struct mauve_ctx {
     // index and the genomes it was made on (an index call clears `valid`, genome_gen tells an upload)
     struct Excursions { bool valid = false; uint64_t genome_gen = 0; int64_t n_stream = 0, n_exc = 0; } exc;
     DevBuf exc_work, exc_tmp, exc_meta, exc_rec;   // the flag word, ranges, their chunks' scan, the sets; per-chunk arrays; stream_off | tail; height | end_col
+    // projection onto a genome subset (project_dev.hip): the result of the last call -- columns and the work area their source columns are made from on the
+    // device, the interval tables and the provenance on the host -- stays for its fetches and for mauve_project_index; genome_gen is that of
+    // the index it was made from
+    struct Projection {
+        bool valid = false; uint64_t genome_gen = 0;
+        int N = 0, n_proj = 0, drop_empty = 1; int32_t proj[MAUVE_MAX_SEQ] = {0};
+        int64_t n_iv = 0, n_cols = 0, n_fill = 0, n_piece = 0, n_unit = 0;      // n_piece, n_unit: the shape of the work area pj_work keeps
+        bool have_src = false;               // pj_src holds the source columns (made by the first fetch that asks for them)
+        std::vector<int64_t> left, right, col_off, src_off, src_iv;
+        std::vector<int8_t> reverse, src_flip;
+    } pj;
+    DevBuf pj_work, pj_cols, pj_src, pj_out;   // the flag word, pieces, unit counts, their scan and kept words (stays with the result); the columns; their source columns, once asked for; the compact form of a fetch
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them
     DevBuf rec_genomes, rec_seg;         // recursive anchoring: gap sub-sequences + segment table
@@ -544,6 +556,9 @@ bool fetch_compact_direct(mauve_ctx *c, int col_bytes, int32_t *mum_length, int3
 // device tail of mauve_align: the two bulk tables start for the buffers mauve_align_prefetch named (assemble_dev.hip)
 int prefetch_tables_enqueue(mauve_ctx *c, int N, int64_t na, const int32_t *alen, const int32_t *ast, const int32_t *alcb);
 bool fetch_tables_direct(mauve_ctx *c, int64_t *mum_length, int64_t *mum_start, int64_t *anchor_length, int64_t *anchor_start, int64_t *anchor_lcb, int *rc_out);
+// coord_dev.hip: the index in force from device columns and a host interval table (mauve_project_index)
+int coord_index_device(mauve_ctx *c, const char *who, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off,
+                       const uint32_t *d_cols);
 bool host_pointer_is_pinned(const void *p);
 // device -> caller on the context's stream: a page-locked destination directly (queued: the caller synchronises), a pageable one through `pin`
 // in pieces of 64 MiB, each waited for

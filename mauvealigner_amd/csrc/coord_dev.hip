@@ -325,6 +325,13 @@ int coord_index_arrays(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, 
     return coord_build_index(c, who, X, index, nseq, n_iv, left, right, reverse, col_off, c->bb_cols.as<uint32_t>());
 }
 
+// The index in force from columns that are on the device already and an interval table on the host (project_dev.hip)
+int coord_index_device(mauve_ctx *c, const char *who, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off,
+                       const uint32_t *d_cols)
+{
+    return coord_build_index(c, who, c->co, c->co_index, nseq, n_iv, left, right, reverse, col_off, d_cols);
+}
+
 extern "C" {
 
 int mauve_coord_index(mauve_ctx *c)
