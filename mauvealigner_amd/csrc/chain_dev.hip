@@ -5,7 +5,7 @@
 // Shape: the list is a few 10^4 .. 10^5 records and the elimination is a chain of dependent passes (genome after
 // genome, pass after pass).  The passes of one genome decompose into independent overlap clusters (see
 // ch_cluster_pass), and the clusters can be cut from the list as it ENTERS the stage, for every genome alike: the
-// orders of all genomes (one batched radix sort, seed_pass.hip), the prefix maxima of the right ends and the cluster
+// orders of all genomes (one batched radix sort, radix_sort.hip), the prefix maxima of the right ends and the cluster
 // starts are made up front in launches with a genome dimension, and a genome's turn is ONE launch -- one thread per
 // cluster for ALL its passes -- with no launch per pass and no host round trip.  The LCB graph (collinear runs in genome-0
 // order, their weights, the per-genome neighbour lists) is built by flag compactions; the greedy breakpoint

@@ -2091,7 +2091,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
 // ~1 us of pointer chasing per gap and genome, 2 ms at C3 for 0.6 ms of DP kernel).  Here the anchors go up once
 // (flat int32 records in chain order) and kernels do the rest: gap of every anchor pair -> which gaps are aligned ->
 // their descriptors, traceback / parked-row needs and step estimates -> offsets by tiled scans -> the launch order by
-// two stable radix passes of seed_pass.hip (size class, then kernel class).  One small read-back (totals, and the gap
+// two stable radix passes of radix_sort.hip (size class, then kernel class).  One small read-back (totals, and the gap
 // code of every anchor for the assembly) sizes the buffers; the DP kernels and their result layout are unchanged.
 // ================================================================================================================
 namespace {

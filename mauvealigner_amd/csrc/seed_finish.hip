@@ -10,7 +10,7 @@
 // ------------------------------------------------------------------------------------------------
 // canonical order on the device (large candidate sets): key = first component << pos_bits | |its start| per candidate
 // (pos_bits = bits of the longest genome: fewer radix passes than a fixed 32)
-// (dropped candidates get first component = nseq and sort behind everything), the radix sort of seed_pass.hip on
+// (dropped candidates get first component = nseq and sort behind everything), the radix sort of radix_sort.hip on
 // (key, candidate index), then a gather of the surviving records as int64 in sorted order.
 // ------------------------------------------------------------------------------------------------
 // guide tree (progressive.cpp): all it needs of the pairwise matches is the sum of their lengths per genome pair -- no

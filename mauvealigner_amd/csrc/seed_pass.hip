@@ -1,6 +1,6 @@
 // seed_pass.hip -- the seed pass of the hot path on gfx950:
 //   seed_extract  : 2-bit packed genomes -> (canonical masked mer, global position | strand)
-//   rs_*          : LSD radix sort of the pairs (the sorted mer list of all genomes at once)
+//   (radix_sort.hip: LSD radix sort of the pairs -- the sorted mer list of all genomes at once)
 //   mum_join      : runs of identical mers -> seed hits by the MatchFinder subclass rule
 //   mum_candidates / mum_extend : ungapped extension of every hit into its maximal match
 //
@@ -15,7 +15,7 @@
 // the scatter, wave64 ballots for ranking and for the extension walk.  No MFMA by design.
 #include "common.hpp"
 #include "dev_scan.hpp"
-#include "small_sort.hpp"
+#include "radix_sort.hpp"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -31,26 +31,15 @@ __device__ __forceinline__ uint64_t bits_from128(uint64_t lo, uint64_t hi, int s
     else v = start ? ((lo >> start) | (hi << (64 - start))) : lo;
     return nbits >= 64 ? v : (v & ((1ULL << nbits) - 1ULL));
 }
-
-// K' of the window starting at base p of the genome whose packed words start at G
-__device__ __forceinline__ uint64_t kprime_at(const uint64_t *__restrict__ G, uint32_t p, const SeedShape &sh)
-{
-    uint32_t q = p >> 5; int r = (p & 31) * 2;
-    uint64_t w0 = G[q], w1 = G[q + 1], w2 = G[q + 2];
-    uint64_t lo = r ? ((w0 >> r) | (w1 << (64 - r))) : w0;
-    uint64_t hi = r ? ((w1 >> r) | (w2 << (64 - r))) : w1;
-    uint64_t k = 0;
-    for (int i = 0; i < sh.nruns; i++)
-        k |= bits_from128(lo, hi, sh.run_src[i], sh.run_bits[i]) << sh.run_dst[i];
-    return k;
-}
+// bits [r, r + 64) of the word pair w1:w0, r < 64
+__device__ __forceinline__ uint64_t funnel64(uint64_t w0, uint64_t w1, int r) { return r ? ((w0 >> r) | (w1 << (64 - r))) : w0; }
 
 // placed-base bitmap: is any of the `span` bases from p on already placed?
 __device__ __forceinline__ bool window_masked(const uint64_t *__restrict__ M, uint32_t p, int span)
 {
     const uint32_t q = p >> 6; const int r = p & 63;
     const uint64_t m0 = M[q], m1 = M[q + 1];
-    const uint64_t v = r ? ((m0 >> r) | (m1 << (64 - r))) : m0;
+    const uint64_t v = r ? ((m0 >> r) | (m1 << (64 - r))) : m0;      // (written out: through funnel64, valid_count compiles to 16 VGPRs instead of 12)
     return (v & ((span >= 64) ? ~0ULL : ((1ULL << span) - 1ULL))) != 0;
 }
 
@@ -63,18 +52,6 @@ __device__ __forceinline__ bool window_blocked(const uint64_t *__restrict__ VM, 
     if (VM) b = window_masked(VM, p, span);
     if (CM && span > 1) b |= window_masked(CM, p + 1, span - 1);
     return b;
-}
-
-// narrow form (span <= 32, weight <= 16): the window is one 64-bit word and K' fits 32 bits
-__device__ __forceinline__ uint32_t kprime_narrow(const uint64_t *__restrict__ G, uint32_t p, const SeedShape &sh)
-{
-    const uint32_t q = p >> 5; const int r = (p & 31) * 2;
-    const uint64_t w0 = G[q], w1 = G[q + 1];
-    const uint64_t lo = r ? ((w0 >> r) | (w1 << (64 - r))) : w0;
-    uint32_t k = 0;
-    for (int i = 0; i < sh.nruns; i++)
-        k |= ((uint32_t)(lo >> sh.run_src[i]) & ((1u << sh.run_bits[i]) - 1u)) << sh.run_dst[i];
-    return k;
 }
 
 __device__ __forceinline__ uint32_t digit_reverse32(uint32_t k, int weight)
@@ -95,6 +72,39 @@ __device__ __forceinline__ uint64_t digit_reverse(uint64_t k, int weight)
     uint64_t x = __brevll(k) >> (64 - 2 * weight);
     return ((x & 0xAAAAAAAAAAAAAAAAULL) >> 1) | ((x & 0x5555555555555555ULL) << 1);
 }
+
+// The canonical mer of a window, in the two steps every extraction site shares.  NARROW (seed_narrow): the window is one 64-bit word and
+// K' fits 32 bits, so the arithmetic is 32-bit; otherwise the window is a 128-bit digit string.
+__host__ __device__ inline bool seed_narrow(const SeedShape &sh) { return sh.span <= 32 && sh.weight <= 15; }
+struct WinDigits { uint64_t lo, hi; };      // (hi: unused when NARROW)
+struct MerKey { uint64_t key; uint32_t strand; };
+// 1. the digit string of the window starting at base p of the genome whose packed words start at G
+template <bool NARROW>
+__device__ __forceinline__ WinDigits window_digits(const uint64_t *__restrict__ G, uint32_t p)
+{
+    const uint32_t q = p >> 5; const int r = (p & 31) * 2;
+    const uint64_t w0 = G[q], w1 = G[q + 1], w2 = NARROW ? 0ULL : G[q + 2];
+    return {funnel64(w0, w1, r), NARROW ? 0ULL : funnel64(w1, w2, r)};
+}
+// 2. K' = the seed's runs of digits, packed; forward mer = digit reverse of K', reverse mer = ~K' (masked).  The smaller one is the key,
+// strand = 1 when that is the reverse mer (a mer that is its own reverse complement: strand 0).
+template <bool NARROW>
+__device__ __forceinline__ MerKey canonical_mer(const WinDigits &d, const SeedShape &sh)
+{
+    if constexpr (NARROW) {
+        uint32_t kp = 0;
+        for (int i = 0; i < sh.nruns; i++) kp |= ((uint32_t)(d.lo >> sh.run_src[i]) & ((1u << sh.run_bits[i]) - 1u)) << sh.run_dst[i];
+        const uint32_t f = digit_reverse32(kp, sh.weight), r = (~kp) & (uint32_t)sh.keymask;
+        return {r < f ? r : f, r < f};
+    } else {
+        uint64_t kp = 0;
+        for (int i = 0; i < sh.nruns; i++) kp |= bits_from128(d.lo, d.hi, sh.run_src[i], sh.run_bits[i]) << sh.run_dst[i];
+        const uint64_t f = digit_reverse(kp, sh.weight), r = (~kp) & sh.keymask;
+        return {r < f ? r : f, r < f};
+    }
+}
+template <bool NARROW>
+__device__ __forceinline__ MerKey mer_at(const uint64_t *__restrict__ G, uint32_t p, const SeedShape &sh) { return canonical_mer<NARROW>(window_digits<NARROW>(G, p), sh); }
 
 // genome of a global window index.  gpos_off[i] for i > nseq is all ones (build_tab), so up to eight genomes need no
 // loop: seven compares against values the scalar unit loads once per kernel.
@@ -141,6 +151,13 @@ __device__ __forceinline__ uint32_t seg_of(const uint32_t *__restrict__ segs, ui
     while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (segs[mid] <= p) lo = mid; else hi = mid; }
     return lo;
 }
+// the segment rule: does the window at base p of genome g lie inside one segment?  *id: the segment p is in (it rides above the mer in the key)
+__device__ __forceinline__ bool window_segment(const uint32_t *__restrict__ seg, uint32_t nseg, int g, uint32_t p, int span, uint32_t *id)
+{
+    const uint32_t *sg = seg + (size_t)g * (nseg + 1);
+    const uint32_t k = *id = seg_of(sg, nseg, p);
+    return p + span <= sg[k + 1];
+}
 
 template <typename KeyT, bool SEG, typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) seed_extract(const uint64_t *__restrict__ packed, GenomeTab tab,
@@ -151,37 +168,19 @@ __global__ void __launch_bounds__(256) seed_extract(const uint64_t *__restrict__
     uint32_t n = tab.nwin[g];
     const uint64_t *G = packed + tab.word_off[g];
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
-        uint64_t kp = kprime_at(G, p, sh);
-        uint64_t f = digit_reverse(kp, sh.weight);
-        uint64_t r = (~kp) & sh.keymask;
-        uint32_t s = r < f;
-        uint64_t key = s ? r : f;
+        const MerKey m = mer_at<false>(G, p, sh);
+        uint64_t key = m.key;
         if (SEG) {
-            const uint32_t *sg = seg + (size_t)g * (nseg + 1);
-            uint32_t k = seg_of(sg, nseg, p);
-            key = (p + sh.span <= sg[k + 1]) ? (((uint64_t)k << (2 * sh.weight)) | key) : ~0ULL;
+            uint32_t k;
+            key = window_segment(seg, nseg, g, p, sh.span, &k) ? (((uint64_t)k << (2 * sh.weight)) | key) : ~0ULL;
         }
         keys[out_base + p] = (KeyT)key;
-        vals[out_base + p] = win_make<ValT>(tab.gpos_off[g] + p, s);
+        vals[out_base + p] = win_make<ValT>(tab.gpos_off[g] + p, m.strand);
     }
 }
 
 // All genomes in one launch, tiled exactly like the radix sort (4096 windows per workgroup), with the digit
 // histogram of the first sort pass accumulated on the way out: saves two launches and one re-read of the keys.
-// K' of a window given as a 128-bit digit string (the run loop of kprime_at / kprime_narrow)
-__device__ __forceinline__ uint64_t kprime_of(uint64_t lo, uint64_t hi, const SeedShape &sh)
-{
-    uint64_t k = 0;
-    for (int i = 0; i < sh.nruns; i++) k |= bits_from128(lo, hi, sh.run_src[i], sh.run_bits[i]) << sh.run_dst[i];
-    return k;
-}
-__device__ __forceinline__ uint32_t kprime_of32(uint64_t lo, const SeedShape &sh)
-{
-    uint32_t k = 0;
-    for (int i = 0; i < sh.nruns; i++) k |= ((uint32_t)(lo >> sh.run_src[i]) & ((1u << sh.run_bits[i]) - 1u)) << sh.run_dst[i];
-    return k;
-}
-
 template <typename KeyT, bool SEG, bool NARROW, typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh,
                                                         KeyT *__restrict__ keys, ValT *__restrict__ vals, uint32_t P,
@@ -214,17 +213,8 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 const int r = r0 + 2 * j;                                             // 0 .. 68
                 uint64_t a0 = w0, a1 = w1, a2 = w2; int rr = r;
                 if (r >= 64) { a0 = w1; a1 = w2; a2 = w3; rr = r - 64; }
-                const uint64_t lo = rr ? ((a0 >> rr) | (a1 << (64 - rr))) : a0;
-                if (NARROW) {
-                    const uint32_t kp = kprime_of32(lo, sh);
-                    const uint32_t f = digit_reverse32(kp, sh.weight), rv = (~kp) & (uint32_t)sh.keymask;
-                    sf[j] = rv < f; key[j] = sf[j] ? rv : f;
-                } else {
-                    const uint64_t hi = rr ? ((a1 >> rr) | (a2 << (64 - rr))) : a1;
-                    const uint64_t kp = kprime_of(lo, hi, sh);
-                    const uint64_t f = digit_reverse(kp, sh.weight), rv = (~kp) & sh.keymask;
-                    sf[j] = rv < f; key[j] = sf[j] ? rv : f;
-                }
+                const MerKey m = canonical_mer<NARROW>({funnel64(a0, a1, rr), NARROW ? 0ULL : funnel64(a1, a2, rr)}, sh);
+                key[j] = m.key; sf[j] = m.strand;
             }
         } else {
 #pragma unroll
@@ -233,16 +223,8 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 key[j] = ~0ULL; sf[j] = 0;
                 if (gp >= P) continue;
                 const int g = genome_of(gp, tab);
-                const uint32_t p = gp - tab.gpos_off[g];
-                if (NARROW) {
-                    const uint32_t kp = kprime_narrow(packed + tab.word_off[g], p, sh);
-                    const uint32_t f = digit_reverse32(kp, sh.weight), rv = (~kp) & (uint32_t)sh.keymask;
-                    sf[j] = rv < f; key[j] = sf[j] ? rv : f;
-                } else {
-                    const uint64_t kp = kprime_at(packed + tab.word_off[g], p, sh);
-                    const uint64_t f = digit_reverse(kp, sh.weight), rv = (~kp) & sh.keymask;
-                    sf[j] = rv < f; key[j] = sf[j] ? rv : f;
-                }
+                const MerKey m = mer_at<NARROW>(packed + tab.word_off[g], gp - tab.gpos_off[g], sh);
+                key[j] = m.key; sf[j] = m.strand;
             }
         }
         if (SEG || vmask || cmask) {
@@ -253,9 +235,8 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 const int g = together ? g0 : genome_of(gp, tab);
                 const uint32_t p = gp - tab.gpos_off[g];
                 if (SEG) {
-                    const uint32_t *sg = seg + (size_t)g * (nseg + 1);
-                    const uint32_t k = seg_of(sg, nseg, p);
-                    key[j] = (p + sh.span <= sg[k + 1]) ? (((uint64_t)k << (2 * sh.weight)) | key[j]) : ~0ULL;
+                    uint32_t k;
+                    key[j] = window_segment(seg, nseg, g, p, sh.span, &k) ? (((uint64_t)k << (2 * sh.weight)) | key[j]) : ~0ULL;
                 }
                 if ((vmask || cmask) && window_blocked(vmask ? vmask + tab.mask_off[g] : nullptr, cmask ? cmask + tab.mask_off[g] : nullptr, p, sh.span)) key[j] = ~0ULL;
             }
@@ -284,11 +265,6 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
     __syncthreads();
     hist[threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
 }
-
-// ------------------------------------------------------------------------------------------------
-// radix sort (LSD, 8-bit digits, stable): histogram / row scan / scatter per pass
-// ------------------------------------------------------------------------------------------------
-// (block_excl_scan: small_sort.hpp)
 
 // ------------------------------------------------------------------------------------------------
 // Masked seed passes (guide-tree nodes below the root, LCB extension): most windows touch a masked base and
@@ -346,145 +322,10 @@ __global__ void __launch_bounds__(256) seed_extract_compact(const uint64_t *__re
         if (!(ok >> i & 1)) continue;
         const uint32_t gp = first + i;
         const int g = genome_of(gp, tab);
-        const uint32_t p = gp - tab.gpos_off[g];
-        uint64_t key; uint32_t s;
-        if (NARROW) {
-            const uint32_t kp = kprime_narrow(packed + tab.word_off[g], p, sh);
-            const uint32_t f = digit_reverse32(kp, sh.weight), r = (~kp) & (uint32_t)sh.keymask;
-            s = r < f; key = s ? r : f;
-        } else {
-            const uint64_t kp = kprime_at(packed + tab.word_off[g], p, sh);
-            const uint64_t f = digit_reverse(kp, sh.weight), r = (~kp) & sh.keymask;
-            s = r < f; key = s ? r : f;
-        }
-        keys[o] = (KeyT)key; vals[o] = win_make<ValT>(gp, s);
+        const MerKey m = mer_at<NARROW>(packed + tab.word_off[g], gp - tab.gpos_off[g], sh);
+        keys[o] = (KeyT)m.key; vals[o] = win_make<ValT>(gp, m.strand);
         o++;
     }
-}
-
-constexpr int RS_ITEMS = 16;                     // (RS_THREADS, the tile ranking rs_scatter_tile: small_sort.hpp)
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;   // 4096 keys per workgroup
-
-template <typename KeyT>
-__global__ void __launch_bounds__(RS_THREADS) rs_hist(const KeyT *__restrict__ keys, uint32_t n, int shift,
-                                                      uint32_t *__restrict__ hist, uint32_t nblk)
-{
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * RS_TILE;
-    if (base + RS_TILE <= n) {
-        // full tile: 16-byte loads, no predication (the order inside a tile does not matter for a histogram)
-        constexpr int KPV = 16 / (int)sizeof(KeyT);
-        struct alignas(16) Vec { KeyT k[KPV]; };
-        const Vec *src = reinterpret_cast<const Vec *>(keys + base);
-#pragma unroll
-        for (int i = 0; i < RS_ITEMS / KPV; i++) {
-            const Vec q = src[i * RS_THREADS + threadIdx.x];
-#pragma unroll
-            for (int j = 0; j < KPV; j++) atomicAdd(&h[(uint32_t)(q.k[j] >> shift) & 255u], 1u);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < RS_ITEMS; i++) {
-            const uint32_t idx = base + i * RS_THREADS + threadIdx.x;
-            if (idx < n) atomicAdd(&h[(uint32_t)(keys[idx] >> shift) & 255u], 1u);
-        }
-    }
-    __syncthreads();
-    hist[threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
-}
-
-// block d: exclusive scan of row d (length nblk) in place, row total -> totals[d]
-// (a wave per quarter of the digit's row, 64 consecutive counts per step -- coalesced loads, a DPP prefix sum, one carry -- instead of a thread per 24
-// consecutive counts walking them twice with loads 96 bytes apart: 17 -> 6 us per launch at C3's 6 104 tiles)
-__device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)v, 0x111, 0xf, 0xf, false); v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)v, 0x112, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)v, 0x114, 0xf, 0xf, false); v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)v, 0x118, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)v, 0x142, 0xa, 0xf, false); v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-__global__ void __launch_bounds__(256) rs_rowscan(uint32_t *__restrict__ hist, uint32_t nblk,
-                                                  uint32_t *__restrict__ totals)
-{
-    __shared__ uint32_t part[4];                             // (launched with 256 threads: four waves, a quarter of the row each)
-    uint32_t *row = hist + (size_t)blockIdx.x * nblk;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t seg = (((nblk + 3) / 4) + 63) & ~63u;           // counts per wave, whole steps of 64
-    const uint32_t lo = min((uint32_t)wv * seg, nblk), hi = min(lo + seg, nblk);
-    // (eight steps' loads in flight at a time: a loop that waits for one load per step is a chain of L2 latencies, 24 of them at C3)
-    uint32_t s = 0;
-    for (uint32_t i0 = lo; i0 < hi; i0 += 512) {
-        uint32_t v[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) { const uint32_t idx = i0 + q * 64 + lane; v[q] = idx < hi ? row[idx] : 0u; }
-#pragma unroll
-        for (int q = 0; q < 8; q++) s += v[q];
-    }
-    s = wave_incl_sum_u32(s);
-    if (lane == 63) part[wv] = s;
-    __syncthreads();
-    uint32_t run = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { const uint32_t c = part[w]; if (w < wv) run += c; total += c; }
-    for (uint32_t i0 = lo; i0 < hi; i0 += 512) {
-        uint32_t v[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) { const uint32_t idx = i0 + q * 64 + lane; v[q] = idx < hi ? row[idx] : 0u; }
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const uint32_t idx = i0 + q * 64 + lane;
-            const uint32_t inc = wave_incl_sum_u32(v[q]);
-            if (idx < hi) row[idx] = run + inc - v[q];
-            run += (uint32_t)__builtin_amdgcn_readlane((int32_t)inc, 63);
-        }
-    }
-    if (threadIdx.x == 0) totals[blockIdx.x] = total;
-}
-
-// RAW: `hist` holds the raw per-tile digit counts (no rs_rowscan ran): every workgroup sums its digit's row for itself --
-// the sorts of the chain / DP front / canonical order have at most a few dozen tiles, where the row scan is one more
-// launch of pure latency.
-// LDS per workgroup (RS_TILE = 4096): keys + values + 7 KiB of counters -- 39 KiB for 4 + 4 bytes, 55 KiB for 8 + 4 or 4 + 8, 71 KiB for 8 + 8
-// (the wide pass with 64-bit keys): 4, 2, 2 workgroups per compute unit of 160 KiB.
-template <typename KeyT, bool RAW = false, typename ValT = uint32_t>
-__global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict__ keys_in,
-                                                         const ValT *__restrict__ vals_in,
-                                                         KeyT *__restrict__ keys_out,
-                                                         ValT *__restrict__ vals_out, uint32_t n, int shift,
-                                                         const uint32_t *__restrict__ hist,
-                                                         const uint32_t *__restrict__ totals, uint32_t nblk)
-{
-    __shared__ KeyT s_keys[RS_TILE];
-    __shared__ ValT s_vals[RS_TILE];
-    __shared__ uint32_t wcount[RS_WAVES][256];
-    __shared__ uint32_t gbase[256];       // global output index of this tile's first key of digit d
-    __shared__ uint32_t tstart[256];      // tile-local start of digit d
-    __shared__ uint32_t scan[256];
-
-    const int tid = threadIdx.x;
-    const uint32_t tile_base = blockIdx.x * RS_TILE;
-    const uint32_t tile_n = min((uint32_t)RS_TILE, n - tile_base);
-
-    for (int w = 0; w < RS_WAVES; w++) wcount[w][tid] = 0;
-    // digit base = exclusive scan of the digit totals
-    if (RAW) {
-        const uint32_t *row = hist + (size_t)tid * nblk;
-        uint32_t tot = 0, before = 0;
-        for (uint32_t t = 0; t < nblk; t++) { const uint32_t c = row[t]; tot += c; before += t < blockIdx.x ? c : 0u; }
-        uint32_t dummy;
-        gbase[tid] = block_excl_scan(tot, &dummy, scan) + before;
-    } else {
-        uint32_t dummy;
-        const uint32_t tot = totals[tid];
-        gbase[tid] = block_excl_scan(tot, &dummy, scan) + hist[(size_t)tid * nblk + blockIdx.x];
-    }
-    __syncthreads();
-    if (tile_n == RS_TILE)
-        rs_scatter_tile<KeyT, RS_ITEMS, true, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
-    else
-        rs_scatter_tile<KeyT, RS_ITEMS, false, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -498,6 +339,13 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict_
 //   MODE_UNIQUE : UniqueMatchFinder.cpp:44-58 -- genomes with more than one copy are dropped, >= 2 stay
 // A position carries at most one mer, so at most one hit is anchored at it: no atomics, no compaction.
 // ------------------------------------------------------------------------------------------------
+// the finder's rule for one mer: once / multi = the genomes that hold it at all / more than once.  The component set, or 0 for no hit
+__device__ __forceinline__ uint32_t finder_components(int mode, uint32_t once, uint32_t multi, uint32_t want_mask)
+{
+    const uint32_t m = once & ~multi;
+    const bool repeat_kills = (mode == MAUVE_MODE_MEM) & (multi != 0), too_few = __popc(m) < 2, other_set = (want_mask != 0) & (m != want_mask);
+    return (repeat_kills | too_few | other_set) ? 0u : m;      // (no short circuit: the joins apply the rule to a dozen rows without a branch)
+}
 // entry i of a sorted list of n entries (the whole list, or one slice join_hash handed back)
 template <typename KeyT, bool SEG, typename ValT>
 __device__ __forceinline__ void mum_join_at(const KeyT *__restrict__ keys, const ValT *__restrict__ vals, uint32_t n, uint32_t i,
@@ -516,10 +364,8 @@ __device__ __forceinline__ void mum_join_at(const KeyT *__restrict__ keys, const
         multi |= once & bit; once |= bit; j++;
         if (mode == MAUVE_MODE_MEM && multi) return;   // MemHash: a repeat kills the seed, no need to finish the run
     }
-    const uint32_t m = once & ~multi;
-    if (mode == MAUVE_MODE_MEM && multi) return;
-    if (__popc(m) < 2) return;
-    if (want_mask && m != want_mask) return;
+    const uint32_t m = finder_components(mode, once, multi, want_mask);
+    if (!m) return;
     // entries of a run are in ascending global position (stable sort), so the anchor comes first
     uint32_t ap = 0xFFFFFFFFu;
     for (uint32_t t = i; t < j; t++) {
@@ -570,7 +416,7 @@ __global__ void __launch_bounds__(256) mum_join_slices(const KeyT *__restrict__ 
 // or after c*HJ_T (chunk_bound; two waves look the two edges up side by side).  A range longer than the
 // HJ_CAP entries its table takes (a bucket blown up by a repeat family or low-complexity sequence) is not processed:
 // it goes to the overflow list and the host gives that slice to the full sort and the serial join below
-// (rs_* + mum_join), which have no size limit.
+// (rs_* of radix_sort.hip + mum_join), which have no size limit.
 // Slot = {mer (later the anchor's value), once | multi << 16 genome sets}; 4096 slots, at most 3072 entries (load <= 0.75).
 // ------------------------------------------------------------------------------------------------
 constexpr int HJ_T = 2048;                   // nominal entries per workgroup
@@ -619,6 +465,28 @@ __global__ void __launch_bounds__(256) join_bounds(const KeyT *__restrict__ keys
     if ((threadIdx.x & 63) == 0) bound[c] = res;
 }
 
+// Grouping by mer in an LDS table of SLOTS slots (join_hash, tiny_join).  group_claim: the key's slot, claimed from slot s on (compare-and-swap
+// on the key word, linear probing).  group_note: OR the entry's genome bit into that slot's once / multi sets; multi is the high half of som's
+// word, or -- WIDE, more than 16 genomes -- the word of som2.  (Two steps: join_hash takes the genome from the entry's value between
+// them, so the wait for that load stays behind the claim loop.)
+template <typename KeyT, int SLOTS>
+__device__ __forceinline__ uint32_t group_claim(KeyT *skey, KeyT key, uint32_t s)
+{
+    constexpr KeyT EMPTY = (KeyT)~0ULL;
+    for (;;) {
+        const KeyT old = atomicCAS(&skey[s], EMPTY, key);
+        if (old == EMPTY || old == key) break;
+        s = (s + 1) & (SLOTS - 1);
+    }
+    return s;
+}
+template <bool WIDE>
+__device__ __forceinline__ void group_note(uint32_t *som, uint32_t *som2, uint32_t s, uint32_t bit)
+{
+    const uint32_t old = atomicOr(&som[s], bit);
+    if (old & bit) { if (WIDE) atomicOr(&som2[s], bit); else atomicOr(&som[s], bit << 16); }
+}
+
 // (ValT = uint64_t: the values ride in registers only -- the slot that takes the anchor gets its window INDEX, which fits the key word --
 // so the LDS table is the narrow pass's)
 template <typename KeyT, bool WIDE, typename ValT = uint32_t>
@@ -661,23 +529,16 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
         }
         if (idx < lo || idx >= hi) k[r] = EMPTY;
     }
-    // ---- pass 1: group by mer: claim a slot (compare-and-swap on the key word, linear probing), then OR the entry's genome
-    // into the slot's once / multi sets ----
+    // ---- pass 1: group by mer (group_claim, group_note) ----
     uint32_t slot[HJ_ROWS]; uint32_t gbit[HJ_ROWS];
 #pragma unroll
     for (int r = 0; r < HJ_ROWS; r++) {
         slot[r] = HJ_NONE; gbit[r] = 0;
         if (k[r] == EMPTY) continue;                          // beyond the range, or an invalid window
-        uint32_t s = ((uint32_t)k[r] ^ (uint32_t)((uint64_t)k[r] >> 32)) * 0x9E3779B1u >> 20;       // 12 bits
-        for (;;) {
-            const KeyT old = atomicCAS(&skey[s], EMPTY, k[r]);
-            if (old == EMPTY || old == k[r]) break;
-            s = (s + 1) & (HJ_SLOTS - 1);
-        }
-        const uint32_t bit = 1u << genome_of(win_idx(v[r]), tab);
-        const uint32_t old = atomicOr(&som[s], bit);
-        if (old & bit) { if (WIDE) atomicOr(&som2[s], bit); else atomicOr(&som[s], bit << 16); }
-        slot[r] = s; gbit[r] = bit;
+        const uint32_t s = ((uint32_t)k[r] ^ (uint32_t)((uint64_t)k[r] >> 32)) * 0x9E3779B1u >> 20;       // 12 bits
+        slot[r] = group_claim<KeyT, HJ_SLOTS>(skey, k[r], s);
+        gbit[r] = 1u << genome_of(win_idx(v[r]), tab);
+        group_note<WIDE>(som, som2, slot[r], gbit[r]);
     }
     __syncthreads();
     // ---- pass 2: the finder rule per mer; the entry of the lowest component genome is the anchor ----
@@ -688,9 +549,8 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
         if (slot[r] == HJ_NONE) continue;
         const uint32_t om = som[slot[r]];
         const uint32_t once = WIDE ? om : (om & 0xffffu), multi = WIDE ? som2[slot[r]] : (om >> 16);
-        const uint32_t m = once & ~multi;
-        if (mode == MAUVE_MODE_MEM && multi) continue;
-        if (__popc(m) < 2 || (want_mask && m != want_mask) || !(m & gbit[r])) continue;
+        const uint32_t m = finder_components(mode, once, multi, want_mask);
+        if (!(m & gbit[r])) continue;
         mm[r] = m;
         if ((m & (0u - m)) == gbit[r]) skey[slot[r]] = sizeof(ValT) == 4 ? (KeyT)v[r] : (KeyT)win_idx(v[r]);   // grouping is over: the slot's mer makes room for the anchor
     }
@@ -711,8 +571,8 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
 // A seed pass over a few thousand windows (a round of the LCB extension over the pieces between the LCBs, a small guide-tree
 // node) spends its time in launches: count, scan, extract, four sort passes, bounds, join -- a dozen kernels of 5-20 us each
 // for a few kilobytes.  Here one workgroup of 1024 threads computes the canonical mers of ALL valid windows, groups them in an
-// LDS hash table (compare-and-swap claim, linear probing; the same once / multi genome sets and the same finder rule as
-// join_hash) and writes the hit table -- no key array, no sort.  <= TJ_MAX windows, <= 16 genomes, mer (+ gap id of a segmented
+// LDS hash table (group_claim / group_note: join_hash's once / multi genome sets; then finder_components, the rule every join applies)
+// and writes the hit table -- no key array, no sort.  <= TJ_MAX windows, <= 16 genomes, mer (+ gap id of a segmented
 // set: the small batches of the deeper recursion levels) of <= 32 bits.
 constexpr int TJ_SLOTS = 16384;                  // 128 KB of LDS: key word + genome sets per slot
 constexpr int TJ_MAX = 9216;                     // load factor <= 0.5625
@@ -740,38 +600,22 @@ __global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ p
         if (!window_valid(gp, P, tab, sh.span, vmask, cmask)) continue;
         const int g = genome_of(gp, tab);
         const uint32_t p = gp - tab.gpos_off[g];
-        uint32_t k, sflag;
-        if (sh.span <= 32 && sh.weight <= 15) {
-            const uint32_t kp = kprime_narrow(packed + tab.word_off[g], p, sh);
-            const uint32_t f = digit_reverse32(kp, sh.weight), rr = (~kp) & (uint32_t)sh.keymask;
-            sflag = rr < f; k = sflag ? rr : f;
-        } else {
-            const uint64_t kp = kprime_at(packed + tab.word_off[g], p, sh);
-            const uint64_t f = digit_reverse(kp, sh.weight), rr = (~kp) & sh.keymask;
-            sflag = rr < f; k = (uint32_t)(sflag ? rr : f);
-        }
+        const MerKey m = seed_narrow(sh) ? mer_at<true>(packed + tab.word_off[g], p, sh) : mer_at<false>(packed + tab.word_off[g], p, sh);
+        uint32_t k = (uint32_t)m.key;
         if (seg) {                                  // segmented set (a batch of recursion gaps): the gap id rides above the mer, no window across gaps
-            const uint32_t *sg = seg + (size_t)g * (nseg + 1);
-            const uint32_t sk = seg_of(sg, nseg, p);
-            if (p + (uint32_t)sh.span > sg[sk + 1]) continue;
+            uint32_t sk;
+            if (!window_segment(seg, nseg, g, p, sh.span, &sk)) continue;
             k |= sk << (2 * sh.weight);
         }
-        key[r] = k; v[r] = (LOCAL ? p : gp) | (sflag << 31); gbit[r] = 1u << g;
+        key[r] = k; v[r] = (LOCAL ? p : gp) | (m.strand << 31); gbit[r] = 1u << g;
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < TJ_ROWS; r++) {
         slot[r] = EMPTY;
         if (key[r] == EMPTY) continue;
-        uint32_t sl = (key[r] * 0x9E3779B1u) >> 18;          // 14 bits
-        for (;;) {
-            const uint32_t old = atomicCAS(&skey[sl], EMPTY, key[r]);
-            if (old == EMPTY || old == key[r]) break;
-            sl = (sl + 1) & (TJ_SLOTS - 1);
-        }
-        const uint32_t old = atomicOr(&som[sl], gbit[r]);
-        if (old & gbit[r]) atomicOr(&som[sl], gbit[r] << 16);
-        slot[r] = sl;
+        slot[r] = group_claim<uint32_t, TJ_SLOTS>(skey, key[r], (key[r] * 0x9E3779B1u) >> 18);          // 14 bits
+        group_note<false>(som, nullptr, slot[r], gbit[r]);
     }
     __syncthreads();
     uint32_t mm[TJ_ROWS];
@@ -779,9 +623,8 @@ __global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ p
     for (int r = 0; r < TJ_ROWS; r++) {
         mm[r] = 0;
         if (slot[r] == EMPTY) continue;
-        const uint32_t om = som[slot[r]], once = om & 0xffffu, multi = om >> 16, m = once & ~multi;
-        if (mode == MAUVE_MODE_MEM && multi) continue;
-        if (__popc(m) < 2 || (want_mask && m != want_mask) || !(m & gbit[r])) continue;
+        const uint32_t om = som[slot[r]], m = finder_components(mode, om & 0xffffu, om >> 16, want_mask);
+        if (!(m & gbit[r])) continue;
         mm[r] = m;
         if ((m & (0u - m)) == gbit[r])                                 // grouping is over: the slot's mer makes room for the anchor
             skey[slot[r]] = LOCAL ? (v[r] & 0x7fffffffu) + tab.gpos_off[__ffs(gbit[r]) - 1] : v[r];
@@ -1408,8 +1251,6 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
 bool seed_trace_on() { static const bool v = getenv("MAUVE_TRACE") != nullptr; return v; }
 // a pass of a few thousand windows takes the hash join like any other
 static bool no_tiny() { static const bool v = getenv("MAUVE_NO_TINY") != nullptr; return v; }
-// MAUVE_SMALL_SORT=0: sorts of up to SS_CAP pairs take the tiled path too
-static bool small_sort_on() { static const bool v = [] { const char *e = getenv("MAUVE_SMALL_SORT"); return !(e && e[0] == '0'); }(); return v; }
 // shrinks the compacted lists so that the capacity checks can be seen to fire (0: off)
 static uint32_t list_cap_env() { static const uint32_t v = getenv("MAUVE_LIST_CAP") ? (uint32_t)strtoul(getenv("MAUVE_LIST_CAP"), nullptr, 10) : 0u; return v; }
 // candidates from which the canonical order is made on the device (below: the host sorts; tests force the device path)
@@ -1467,89 +1308,6 @@ static int build_tab(mauve_ctx *ctx, const GenomeSet &gs, int span, GenomeTab *t
     for (int g = gs.nseq + 1; g <= MAUVE_MAX_SEQ; g++) tab->gpos_off[g] = 0xffffffffu;      // see genome_of
     *total_windows = tot;
     return MAUVE_OK;
-}
-
-template <typename KeyT, typename ValT = uint32_t>
-static int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **vals_io, KeyT *keys_alt,
-                      ValT *vals_alt, bool have_hist0, int timer_id = -1, int shift_lo = 0)
-{
-    // LSD passes over bits [shift_lo, key_bits); have_hist0: the tile histograms of the first pass are already in ctx->hist
-    // timer_id >= 0: all launches are booked under that id (the small canonical-order sort must not dilute the
-    // per-kernel figures of the main sort)
-    const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scan = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCAN,
-              k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
-    if (small_sort_on() && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
-        HIPCHK(ctx, ctx->hist.ensure(ss_ws_words(n) * sizeof(uint32_t)));
-        small_sort<KeyT>(ctx->stream, n, key_bits, shift_lo, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
-                         [&](bool scatter, auto &&launch) { KernelTimer t(ctx, scatter ? k_scat : k_hist, n); launch(); });
-        HIPCHK(ctx, hipGetLastError());
-        return MAUVE_OK;
-    }
-    uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
-    HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
-    HIPCHK(ctx, ctx->totals.ensure(256 * sizeof(uint32_t)));
-    KeyT *kin = *keys_io, *kout = keys_alt; ValT *vin = *vals_io, *vout = vals_alt;
-    for (int shift = shift_lo; shift < key_bits; shift += 8) {
-        if (!(shift == shift_lo && have_hist0)) { KernelTimer t(ctx, k_hist, n);
-          hipLaunchKernelGGL(rs_hist<KeyT>, dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, n, shift,
-                             ctx->hist.as<uint32_t>(), nblk); }
-        if (nblk <= 64) {      // small sort: no row scan launch, the scatter reads the raw tile histograms
-            KernelTimer t(ctx, k_scat, n);
-            hipLaunchKernelGGL((rs_scatter<KeyT, true, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
-                               shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk);
-            std::swap(kin, kout); std::swap(vin, vout);
-            continue;
-        }
-        { KernelTimer t(ctx, k_scan, n);
-          hipLaunchKernelGGL(rs_rowscan, dim3(256), dim3(256), 0, ctx->stream, ctx->hist.as<uint32_t>(), nblk,
-                             ctx->totals.as<uint32_t>()); }
-        { KernelTimer t(ctx, k_scat, n);
-          hipLaunchKernelGGL((rs_scatter<KeyT, false, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
-                             shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk); }
-        std::swap(kin, kout); std::swap(vin, vout);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    *keys_io = kin; *vals_io = vin;
-    return MAUVE_OK;
-}
-
-// stable LSD radix sort of (32-bit key, 32-bit value) pairs for the other translation units (chain_dev.hip) ...
-int sort_pairs_u32(mauve_ctx *ctx, uint32_t n, int key_bits, uint32_t **keys_io, uint32_t **vals_io, uint32_t *keys_alt, uint32_t *vals_alt,
-                   int timer_id)
-{
-    return sort_pairs<uint32_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
-}
-// S such sorts of n pairs each, same key_bits, segment s in the n pairs from s * seg_stride of all four buffers (chain_dev.hip: the orders of all
-// genomes): one batched small sort, or -- engine off, n beyond its range -- S sorts one after another on the same buffers.  Either way every
-// segment gets the permutation and the result-buffer parity of sort_pairs_u32; *keys_io / *vals_io point at segment 0 of the result.
-int sort_pairs_u32_batch(mauve_ctx *ctx, uint32_t S, uint32_t n, size_t seg_stride, int key_bits, uint32_t **keys_io, uint32_t **vals_io,
-                         uint32_t *keys_alt, uint32_t *vals_alt, int timer_id)
-{
-    if (S == 0 || n == 0) return MAUVE_OK;
-    if (S > 65535u || seg_stride < n) { ctx->err = "sort_pairs_u32_batch: bad segment layout"; return MAUVE_ERR_ARG; }
-    if (small_sort_on() && n <= SS_CAP) {
-        const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
-        HIPCHK(ctx, ctx->hist.ensure(ss_ws_words_batch(S, n) * sizeof(uint32_t)));
-        small_sort_batch<uint32_t>(ctx->stream, S, n, seg_stride, key_bits, 0, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
-                                   [&](bool scatter, auto &&launch) { KernelTimer t(ctx, scatter ? k_scat : k_hist, (int64_t)S * n); launch(); });
-        HIPCHK(ctx, hipGetLastError());
-        return MAUVE_OK;
-    }
-    uint32_t *k0 = *keys_io, *v0 = *vals_io;
-    for (uint32_t s = 0; s < S; s++) {
-        uint32_t *kk = *keys_io + s * seg_stride, *vv = *vals_io + s * seg_stride;
-        int rc = sort_pairs<uint32_t>(ctx, n, key_bits, &kk, &vv, keys_alt + s * seg_stride, vals_alt + s * seg_stride, false, timer_id);
-        if (rc) return rc;
-        if (s == 0) { k0 = kk; v0 = vv; }
-    }
-    *keys_io = k0; *vals_io = v0;
-    return MAUVE_OK;
-}
-// ... and of (64-bit key, 32-bit value) pairs (seed_finish.hip)
-int sort_pairs_u64(mauve_ctx *ctx, uint32_t n, int key_bits, uint64_t **keys_io, uint32_t **vals_io, uint64_t *keys_alt, uint32_t *vals_alt,
-                   int timer_id)
-{
-    return sort_pairs<uint64_t>(ctx, n, key_bits, keys_io, vals_io, keys_alt, vals_alt, false, timer_id);
 }
 
 // ---- what the stages of a pass share ----
@@ -1648,7 +1406,7 @@ static int ensure_sort_buffers(mauve_ctx *ctx, uint32_t n)
 template <typename F>
 static void launch_narrow_or_not(const SeedShape &sh, F &&launch)
 {
-    if (sh.span <= 32 && sh.weight <= 15) launch(std::true_type{});
+    if (seed_narrow(sh)) launch(std::true_type{});
     else launch(std::false_type{});
 }
 

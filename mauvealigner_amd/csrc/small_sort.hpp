@@ -1,7 +1,7 @@
 // small_sort.hpp -- the tile ranking of the LSD radix sort (8-bit digits, stable, (u32 | u64 key, u32 value) pairs) and the
 // small-sort engine built on it.
 //
-// rs_scatter_tile is the ranking and scatter of one tile, templated on the keys per thread: the main sort of seed_pass.hip
+// rs_scatter_tile is the ranking and scatter of one tile, templated on the keys per thread: the main sort of radix_sort.hip
 // runs it at 16 (4096-key tiles), the small engine at 1 .. 16.
 //
 // Small sorts (n <= SS_CAP: the chain's per-genome orders, the DP launch list, the canonical order -- 10^3 .. 10^5 pairs)
