@@ -9,6 +9,7 @@
 #include <functional>
 #include "workers.hpp"
 #include "host_chain.hpp"
+#include "backbone_host.hpp"
 #include <chrono>
 #include <algorithm>
 #include <cstring>
@@ -251,18 +252,13 @@ struct mauve_ctx {
     DevBuf ch_mw;                        // sum-of-pairs scores of the chain's cropped records (score-weighted LCBs on the device chain)
     DevBuf as_wide;                      // the anchor table widened to int64 for a direct fetch (compact fetch: the match list narrowed to int32)
     DevBuf res_narrow;                   // the columns narrowed to 8 / 16 bits for a compact fetch
-    DevBuf hom_cols;                     // homology pass (backbone_dev.hip): the re-split columns, swapped with res_cols when done
+    DevBuf hom_cols;                     // homology pass (homology_dev.hip): the re-split columns, swapped with res_cols when done
     DevBuf as_work, as_isl, res_cols;    // device assembly (assemble_dev.hip): work area, islands, result columns
     PinnedBuf pin_tab;                   // anchor table and match list of a device-assembled result on their way to the host
     PinnedBuf pin_asm, pin_cols;         // ... its per-LCB rows coming back; the columns and anchors on their way to a fetch
     PinnedBuf pin_chain;
     PinnedBuf pin_mask;                  // LCB extension: the valid-piece bitmap on its way to placed_mask
-    // backbone / islands of the last alignment (backbone_dev.hip)
-    struct BackboneResult {
-        int N = 0; bool valid = false;
-        std::vector<int64_t> seg_iv, seg_col, seg_len, seg_left, seg_right, islands;
-        std::vector<uint32_t> seg_mask;
-    } bb;
+    BackboneResult bb;                   // backbone / islands of the last alignment (backbone_dev.hip; the struct: backbone_host.hpp)
     PinnedBuf pin_bb;                    // rank queries and their answers
     DevBuf bb_cols, bb_work, bb_query;   // a caller's / a host-assembled column array; interval table + records; rank queries
     size_t bb_rec_cap = 0;
@@ -540,10 +536,19 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na, const int32_t *h_len,
                         int64_t max_gapped_len, const mauve_scoring *scoring, int32_t *gapcode, int64_t *n_dp_out, int64_t *code_total_out,
                         PinnedBuf *dcols, std::vector<int64_t> &dcol_off, std::vector<int64_t> &dscore, int64_t *cells, int stay = 0);
 int assemble_device(mauve_ctx *c, int64_t na, int64_t cells, mauve_align_sizes *sizes, bool host_chains = false);
-// a caller's column array against its interval table: right - left + 1 residues of every present genome, none of an absent one, no bit at
-// or above nseq -- else MAUVE_ERR_ARG with `who` in the text (backbone_dev.hip; the _alignment entry points of the backbone, the homology
-// pass and the coordinate index)
-int check_columns(mauve_ctx *c, const char *who, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int64_t *col_off, const uint32_t *d_cols);
+// An alignment as the stages behind it take it (backbone S12, homology pass S12b, coordinate index S14): the interval table on the host
+// ([n_iv][N] ends and strands, n_iv + 1 column offsets), the columns on the device.  The two makers and the checks are in aln_view.hip
+struct AlnView { int N; int64_t n_iv; const int64_t *left, *right; const int8_t *reverse; const int64_t *col_off; const uint32_t *d_cols; };
+// the result of this context: refused when it is stale (refuse_replaced: also when the genomes were replaced under a host-side result) or when there is
+// none; the columns where the assembly stage left them, else uploaded to upload_to.  An empty alignment comes back with N = nseq and no columns
+int aln_from_context(mauve_ctx *c, const char *who, bool refuse_replaced, DevBuf &upload_to, AlnView *out);
+// a caller's arrays: pointer checks, col_off ascends from 0, the columns to bb_cols (waited for: they are the caller's memory), check_columns
+int aln_from_arrays(mauve_ctx *c, const char *who, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off,
+                    const uint32_t *cols, AlnView *out);
+// the kernels turn column offsets into block and tile indices: they ascend from 0 (checked before anything is sized by them)
+int coord_check_offsets(mauve_ctx *c, const char *who, int64_t n_iv, const int64_t *col_off);
+// a caller's columns against its interval table: right - left + 1 residues of every present genome, none of an absent one, no bit at or above nseq
+int check_columns(mauve_ctx *c, const char *who, const AlnView &A);
 void coord_index_release(mauve_ctx *c);  // coord_dev.hip: the host side of the coordinate indices (their device buffers go with the context's DevBufs)
 // coord_dev.hip: the index of a caller's alignment into the slot X / index (mauve_coord_index_alignment: co / co_index; mauve_score_truth: co_truth / co_truth_index)
 int coord_index_arrays(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right,
@@ -557,8 +562,7 @@ bool fetch_compact_direct(mauve_ctx *c, int col_bytes, int32_t *mum_length, int3
 int prefetch_tables_enqueue(mauve_ctx *c, int N, int64_t na, const int32_t *alen, const int32_t *ast, const int32_t *alcb);
 bool fetch_tables_direct(mauve_ctx *c, int64_t *mum_length, int64_t *mum_start, int64_t *anchor_length, int64_t *anchor_start, int64_t *anchor_lcb, int *rc_out);
 // coord_dev.hip: the index in force from device columns and a host interval table (mauve_project_index)
-int coord_index_device(mauve_ctx *c, const char *who, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off,
-                       const uint32_t *d_cols);
+int coord_index_device(mauve_ctx *c, const char *who, const AlnView &A);
 bool host_pointer_is_pinned(const void *p);
 // device -> caller on the context's stream: a page-locked destination directly (queued: the caller synchronises), a pageable one through `pin`
 // in pieces of 64 MiB, each waited for

@@ -143,21 +143,12 @@ __global__ void __launch_bounds__(256) coord_select(CoordDev D, int64_t n, const
     if (bad) atomicOr(flag, bad);
 }
 
-// the kernels turn column offsets into block indices: they ascend from 0 (checked before anything is sized by them)
-int coord_check_offsets(mauve_ctx *c, const char *who, int64_t n_iv, const int64_t *col_off)
-{
-    bool ok = col_off[0] == 0;
-    for (int64_t i = 0; i < n_iv && ok; i++) ok = col_off[i + 1] >= col_off[i];
-    if (!ok) c->err = std::string(who) + ": col_off must ascend from 0";
-    return ok ? MAUVE_OK : MAUVE_ERR_ARG;
-}
-
 // Build the index of an alignment whose columns are on the device (d_cols) and whose interval table is on the host, into the slot X with
 // its buffer (the index in force: ctx->co / co_index; the correct alignment of DESIGN.md S17: ctx->co_truth / co_truth_index).  bb_work is
 // scratch of the build: the call ends in a stream synchronise.
-int coord_build_index(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, int N, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse,
-                      const int64_t *col_off, const uint32_t *d_cols)
+int coord_build_index(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, const AlnView &A)
 {
+    const int N = A.N; const int64_t n_iv = A.n_iv, *left = A.left, *right = A.right, *col_off = A.col_off;
     X.valid = false;
     const std::string w = who;
     if (N < 1 || N > MAUVE_MAX_SEQ) { c->err = w + ": genome count out of range"; return MAUVE_ERR_ARG; }
@@ -212,14 +203,14 @@ int coord_build_index(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, D
     if (n_ivg) {
         HIPCHK(c, hipMemcpyAsync(wk + w_left, left, n_ivg * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(wk + w_right, right, n_ivg * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(wk + w_rev, reverse, n_ivg, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(wk + w_rev, A.reverse, n_ivg, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(c, hipMemsetAsync(ix + o_samp, 0, n_samp * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(wk + w_flag, 0, 64, c->stream));
     CoordRec *rec = reinterpret_cast<CoordRec *>(ix);
     uint32_t *cnt = reinterpret_cast<uint32_t *>(wk);
     int64_t *pre = reinterpret_cast<int64_t *>(wk + w_pre), *bsum = reinterpret_cast<int64_t *>(wk + w_bsum);
-    hipLaunchKernelGGL(coord_build, dim3((uint32_t)((nb1 + 3) / 4)), dim3(256), 0, c->stream, d_cols, n_cols, N, nb1, rec, cnt);
+    hipLaunchKernelGGL(coord_build, dim3((uint32_t)((nb1 + 3) / 4)), dim3(256), 0, c->stream, A.d_cols, n_cols, N, nb1, rec, cnt);
     const CoCnt in{cnt, (uint32_t)nb1, N};
     hipLaunchKernelGGL((devscan::vscan_partial<int64_t, CoCnt>), dim3(n_tiles), dim3(256), 0, c->stream, in, n_scan, bsum);
     hipLaunchKernelGGL((devscan::vscan_write<int64_t, CoCnt>), dim3(n_tiles), dim3(256), 0, c->stream, in, n_scan, bsum, pre, (int64_t *)nullptr);
@@ -306,31 +297,19 @@ int coord_run(mauve_ctx *c, int kind, int64_t n, const int64_t *a, const int64_t
 
 }  // namespace
 
-// The index of a caller's alignment (the arrays of mauve_align_fetch) in the slot X: argument checks, the columns against the interval ends,
-// the build.  bb_cols holds the caller's columns during the call.
+// The index of a caller's alignment (the arrays of mauve_align_fetch) in the slot X: the front end's checks (aln_from_arrays), the build.
+// bb_cols holds the caller's columns during the call.
 int coord_index_arrays(mauve_ctx *c, const char *who, mauve_ctx::CoordIndex &X, DevBuf &index, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right,
                        const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)
 {
     X.valid = false;
-    if (nseq < 1 || nseq > MAUVE_MAX_SEQ || n_iv < 0 || !col_off || (n_iv && (!left || !right || !reverse)) || (n_iv && col_off[n_iv] > 0 && !cols)) {
-        c->err = std::string(who) + ": bad arguments"; return MAUVE_ERR_ARG;
-    }
-    if (const int rco = coord_check_offsets(c, who, n_iv, col_off)) return rco;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t nb = (size_t)col_off[n_iv] * 4;
-    HIPCHK(c, c->bb_cols.ensure(nb + 64));
-    if (nb) HIPCHK(c, hipMemcpyAsync(c->bb_cols.p, cols, nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                            // cols is the caller's (pageable) memory
-    if (n_iv) if (const int rcc = check_columns(c, who, nseq, n_iv, left, right, col_off, c->bb_cols.as<uint32_t>())) return rcc;
-    return coord_build_index(c, who, X, index, nseq, n_iv, left, right, reverse, col_off, c->bb_cols.as<uint32_t>());
+    AlnView A;
+    if (const int rc = aln_from_arrays(c, who, nseq, n_iv, left, right, reverse, col_off, cols, &A)) return rc;
+    return coord_build_index(c, who, X, index, A);
 }
 
 // The index in force from columns that are on the device already and an interval table on the host (project_dev.hip)
-int coord_index_device(mauve_ctx *c, const char *who, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off,
-                       const uint32_t *d_cols)
-{
-    return coord_build_index(c, who, c->co, c->co_index, nseq, n_iv, left, right, reverse, col_off, d_cols);
-}
+int coord_index_device(mauve_ctx *c, const char *who, const AlnView &A) { return coord_build_index(c, who, c->co, c->co_index, A); }
 
 extern "C" {
 
@@ -338,22 +317,10 @@ int mauve_coord_index(mauve_ctx *c)
 {
     if (!c) return MAUVE_ERR_ARG;
     c->co.valid = false; c->ex.valid = false; c->exc.valid = false;      // (a selection, DESIGN.md S15, and an excursion result, S18, belong to the index they were made on)
-    AlignResult &R = c->res;
-    if (R.stale) { c->err = "coord_index: the genomes were replaced after this alignment was made"; return MAUVE_ERR_STATE; }
-    const int64_t n_iv = R.sz.n_iv;
-    if ((int64_t)R.col_off.size() != n_iv + 1) { c->err = "coord_index: no alignment in this context"; return MAUVE_ERR_STATE; }
-    const int N = n_iv ? (int)(R.iv_left.size() / (size_t)n_iv) : c->nseq;
-    if (const int rco = coord_check_offsets(c, "coord_index", n_iv, R.col_off.data())) return rco;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t *d_cols;
-    if (R.cols_pending) d_cols = c->res_cols.as<uint32_t>();                // still where the assembly stage wrote them
-    else {
-        const size_t nb = (size_t)R.col_off[(size_t)n_iv] * 4;
-        HIPCHK(c, c->bb_cols.ensure(nb + 64));
-        if (nb) HIPCHK(c, hipMemcpyAsync(c->bb_cols.p, R.cols_data(), nb, hipMemcpyHostToDevice, c->stream));
-        d_cols = c->bb_cols.as<uint32_t>();
-    }
-    return coord_build_index(c, "coord_index", c->co, c->co_index, N, n_iv, R.iv_left.data(), R.iv_right.data(), R.iv_reverse.data(), R.col_off.data(), d_cols);
+    AlnView A;
+    if (const int rc = aln_from_context(c, "coord_index", false, c->bb_cols, &A)) return rc;
+    if (const int rco = coord_check_offsets(c, "coord_index", A.n_iv, A.col_off)) return rco;
+    return coord_build_index(c, "coord_index", c->co, c->co_index, A);    // (an empty alignment has an index, too)
 }
 
 int mauve_coord_index_alignment(mauve_ctx *c, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)

@@ -372,7 +372,7 @@ int mauve_project_index(mauve_ctx *c)
     if (R.genome_gen != c->genome_gen) { c->err = "project_index: the genomes were replaced after the projected index was built"; return MAUVE_ERR_STATE; }
     c->co.valid = false; c->ex.valid = false; c->exc.valid = false;      // (a selection, DESIGN.md S15, and an excursion result, S18, belong to the index they were made on)
     HIPCHK(c, hipSetDevice(c->device));
-    return coord_index_device(c, "project_index", R.N, R.n_iv, R.left.data(), R.right.data(), R.reverse.data(), R.col_off.data(), c->pj_cols.as<uint32_t>());
+    return coord_index_device(c, "project_index", AlnView{R.N, R.n_iv, R.left.data(), R.right.data(), R.reverse.data(), R.col_off.data(), c->pj_cols.as<uint32_t>()});
 }
 
 }  // extern "C"

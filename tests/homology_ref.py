@@ -1,6 +1,6 @@
 """The homology pass once more, written from that text alone: plain Python integers, both Viterbi values of every
 pair-column, a predecessor table, the walk back, then the split.  No clamp form, no scan, no segments -- what the device's segment
-scan (csrc/backbone_dev.hip) and the oracle's loop (orc_homology_apply) are both compared with.
+scan (csrc/homology_dev.hip) and the oracle's loop (orc_homology_apply) are both compared with.
 
 numpy only looks up the base of every (column, genome) and the emission score of every pair-column; the recurrence runs on Python
 ints, which do not overflow, so the score limits of the device (|score| <= 65536, transitions >= -2^28) mean nothing here."""

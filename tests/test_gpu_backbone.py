@@ -1,11 +1,14 @@
 """GPU parity tests of the backbone / island stage (mauve_backbone, mauve_backbone_alignment) against the
 CPU oracle's column-by-column restatement.  Integer work: every segment, genome set, column range and coordinate must
 match exactly."""
+import functools
+
 import numpy as np
 import pytest
 
 from mauvealigner_amd import synth
 from oracle import pyoracle as O
+from tests.backbone_cases import GAPS, random_case, random_alignment as _random_alignment  # noqa: F401 (tests/test_gpu_coord.py takes the generator from here)
 
 pytestmark = pytest.mark.gpu
 KEYS = ("seg_iv", "seg_col", "seg_len", "seg_mask", "seg_left", "seg_right", "islands")
@@ -17,56 +20,6 @@ def ctx():
     c = _lib.Context(0)
     yield c
     c.close()
-
-
-def _random_alignment(rng, N, n_iv, length, long_runs=False):
-    """intervals over random genome subsets: stretches where a random subset is present (the rest gapped), with
-    per-column dropouts; lengths chosen so that runs cross the 64-column words and the 4096-column chunks"""
-    left, right, rev, col_off, cols = [], [], [], [0], []
-    for _ in range(n_iv):
-        k = int(rng.integers(1, N + 1))
-        S = np.sort(rng.choice(N, k, replace=False))
-        full = 0
-        for g in S:
-            full |= 1 << int(g)
-        out = []
-        L = int(rng.integers(1, length))
-        while len(out) < L:
-            kind = rng.random()
-            if kind < 0.45:                                   # everybody present, a few dropouts
-                n = int(rng.integers(1, 200))
-                m = np.full(n, full, np.uint32)
-                drop = rng.random(n) < 0.05
-                m[drop] &= ~np.uint32(1 << int(rng.choice(S)))
-            elif kind < 0.9:                                  # a subset present: short or long run
-                n = int(rng.integers(1, 9000 if long_runs and rng.random() < 0.2 else 70))
-                sub = 0
-                for g in S:
-                    if rng.random() < 0.5:
-                        sub |= 1 << int(g)
-                m = np.full(n, sub, np.uint32)
-            else:                                             # alternating single genomes
-                n = int(rng.integers(1, 60))
-                m = np.array([1 << int(rng.choice(S)) for _ in range(n)], np.uint32)
-            out.append(m[m != 0])
-        m = np.concatenate(out) if out else np.zeros(0, np.uint32)
-        for g in S:                                           # every genome of the interval has a residue
-            if not np.any(m >> np.uint32(g) & 1):
-                m = np.concatenate([m, np.array([1 << int(g)], np.uint32)])
-        lo = np.zeros(N, np.int64)
-        hi = np.zeros(N, np.int64)
-        rv = np.zeros(N, np.int8)
-        for g in S:
-            cnt = int(np.count_nonzero(m >> np.uint32(g) & 1))
-            lo[g] = int(rng.integers(1, 1 << 20))
-            hi[g] = lo[g] + cnt - 1
-            rv[g] = int(rng.random() < 0.4)
-        left.append(lo)
-        right.append(hi)
-        rev.append(rv)
-        cols.append(m)
-        col_off.append(col_off[-1] + len(m))
-    return np.array(left), np.array(right), np.array(rev), np.array(col_off, np.int64), np.concatenate(cols)
 
 
 def _same(r, e):
@@ -97,10 +50,8 @@ def test_backbone_hand_case(ctx):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_backbone_random_alignments(ctx, seed):
-    rng = np.random.default_rng(1000 + seed)
-    N = [2, 3, 5, 8, 17, 32][seed]
-    left, right, rev, col_off, cols = _random_alignment(rng, N, n_iv=12, length=[3000, 9000, 20000][seed % 3], long_runs=seed >= 2)
-    for gap in (0, 3, 20, 500):
+    left, right, rev, col_off, cols = random_case(seed)
+    for gap in GAPS:
         r = ctx.backbone_alignment(left, right, rev, col_off, cols, island_gap=gap)
         e = O.backbone(left, right, rev, col_off, cols, island_gap=gap)
         _same(r, e)
@@ -215,3 +166,84 @@ def test_inconsistent_columns_are_refused(ctx):
         with pytest.raises(RuntimeError, match=r"\(-1\)"):
             ctx.backbone_alignment(l, r, v, off, c)
     _same(ctx.backbone_alignment(left, right, rev, off, cols), O.backbone(left, right, rev, off, cols, island_gap=20))
+
+
+def test_homology_refusals_of_a_foreign_alignment_keep_their_order(ctx):
+    """mauve_apply_homology_alignment on an alignment over 2 genomes in a context of 3: the offsets are looked at first (MAUVE_ERR_ARG),
+    then the genome count (MAUVE_ERR_STATE) -- before the columns are counted and before the scores are looked at, so inconsistent
+    columns or positive transition scores on top of the wrong count do not change the answer"""
+    ctx.set_genomes(synth.star_genomes(3, 20_000, 0.05, 7))
+    left, right, rev = np.array([[1, 1]]), np.array([[4, 4]]), np.zeros((1, 2), np.int8)
+    good, short, high = np.array([3, 3, 3, 3], np.uint32), np.array([3, 3, 3, 1], np.uint32), np.array([3, 3, 3, 7], np.uint32)
+    for cols in (good, short, high):
+        with pytest.raises(RuntimeError, match=r"\(-5\).*does not belong to the genomes"):
+            ctx.apply_homology_alignment(left, right, rev, [0, 4], cols)
+        with pytest.raises(RuntimeError, match=r"\(-5\).*does not belong to the genomes"):
+            ctx.apply_homology_alignment(left, right, rev, [0, 4], cols, ctx.hmm_params(go_homologous=1))
+        with pytest.raises(RuntimeError, match=r"\(-1\).*apply_homology: col_off must ascend from 0"):
+            ctx.apply_homology_alignment(left, right, rev, [1, 4], cols)
+
+
+@functools.lru_cache(maxsize=None)
+def _sequence_reference():
+    """the star genomes of test_inconsistent_columns_are_refused, the oracle's alignment of them and, under two HMM schemes, the oracle's
+    homology pass on it: the frozen default, which moves nothing here (the columns stay where they are), and `zero`, under which 1328
+    residues move (the re-split columns replace them).  Computed once, shared, never changed"""
+    from tests import homology_cases as HC
+    gs = synth.star_genomes(3, 20_000, 0.05, 7)
+    e = O.align(gs, O.default_params())["aln"]
+    hom = {}
+    for scheme in ("default", "zero"):
+        m, x, g, gh, gu = HC.SCHEMES[scheme]
+        hom[scheme] = O.homology_apply(gs, e["left"], e["right"], e["reverse"], e["col_off"], e["cols"],
+                                       O.hmm_params(match=m, mismatch=x, gap=g, go_homologous=gh, go_unrelated=gu))
+    assert hom["default"][2] == 0 and hom["zero"][2] > 1000
+    return gs, e, hom
+
+
+@pytest.mark.parametrize("scheme", ["default", "zero"])
+@pytest.mark.parametrize("resident", [True, False])
+def test_stages_in_sequence_on_one_result(ctx, resident, scheme):
+    """mauve_backbone -> mauve_apply_homology -> mauve_backbone -> mauve_coord_index on one result of this context, each step against the
+    oracle on the fetched arrays.  resident: nothing is fetched in between, the columns are only in HBM (after a homology pass that
+    moves residues: its re-split ones); else the result was fetched first and every stage that finds the columns on the host uploads
+    them.  The four entry points take the result in through one front end (aln_from_context): each must get the columns the step
+    before left, wherever they are.  After the fetched run the genomes are uploaded again under the host-side result: the stages that
+    read no bases still take it, the homology pass refuses it."""
+    from mauvealigner_amd import _lib
+    from tests import homology_cases as HC
+    from tests.coord_ref import CoordRef
+    gs, e, hom = _sequence_reference()
+    left, right, rev = e["left"], e["right"], e["reverse"]
+    hoff, hcols, hmoved = hom[scheme]
+    m, x, g, gh, gu = HC.SCHEMES[scheme]
+    ctx.set_genomes(gs)
+    a = ctx.align(_lib.default_params(), fetch=not resident)
+    if not resident:
+        assert np.array_equal(a["cols"], e["cols"]) and np.array_equal(a["col_off"], e["col_off"]) and np.array_equal(a["left"], left)
+    _same(ctx.backbone(island_gap=20), O.backbone(left, right, rev, e["col_off"], e["cols"], island_gap=20))
+    h = ctx.apply_homology(ctx.hmm_params(match=m, mismatch=x, gap=g, go_homologous=gh, go_unrelated=gu), fetch=not resident)
+    assert h["n_moved"] == hmoved and h["n_cols"] == len(hcols) and h["n_iv"] == len(left)
+    if not resident:
+        assert np.array_equal(h["cols"], hcols) and np.array_equal(h["col_off"], hoff)
+    _same(ctx.backbone(island_gap=20), O.backbone(left, right, rev, hoff, hcols, island_gap=20))
+    ctx.coord_index()
+    assert ctx.coord_index_size() == (3, len(left), len(hcols))
+    R = CoordRef(left, right, rev, hoff, hcols)
+    iv = np.repeat(np.arange(len(left), dtype=np.int64), np.diff(hoff))
+    col = np.arange(len(hcols), dtype=np.int64) - hoff[iv]
+    p, d = ctx.column_positions(iv, col)
+    ep, ed = R.column_positions(iv, col)
+    assert np.array_equal(p, ep) and np.array_equal(d, ed) and np.array_equal(d, hcols)
+    seq = np.concatenate([np.full(len(g), k, np.int32) for k, g in enumerate(gs)])
+    pos = np.concatenate([np.arange(1, len(g) + 1, dtype=np.int64) for g in gs])
+    qi, qc = ctx.seqpos_to_column(seq, pos)
+    ei, ec = R.seqpos_to_column(seq, pos)
+    assert np.array_equal(qi, ei) and np.array_equal(qc, ec)
+    if not resident:                                         # the same genomes again: the result, wholly on the host, stays, but its genomes count as replaced
+        ctx.set_genomes(gs)
+        _same(ctx.backbone(island_gap=20), O.backbone(left, right, rev, hoff, hcols, island_gap=20))
+        ctx.coord_index()
+        assert ctx.coord_index_size() == (3, len(left), len(hcols))
+        with pytest.raises(RuntimeError, match=r"\(-5\).*replaced"):
+            ctx.apply_homology(fetch=False)
