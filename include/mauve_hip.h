@@ -209,6 +209,21 @@ int mauve_seed_match_enumerate(mauve_ctx *ctx, int seq, uint64_t pattern, int64_
                                int64_t max_multi, int direct_only, int64_t *n_out, int64_t *n_starts,
                                int64_t *mult, int64_t *start_off, int64_t *starts);
 
+/* ---- repeat map of one genome: RepeatHash::FindMatches (mauveAligner.cpp:480-483, mauveAligner --repeats; frozen form DESIGN.md
+        S20).  The copies of a mer inside resident genome `seq` -- a family of m valid windows, max(2, min_multi) <= m <= max_multi
+        <= MAUVE_REPEAT_MAX_MULT -- are extended along their diagonal into maximal ungapped repeat matches, each emitted once.
+        mauve_repeat_matches leaves the result on the device and returns the counts; mauve_repeat_fetch copies it out in canonical
+        order as a CSR: length[n], mult[n], start_off[n + 1], starts[n_starts] (signed 1-based starts of a match's components in
+        ascending position; component 0 is positive).  The result stays until the next mauve_repeat_matches or genome upload;
+        like mauve_seed_match_enumerate the call reuses the seed pass's workspace (a device-resident alignment result is brought
+        to the host first); the match list of an earlier mauve_seed_mums stays fetchable.
+        MAUVE_ERR_ARG: null pointers, a bad pattern, seq out of range, max_multi > MAUVE_REPEAT_MAX_MULT or < 2; MAUVE_ERR_STATE: no
+        genomes set, a fetch with no repeat result in force; MAUVE_ERR_LIMIT: the genomes hold 2^31 bases or more together. ---- */
+#define MAUVE_REPEAT_MAX_MULT MAUVE_MAX_SEQ
+int mauve_repeat_matches(mauve_ctx *ctx, int seq, uint64_t pattern, int64_t min_multi, int64_t max_multi,
+                         int64_t *n_matches, int64_t *n_starts);
+int mauve_repeat_fetch(mauve_ctx *ctx, int64_t *length, int64_t *mult, int64_t *start_off, int64_t *starts);
+
 /* ---- chaining: MultiplicityFilter + EliminateOverlaps + Aligner::align's LCB stage
         (IdentifyBreakpoints / ComputeLCBs_v2 / greedy breakpoint elimination /
         computeLCBAdjacencies_v2; mauveAligner.cpp:596,600,698; toGrimmFormat.cpp:51-79).

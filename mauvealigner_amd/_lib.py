@@ -39,6 +39,7 @@ EXPORTS = [
     "mauve_score_truth", "mauve_score_alignment", "mauve_score_totals_from",
     "mauve_excursions_pairs", "mauve_excursions_core", "mauve_excursions_fetch", "mauve_excursion_thresholds",
     "mauve_default_project_params", "mauve_project", "mauve_project_fetch", "mauve_project_index",
+    "mauve_repeat_matches", "mauve_repeat_fetch",
 ]
 
 
@@ -545,6 +546,20 @@ class Context:
         self._chk(self.L.mauve_seed_match_enumerate(*args, C.byref(n), C.byref(ns), _p(mult, C.c_int64), _p(off, C.c_int64),
                                                     _p(st, C.c_int64)), "seed_match_enumerate")
         return mult, off, st
+
+    def repeat_matches(self, seq, pattern, min_multi=2, max_multi=32):
+        """extended repeat matches of resident genome `seq` (mauve_repeat_matches / mauve_repeat_fetch) ->
+        (length, mult, start_off, starts), int64, in canonical order"""
+        n, ns = C.c_int64(), C.c_int64()
+        self._chk(self.L.mauve_repeat_matches(self.h, int(seq), C.c_uint64(pattern), C.c_int64(min_multi), C.c_int64(max_multi),
+                                              C.byref(n), C.byref(ns)), "mauve_repeat_matches")
+        length = np.zeros(n.value, np.int64)
+        mult = np.zeros(n.value, np.int64)
+        off = np.zeros(n.value + 1, np.int64)
+        st = np.zeros(ns.value, np.int64)
+        self._chk(self.L.mauve_repeat_fetch(self.h, _p(length, C.c_int64), _p(mult, C.c_int64), _p(off, C.c_int64), _p(st, C.c_int64)),
+                  "mauve_repeat_fetch")
+        return length, mult, off, st
 
     def dp_batch(self, intervals, scoring=None, band_from=None):
         """intervals: list of lists of code arrays (nseq each).  -> (cols list, scores).  band_from: intervals whose

@@ -374,6 +374,11 @@ struct mauve_ctx {
     uint64_t rp_gen = 0, rp_pat = 0;     // what rp_mult holds (rp_gen 0: nothing)
     DevBuf rp_wcnt, rp_mult;             // per window: its genome's count of the canonical mer (0 = invalid window); per base: the multiplicity
     std::vector<uint64_t> rp_off;        // byte offset of every genome in rp_mult (16-byte aligned)
+    // repeat matches of one genome (repeat_dev.hip): the result of the last mauve_repeat_matches stays on the device for
+    // mauve_repeat_fetch -- int64 length[n] | mult[n] | start_off[n + 1] | starts[ns], ordered by start 0 -- in a buffer no other call
+    // writes; it belongs to the genomes it was made on (genome_gen tells an upload)
+    struct RepeatMap { bool valid = false; uint64_t genome_gen = 0; int64_t n = 0, ns = 0; } rm;
+    DevBuf rm_work, rm_res;              // the window table, candidate lists and scans; the result
 
     AlignResult res;
     AlignState ast;
@@ -502,6 +507,9 @@ void host_lcb_chain(const MatchVec &m, int64_t min_weight, bool collinear, std::
 int match_sp_scores(mauve_ctx *c, const MatchVec &m, const int *gmap, const mauve_scoring *sc, std::vector<int64_t> &out);
 // base multiplicities of the resident genomes for `pattern` into c->rp_mult (seed_pass.hip; cached)
 int repeat_multiplicity(mauve_ctx *c, uint64_t pattern);
+// the repeat map of resident genome `seq` (repeat_dev.hip) into c->rm / c->rm_res; the fetch finishes the canonical order
+int repeat_matches(mauve_ctx *c, int seq, uint64_t pattern, int64_t min_multi, int64_t max_multi);
+int repeat_fetch(mauve_ctx *c, int64_t *length, int64_t *mult, int64_t *start_off, int64_t *starts);
 // the root seed pattern of a call (seed families: the first of the family) -> multiplicities, c->rp_now = the context's mode; only
 // under sum-of-pairs LCB scoring (pipeline.cpp)
 int repeat_begin(mauve_ctx *c, const mauve_params *p, int w, uint64_t pat);
