@@ -22,7 +22,8 @@ def _child(args, env_extra, timeout):
 
 
 # every finder mode, recursion (segmented keys), contigs and ambiguity bitmaps, the extension rounds, extend_hits, SP scoring with the
-# repeat penalty, progressive with and without a tree, the multiplicity pass, sorted lists and the enumerator
+# repeat penalty, progressive with and without a tree, the multiplicity pass, sorted lists and the enumerator, the planted guide-tree and
+# breakpoint cases
 WIDE_MATRIX = [
     "tests/test_gpu_seed.py",
     "tests/test_gpu_align.py::test_align_equals_oracle",
@@ -35,6 +36,8 @@ WIDE_MATRIX = [
     "tests/test_gpu_align.py::test_progressive_align_along_a_given_tree",
     "tests/test_gpu_repeat_penalty.py::test_multiplicity_matches_reference",
     "tests/test_gpu_repeat_penalty.py::test_penalized_alignments_equal_oracle",
+    "tests/test_gpu_progressive.py::test_guide_tree_cases",
+    "tests/test_gpu_progressive.py::test_breakpoint_cases",
 ]
 
 
