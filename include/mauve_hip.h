@@ -596,6 +596,48 @@ int mauve_project(mauve_ctx *ctx, const mauve_project_params *p, mauve_project_s
 int mauve_project_fetch(mauve_ctx *ctx, int compact, int64_t *left, int64_t *right, int8_t *reverse, int64_t *col_off,
                         uint32_t *cols, int64_t *src_off, int64_t *src_iv, int8_t *src_flip, int64_t *src_col);
 int mauve_project_index(mauve_ctx *ctx);
+/* ---- annotated ranges mapped through the alignment, and the interval-overlap join behind them: the walk of getOrthologList
+        (getOrthologList.cpp:137-313), randomGeneSample (randomGeneSample.cpp:118-157), bbBreakOnGenes (bbBreakOnGenes.cpp:140-160) and
+        scoreProcrastAlignment (scoreProcrastAlignment.cpp:285-305) -- the intervals a range intersects, the range clipped to each,
+        SeqPosToColumn on both ends, copyRange, LeftEnd / RightEnd of every row, the feature of every genome with the largest overlap --
+        on the coordinate index in force.  Frozen form DESIGN.md S21.  No genome data is read.
+        A query is (seq, lo, hi): positions 1-based and unsigned, 1 <= lo <= hi; hi may lie past the genome's end (the index does not know
+        genome lengths) and is clipped.
+        (a) The pieces of query q are the intervals of the index in which seq is present and whose [left, right] in seq shares a base with
+        [lo, hi], in ascending order of their left end in seq.  A piece holds piece_query, piece_iv; clip_lo = max(lo, left), clip_hi =
+        min(hi, right); piece_col, piece_len: the columns of clip_lo and clip_hi by S14's rule, relative to the interval -- piece_col the
+        smaller of the two (on a reverse row they swap), piece_len their distance plus 1: a range in the form mauve_extract_select,
+        mauve_pair_stats and mauve_excursions_* take.  For every genome g of the index n_res[p*nseq + g] = the residues of row g in those
+        columns, ext_left / ext_right [p*nseq + g] = the smallest and the greatest position among them, both negative where the row is
+        reversed in the interval (S14's sign); all three 0 where g is absent from the interval or has only gaps in the range.  For g = seq
+        n_res = clip_hi - clip_lo + 1 and the extent is the clip.
+        (b) Per query: piece_off [n + 1]; covered[q] = the sum of the clipped lengths; best[q] = the index, in the piece arrays, of the
+        piece with the greatest clipped length, among equals the one with the greater interval id (the tool sorts (size, interval) pairs
+        and takes the last, :200-206), -1 without pieces.  A query with more than one piece is what the tool flags as rearranged.
+        mauve_map_ranges computes everything into device buffers of the context and tells the sizes (*sz may be NULL);
+        mauve_map_ranges_fetch writes it; any output pointer may be NULL, page-locked ones (mauve_host_alloc) are copied directly, and
+        so are page-locked query arrays.  The result stays until the next mauve_map_ranges, mauve_coord_index* or mauve_project_index ends
+        it; it neither needs nor disturbs the extract selection, the excursion result or the projection.  Two calls return identical bytes.
+        (c) mauve_range_overlaps is independent of any index and of the genomes: a table of m ranges (tab_seq, tab_lo, tab_hi) in any
+        order -- entries may nest, overlap and repeat -- and n queries (q_seq, q_lo, q_hi), which may be signed: their absolute values
+        are used and (0, 0) means "nothing", so a row of extents from (a) goes in as it is.  n_hit[q] = the table entries of the same
+        genome that share at least one base with the query; best[q] = the table index of the entry sharing the most bases, among equals
+        the greater table index (getOrthologList.cpp:250-273); overlap[q] = that number of bases; (0, -1, 0) for no hit.  The tool measures
+        the overlap inside n-way backbone segments; this rule measures plain shared bases.  A table entry that spans its genome makes every
+        query of that genome visit the genome's whole slice of the table: pass CDS-like features, as the tool does, not `source` features.
+        MAUVE_ERR_ARG, for the whole call: seq outside [0, nseq), lo < 1, lo > hi; a table entry with lo < 1 or lo > hi; a table or
+        query genome id of (c) outside [0, MAUVE_MAX_SEQ); a query of (c) with exactly one end 0, with ends of different sign, or with
+        |lo| > |hi|.  MAUVE_ERR_LIMIT: a position of 2^31 or more, more than 2^24 queries or table entries, 2^31 pieces or more.
+        MAUVE_ERR_STATE: no index (the first call), no result (the second).  n = 0 and m = 0 are MAUVE_OK.  A refused mauve_map_ranges
+        leaves the index and every other result usable. ---- */
+typedef struct { int64_t n_query, n_piece; } mauve_range_map_sizes;
+int mauve_map_ranges(mauve_ctx *ctx, int64_t n, const int32_t *seq, const int64_t *lo, const int64_t *hi, mauve_range_map_sizes *sz);
+int mauve_map_ranges_fetch(mauve_ctx *ctx, int64_t *piece_off /* n+1 */, int64_t *covered /* n */, int64_t *best /* n */,
+                           int64_t *piece_query, int64_t *piece_iv, int64_t *piece_col, int64_t *piece_len, int64_t *clip_lo,
+                           int64_t *clip_hi /* n_piece each */, int64_t *n_res, int64_t *ext_left, int64_t *ext_right /* n_piece*nseq each */);
+int mauve_range_overlaps(mauve_ctx *ctx, int64_t m, const int32_t *tab_seq, const int64_t *tab_lo, const int64_t *tab_hi,
+                         int64_t n, const int32_t *q_seq, const int64_t *q_lo, const int64_t *q_hi,
+                         int64_t *n_hit, int64_t *best, int64_t *overlap /* n each */);
 /* ---- an alignment scored against a correct one: scoreAlignment <correct alignment> <calculated alignment> (scoreAlignment.cpp:99-457),
         counted on two coordinate indices.  Frozen form DESIGN.md S17.  T is the correct alignment, loaded by the first call below; C, the
         calculated one, is the coordinate index in force (S14); both are over the same nseq genomes and follow S14's position rule.  No

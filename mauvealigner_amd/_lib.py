@@ -40,6 +40,7 @@ EXPORTS = [
     "mauve_excursions_pairs", "mauve_excursions_core", "mauve_excursions_fetch", "mauve_excursion_thresholds",
     "mauve_default_project_params", "mauve_project", "mauve_project_fetch", "mauve_project_index",
     "mauve_repeat_matches", "mauve_repeat_fetch",
+    "mauve_map_ranges", "mauve_map_ranges_fetch", "mauve_range_overlaps",
 ]
 
 
@@ -72,6 +73,10 @@ class ProjectParams(C.Structure):
 
 class ProjectSizes(C.Structure):
     _fields_ = [("n_iv", C.c_int64), ("n_cols", C.c_int64), ("n_src", C.c_int64), ("n_fill", C.c_int64)]
+
+
+class RangeMapSizes(C.Structure):
+    _fields_ = [("n_query", C.c_int64), ("n_piece", C.c_int64)]
 
 
 class AlignSizes(C.Structure):
@@ -1114,6 +1119,68 @@ class Context:
     def project_index(self):
         """mauve_project_index: the projection in force becomes the index in force (its columns stay on the device)"""
         self._chk(self.L.mauve_project_index(self.h), "mauve_project_index")
+
+    # ---- annotated ranges mapped through the alignment, the interval-overlap join (DESIGN.md S21) ----
+    def map_ranges(self, seq, lo, hi):
+        """mauve_map_ranges: the ranges [lo, hi] (1-based) of the genomes seq cut into their pieces, one per interval of the index in force
+        that they intersect; the result stays in the context for map_ranges_fetch.  -> dict(n_query, n_piece)"""
+        seq = np.ascontiguousarray(seq, np.int32)
+        lo = np.ascontiguousarray(lo, np.int64)
+        hi = np.ascontiguousarray(hi, np.int64)
+        n = len(seq)
+        if seq.ndim != 1 or lo.shape != seq.shape or hi.shape != seq.shape:
+            raise ValueError("map_ranges: seq, lo and hi differ in length")
+        z8, z4 = np.zeros(1, np.int64), np.zeros(1, np.int32)
+        sz = RangeMapSizes()
+        self._fm_shape = None
+        self._chk(self.L.mauve_map_ranges(self.h, C.c_int64(n), _p(seq if n else z4, C.c_int32), _p(lo if n else z8, C.c_int64), _p(hi if n else z8, C.c_int64), C.byref(sz)),
+                  "mauve_map_ranges")
+        self._fm_shape = (self.coord_index_size()[0], sz.n_query, sz.n_piece)
+        return dict(n_query=sz.n_query, n_piece=sz.n_piece)
+
+    RANGE_MAP_ARRAYS = ("piece_off", "covered", "best", "piece_query", "piece_iv", "piece_col", "piece_len", "clip_lo", "clip_hi", "n_res", "ext_left", "ext_right")
+
+    def map_ranges_fetch(self, out=None, want=None):
+        """mauve_map_ranges_fetch of the range map in force -> dict of piece_off [n + 1], covered, best [n], piece_query, piece_iv, piece_col,
+        piece_len, clip_lo, clip_hi [n_piece], n_res, ext_left, ext_right [n_piece, nseq]; out = dict of destination arrays (e.g. from
+        pinned_empty: copied without staging); want: the names to copy (None = all; the others are None)"""
+        shape = getattr(self, "_fm_shape", None)
+        self.L.mauve_map_ranges_fetch.argtypes = [C.c_void_p] * 13
+        if shape is None:                                        # no result: the library says so (nothing is written)
+            self._chk(self.L.mauve_map_ranges_fetch(self.h, *([None] * 12)), "mauve_map_ranges_fetch")
+            raise RuntimeError("mauve_map_ranges_fetch ran without a range map")
+        N, n, P = shape
+        shapes = [(n + 1,), (n,), (n,)] + [(P,)] * 6 + [(P, N)] * 3
+        res, args = {}, []
+        for name, shp in zip(self.RANGE_MAP_ARRAYS, shapes):
+            if want is not None and name not in want:
+                res[name] = None
+                args.append(None)
+                continue
+            a = out[name] if out is not None and name in out else np.zeros(shp, np.int64)
+            if a.dtype != np.int64 or a.shape != shp or not a.flags.c_contiguous:
+                raise ValueError("map_ranges_fetch: out[%r] must be a contiguous int64 array of shape %s" % (name, shp))
+            res[name] = a
+            args.append(C.c_void_p(a.ctypes.data) if a.size else None)
+        self._chk(self.L.mauve_map_ranges_fetch(self.h, *args), "mauve_map_ranges_fetch")
+        return res
+
+    def range_overlaps(self, tab, queries, out=None):
+        """mauve_range_overlaps: tab = (seq, lo, hi) arrays of annotated ranges in any order, queries = (seq, lo, hi) arrays, signed ends
+        allowed and (0, 0) = nothing (a column of map_ranges_fetch's ext_left / ext_right goes in as it is) -> (n_hit, best, overlap) per
+        query: the table entries sharing a base with it, the table index of the one sharing the most (ties: the greater index) and that
+        number of bases; (0, -1, 0) without a hit.  out = the three result arrays (e.g. from pinned_empty)"""
+        ts, qs = np.ascontiguousarray(tab[0], np.int32), np.ascontiguousarray(queries[0], np.int32)
+        tl, th, ql, qh = (np.ascontiguousarray(x, np.int64) for x in (tab[1], tab[2], queries[1], queries[2]))
+        m, n = len(ts), len(qs)
+        if ts.ndim != 1 or tl.shape != ts.shape or th.shape != ts.shape or qs.ndim != 1 or ql.shape != qs.shape or qh.shape != qs.shape:
+            raise ValueError("range_overlaps: the arrays of the table or of the queries differ in length")
+        z8, z4 = np.zeros(1, np.int64), np.zeros(1, np.int32)
+        res = [self._co_out(out, k, (n,), np.int64) for k in range(3)]
+        self._chk(self.L.mauve_range_overlaps(self.h, C.c_int64(m), _p(ts if m else z4, C.c_int32), _p(tl if m else z8, C.c_int64), _p(th if m else z8, C.c_int64),
+                                              C.c_int64(n), _p(qs if n else z4, C.c_int32), _p(ql if n else z8, C.c_int64), _p(qh if n else z8, C.c_int64),
+                                              *[_p(a if n else z8, C.c_int64) for a in res]), "mauve_range_overlaps")
+        return tuple(res)
 
     # ---- an alignment scored against a correct one (DESIGN.md S17) ----
     def score_truth(self, aln):

@@ -299,6 +299,11 @@ struct mauve_ctx {
         std::vector<int64_t> left, right, col_off, src_off, src_iv;
         std::vector<int8_t> reverse, src_flip;
     } pj;
+    // annotated ranges mapped through the alignment (feature_dev.hip): the pieces of the last mauve_map_ranges stay on the device
+    // for their fetches -- int64 piece_off[n + 1] | covered[n] | best[n] | six arrays [n_piece] | three [n_piece * N] (FmLayout) -- and belong to the
+    // index they were made on (an index call clears `valid`).  The overlap join keeps nothing between calls
+    struct RangeMap { bool valid = false; int N = 0; int64_t n_query = 0, n_piece = 0; } fm;
+    DevBuf fm_work, fm_res, fo_work;           // the flag word, queries, first pieces, counts and their scan; the result; the join's table, its sort buffers, queries and answers
     DevBuf pj_work, pj_cols, pj_src, pj_out;   // the flag word, pieces, unit counts, their scan and kept words (stays with the result); the columns; their source columns, once asked for; the compact form of a fetch
     DevBuf run_sum;                      // pairwise finder: run list (start, length, exactly-once genome set)
     DevBuf rec_vinv, rec_vcm;            // ... and their ambiguity / contig bitmaps, when the resident genomes have them

@@ -160,4 +160,49 @@ __global__ void __launch_bounds__(256) vscan_write(In in, uint32_t n, const T *_
     if (blockIdx.x == 0 && threadIdx.x == 0) { if (total) *total = s_all; out[n] = s_all; }
 }
 
+// ---- inclusive running maximum of values: vmax_partial (tile maxima) + vmax_write (out[i] = max of in[0..i]) ----
+// T unsigned (identity 0).  A caller whose values carry their segment in the high bits, ascending, gets the maximum inside each segment.
+template <class T, class In>
+__global__ void __launch_bounds__(256) vmax_partial(In in, uint32_t n, T *__restrict__ bmax)
+{
+    __shared__ T red[4];
+    const uint32_t r0 = blockIdx.x * (uint32_t)TILE + threadIdx.x * 4u;
+    T s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) if (r0 + i < n) s = max(s, in.value(r0 + i));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s = max(s, __shfl_down(s, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) bmax[blockIdx.x] = max(max(red[0], red[1]), max(red[2], red[3]));
+}
+template <class T, class In>
+__global__ void __launch_bounds__(256) vmax_write(In in, uint32_t n, const T *__restrict__ bmax, T *__restrict__ out)
+{
+    __shared__ T red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T sb = 0;                                // tiles before this one
+    for (uint32_t t = threadIdx.x; t < blockIdx.x; t += 256) sb = max(sb, bmax[t]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sb = max(sb, __shfl_down(sb, o));
+    if (lane == 0) red[wave] = sb;
+    __syncthreads();
+    const T before = max(max(red[0], red[1]), max(red[2], red[3]));
+    const uint32_t r0 = blockIdx.x * (uint32_t)TILE + threadIdx.x * 4u;
+    T v[4], s = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { v[i] = r0 + i < n ? in.value(r0 + i) : (T)0; s = max(s, v[i]); }
+    T inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const T t = __shfl_up(inc, o); if (lane >= o) inc = max(inc, t); }
+    __syncthreads();
+    if (lane == 63) red[wave] = inc;
+    __syncthreads();
+    const T up = __shfl_up(inc, 1);
+    T run = max(before, lane ? up : (T)0);   // everything in front of this thread's four entries
+    for (int w = 0; w < wave; w++) run = max(run, red[w]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) if (r0 + i < n) { run = max(run, v[i]); out[r0 + i] = run; }
+}
+
 }  // namespace devscan
