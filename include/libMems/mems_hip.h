@@ -29,4 +29,5 @@
 #include "Backbone.h"
 #include "Islands.h"
 #include "AlignmentScore.h"
+#include "RepeatScore.h"
 #endif

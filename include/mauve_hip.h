@@ -669,6 +669,41 @@ int mauve_score_truth(mauve_ctx *ctx, int nseq, int64_t n_iv, const int64_t *lef
                       const int64_t *col_off, const uint32_t *cols);
 int mauve_score_alignment(mauve_ctx *ctx, int64_t *records /* nseq*nseq*8 */);
 void mauve_score_totals_from(const int64_t *records, int nseq, mauve_score_totals *out);
+/* ---- a repeat map scored against a correct alignment of the copies of its repeats: scoreProcrastAlignment <correct alignment>
+        <calculated matches> (scoreProcrastAlignment.cpp:120-364, compareAlignmentsAceD), counted on the truth index of S17 and the
+        component extents of the map.  Frozen form DESIGN.md S22.  No genome data is read: the call needs no resident genomes.
+        T is the alignment loaded by mauve_score_truth, unchanged; here its nseq <= 32 rows are the copy slots of a repeat, an interval is
+        one repeat family, and a residue of row r lies at genome position row_offset[r] + its position (row_offset NULL: zeros, the rows
+        carry genome coordinates; non-zero: the tool's concat_coords, rows as the contigs of one concatenated sequence).
+        C is a list in the layout of mauve_repeat_fetch -- length[n], mult[n], start_off[n + 1], starts[start_off[n]], signed 1-based
+        starts, 2 <= mult <= MAUVE_REPEAT_MAX_MULT, ungapped: component c of record r covers [|start|, |start| + length - 1], is reverse
+        iff its start is negative, and holds base q in column q - left (forward) or right - q (reverse).  length == NULL (mult, start_off
+        and starts NULL too, n ignored) scores the result of the last mauve_repeat_matches where it lies on the device, in the order of
+        mauve_repeat_fetch (its finishing of the groups of equal start 0 included); the starts are not brought to the host.
+        A truth pair is two rows i < j with residues in one column of T, at genome positions q_i and q_j; same_T: the rows have the same
+        reverse flag in that interval.  A triple (r, c1, c2), c1 != c2, supports the pair iff q_i lies in c1, q_j lies in c2 and
+        (c1, c2 have the same sign) == same_T; exactly iff in addition q_i and q_j have the same column.  All combinations count (the
+        components of a tandem record overlap).  The tool pairs the k-th elements of two set intersections (:256-283), which is arbitrary
+        there; for an ungapped match its "an anchor intervenes" test (:291-316) always passes, so its figure is sp_truepos and sp_exact
+        is the stricter one.
+        totals: sp_possible = the truth pairs; sp_truepos / sp_exact = those with a supporting / an exactly supporting triple; components
+        = the sum of mult, component_pairs = the sum of m (m - 1) / 2, components_hit and component_pairs_hit = the set bits of the two
+        tables below.  pair_records[nseq * nseq * 4], row-major (i, j), filled for i < j: possible, truepos, exact, 0.  comp_hit[n]: bit c
+        of word r is set iff c is c1 or c2 of a supporting triple (:318-321).  pair_hit[start_off[n]]: bit max(c1, c2) of word
+        start_off[r] + min(c1, c2) (:323-335).  Any output but totals may be NULL; page-locked ones are copied directly, and so is a
+        page-locked list.  All counts are integers and every update commutes: two calls return identical bytes.
+        MAUVE_ERR_STATE: no truth; the resident form without a repeat result in force.  MAUVE_ERR_ARG, the text names the record: mult
+        outside [2, 32], start_off not the prefix sum of mult, a zero start, length < 1; a negative row_offset.  MAUVE_ERR_LIMIT: a genome
+        position of 2^31 or more, offset included; more than 2^24 records.  n = 0 and a truth without columns are MAUVE_OK and give zero
+        counts (components is still the sum of mult).  The call leaves the truth, the index in force, the repeat result, the extract
+        selection, the range map and the projection as they are.
+        The second, on the host and without a context: sensitivity = sp_truepos / sp_possible, exact sensitivity = sp_exact /
+        sp_possible, component PPV = components_hit / components, pairwise PPV = component_pairs_hit / component_pairs; 0 / 0 gives 0. ---- */
+typedef struct { int64_t sp_possible, sp_truepos, sp_exact, components, components_hit, component_pairs, component_pairs_hit, reserved; } mauve_repeat_score_totals;
+int mauve_repeat_score(mauve_ctx *ctx, int64_t n, const int64_t *length, const int64_t *mult, const int64_t *start_off,
+                       const int64_t *starts, const int64_t *row_offset, mauve_repeat_score_totals *totals,
+                       int64_t *pair_records /* nseq*nseq*4 */, uint32_t *comp_hit /* n */, uint32_t *pair_hit /* start_off[n] */);
+void mauve_repeat_score_ppv(const mauve_repeat_score_totals *t, double out[4]);
 /* IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760; format mfa2xmfa.cpp:64-115).
    Two-phase: buf == NULL returns the needed size (including NUL) in *len. */
 int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_t *len);

@@ -41,6 +41,7 @@ EXPORTS = [
     "mauve_default_project_params", "mauve_project", "mauve_project_fetch", "mauve_project_index",
     "mauve_repeat_matches", "mauve_repeat_fetch",
     "mauve_map_ranges", "mauve_map_ranges_fetch", "mauve_range_overlaps",
+    "mauve_repeat_score", "mauve_repeat_score_ppv",
 ]
 
 
@@ -307,6 +308,28 @@ def score_totals(records):
     return out
 
 
+REPEAT_SCORE_WORDS = 4                # int64 per row pair of mauve_repeat_score's pair_records: possible, truepos, exact, 0
+
+
+class RepeatScoreTotals(C.Structure):
+    _fields_ = [("sp_possible", C.c_int64), ("sp_truepos", C.c_int64), ("sp_exact", C.c_int64), ("components", C.c_int64), ("components_hit", C.c_int64),
+                ("component_pairs", C.c_int64), ("component_pairs_hit", C.c_int64), ("reserved", C.c_int64)]
+
+
+def repeat_score_ppv(totals):
+    """mauve_repeat_score_ppv (host entry, no context): the totals of Context.repeat_score (dict or RepeatScoreTotals) -> dict(sensitivity,
+    exact_sensitivity, component_ppv, pairwise_ppv), the figures of scoreProcrastAlignment.cpp:346-363; 0 / 0 gives 0"""
+    t = totals
+    if not isinstance(t, RepeatScoreTotals):
+        t = RepeatScoreTotals(*[int(totals.get(k, 0)) for k, _ in RepeatScoreTotals._fields_])
+    out = (C.c_double * 4)()
+    L = load()
+    L.mauve_repeat_score_ppv.restype = None
+    L.mauve_repeat_score_ppv.argtypes = [C.POINTER(RepeatScoreTotals), C.POINTER(C.c_double)]
+    L.mauve_repeat_score_ppv(C.byref(t), out)
+    return dict(zip(("sensitivity", "exact_sensitivity", "component_ppv", "pairwise_ppv"), (float(x) for x in out)))
+
+
 def pack_codes(codes):
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
     L = load()
@@ -558,6 +581,7 @@ class Context:
         n, ns = C.c_int64(), C.c_int64()
         self._chk(self.L.mauve_repeat_matches(self.h, int(seq), C.c_uint64(pattern), C.c_int64(min_multi), C.c_int64(max_multi),
                                               C.byref(n), C.byref(ns)), "mauve_repeat_matches")
+        self._rm_shape = (n.value, ns.value)
         length = np.zeros(n.value, np.int64)
         mult = np.zeros(n.value, np.int64)
         off = np.zeros(n.value + 1, np.int64)
@@ -1208,6 +1232,52 @@ class Context:
         rec = self._co_out((out,), 0, (N, N, SCORE_WORDS), np.int64) if out is not None else np.zeros((N, N, SCORE_WORDS), np.int64)
         self._chk(self.L.mauve_score_alignment(self.h, _p(rec, C.c_int64)), "mauve_score_alignment")
         return rec
+
+    # ---- a repeat map scored against a correct repeat alignment ----
+    REPEAT_SCORE_ARRAYS = ("pair_records", "comp_hit", "pair_hit")
+
+    def repeat_score(self, records=None, row_offset=None, want=REPEAT_SCORE_ARRAYS, out=None):
+        """mauve_repeat_score: the truth of score_truth, its rows the copy slots of a repeat, against a repeat map.  records = (length, mult,
+        start_off, starts) as repeat_matches returns them, or None = the result of the last repeat_matches where it lies on the device.
+        row_offset [nseq]: genome bases in front of every row's origin (None: zeros).  -> dict(totals = dict of the 8 counters, pair_records
+        [nseq, nseq, 4], comp_hit [n] uint32, pair_hit [n_starts] uint32); want: the tables to copy (the others are None); out = dict of
+        destination arrays (e.g. from pinned_empty: copied without staging)"""
+        N = getattr(self, "_score_n", 0)
+        self.L.mauve_repeat_score.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(RepeatScoreTotals)] + [C.c_void_p] * 3
+        tot = RepeatScoreTotals()
+        ro = None
+        if row_offset is not None:
+            ro = np.ascontiguousarray(row_offset, np.int64)
+            if N and ro.shape != (N,):
+                raise ValueError("repeat_score: row_offset must have one entry per row of the truth")
+        if records is None:
+            n, ns = getattr(self, "_rm_shape", (0, 0))
+            lst = [None] * 4
+        else:
+            length, mult, off, st = (np.ascontiguousarray(a, np.int64) for a in records)
+            n = len(length)
+            if length.ndim != 1 or mult.shape != (n,) or off.shape != (n + 1,) or st.ndim != 1 or (n and len(st) != int(off[n])):
+                raise ValueError("repeat_score: records = (length [n], mult [n], start_off [n + 1], starts [start_off[n]])")
+            ns = len(st)
+            z = np.zeros(1, np.int64)
+            lst = [(a if a.size else z) for a in (length, mult, off, st)]
+        shapes = {"pair_records": ((N, N, REPEAT_SCORE_WORDS), np.int64), "comp_hit": ((n,), np.uint32), "pair_hit": ((ns,), np.uint32)}
+        res, args = {}, []
+        for name in self.REPEAT_SCORE_ARRAYS:
+            shp, dt = shapes[name]
+            if name not in want or N == 0:
+                res[name] = None
+                args.append(None)
+                continue
+            a = out[name] if out is not None and name in out else np.zeros(shp, dt)
+            if a.dtype != np.dtype(dt) or a.shape != shp or not a.flags.c_contiguous:
+                raise ValueError("repeat_score: out[%r] must be a contiguous %s array of shape %s" % (name, np.dtype(dt).name, shp))
+            res[name] = a
+            args.append(C.c_void_p(a.ctypes.data) if a.size else None)
+        self._chk(self.L.mauve_repeat_score(self.h, C.c_int64(n), *[None if a is None else C.c_void_p(a.ctypes.data) for a in lst],
+                                            None if ro is None else C.c_void_p(ro.ctypes.data), C.byref(tot), *args), "mauve_repeat_score")
+        res["totals"] = {k: int(getattr(tot, k)) for k, _ in RepeatScoreTotals._fields_}
+        return res
 
     def stage_times(self):
         t = StageTimes()

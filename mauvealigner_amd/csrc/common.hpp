@@ -384,6 +384,8 @@ struct mauve_ctx {
     // writes; it belongs to the genomes it was made on (genome_gen tells an upload)
     struct RepeatMap { bool valid = false; uint64_t genome_gen = 0; int64_t n = 0, ns = 0; } rm;
     DevBuf rm_work, rm_res;              // the window table, candidate lists and scans; the result
+    // a repeat map scored against a correct repeat alignment (repeat_score_dev.hip): no state between calls, buffers of its own
+    DevBuf rs_work;                      // the flag word, totals, pair table and hit tables; the list; its extents, their sort buffers and prefix maxima
 
     AlignResult res;
     AlignState ast;

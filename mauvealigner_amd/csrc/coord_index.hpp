@@ -1,6 +1,6 @@
 // coord_index.hpp -- the coordinate index as its kernels see it: shared by coord_dev.hip, which builds and queries it,
 // extract_dev.hip and pairstat_dev.hip, which read ranks from it, score_dev.hip, which looks bases up in it (S17), and
-// feature_dev.hip, which maps ranges through it (S21).
+// feature_dev.hip, which maps ranges through it (S21), and repeat_score_dev.hip, which reads the positions of the truth's rows from it (S22).
 // The one column -> position rule (co_column, co_residue), the one position -> column rule (co_find), and the one error flag of the four
 // stages: a word with the bits CO_BAD_ARG and CO_BAD_INDEX, set with atomicOr by a thread that found something, read by co_flag_result.
 #pragma once
