@@ -90,7 +90,9 @@ __global__ void __launch_bounds__(256) rs_rowscan(uint32_t *__restrict__ hist, u
 // launch of pure latency.
 // LDS per workgroup (RS_TILE = 4096): keys + values + 7 KiB of counters -- 39 KiB for 4 + 4 bytes, 55 KiB for 8 + 4 or 4 + 8, 71 KiB for 8 + 8
 // (the wide pass with 64-bit keys): 4, 2, 2 workgroups per compute unit of 160 KiB.
-template <typename KeyT, bool RAW = false, typename ValT = uint32_t>
+// IOTA: the first pass of the seed pass's sort -- no value array comes in, vals_in is the strand bitmap seed_extract_all wrote beside the keys
+// (one bit per key, whole tiles) and a key's value is its own index plus that bit (rs_scatter_tile).
+template <typename KeyT, bool RAW = false, typename ValT = uint32_t, bool IOTA = false>
 __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict__ keys_in,
                                                          const ValT *__restrict__ vals_in,
                                                          KeyT *__restrict__ keys_out,
@@ -124,9 +126,11 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict_
     }
     __syncthreads();
     if (tile_n == RS_TILE)
-        rs_scatter_tile<KeyT, RS_ITEMS, true, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
+        rs_scatter_tile<KeyT, RS_ITEMS, true, ValT, IOTA>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan,
+                                                          nullptr, 0, 0, reinterpret_cast<const uint64_t *>(vals_in));
     else
-        rs_scatter_tile<KeyT, RS_ITEMS, false, ValT>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan);
+        rs_scatter_tile<KeyT, RS_ITEMS, false, ValT, IOTA>(keys_in, vals_in, keys_out, vals_out, tile_base, tile_n, shift, s_keys, s_vals, wcount, gbase, tstart, scan,
+                                                           nullptr, 0, 0, reinterpret_cast<const uint64_t *>(vals_in));
 }
 
 // MAUVE_SMALL_SORT=0: sorts of up to SS_CAP pairs take the tiled path too (read once, when it is first asked for)
@@ -134,10 +138,11 @@ static bool small_sort_on() { static const bool v = [] { const char *e = getenv(
 
 template <typename KeyT, typename ValT>
 int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **vals_io, KeyT *keys_alt, ValT *vals_alt, bool have_hist0,
-               int timer_id, int shift_lo)
+               int timer_id, int shift_lo, bool iota)
 {
     const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scan = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCAN,
               k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
+    if (iota && !(have_hist0 && shift_lo < key_bits)) { ctx->err = "sort_pairs: values from the strand bitmap need a first tiled pass"; return MAUVE_ERR_ARG; }
     if (small_sort_on() && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
         HIPCHK(ctx, ctx->hist.ensure(ss_ws_words(n) * sizeof(uint32_t)));
         small_sort<KeyT>(ctx->stream, n, key_bits, shift_lo, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
@@ -153,10 +158,11 @@ int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **
         if (!(shift == shift_lo && have_hist0)) { KernelTimer t(ctx, k_hist, n);
           hipLaunchKernelGGL(rs_hist<KeyT>, dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, n, shift,
                              ctx->hist.as<uint32_t>(), nblk); }
+        const bool first_iota = iota && shift == shift_lo;      // *vals_io holds the strand bitmap, not values
         if (nblk <= 64) {      // small sort: no row scan launch, the scatter reads the raw tile histograms
             KernelTimer t(ctx, k_scat, n);
-            hipLaunchKernelGGL((rs_scatter<KeyT, true, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
-                               shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk);
+            hipLaunchKernelGGL((first_iota ? rs_scatter<KeyT, true, ValT, true> : rs_scatter<KeyT, true, ValT, false>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream,
+                               kin, vin, kout, vout, n, shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk);
             std::swap(kin, kout); std::swap(vin, vout);
             continue;
         }
@@ -164,8 +170,8 @@ int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **
           hipLaunchKernelGGL(rs_rowscan, dim3(256), dim3(256), 0, ctx->stream, ctx->hist.as<uint32_t>(), nblk,
                              ctx->totals.as<uint32_t>()); }
         { KernelTimer t(ctx, k_scat, n);
-          hipLaunchKernelGGL((rs_scatter<KeyT, false, ValT>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream, kin, vin, kout, vout, n,
-                             shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk); }
+          hipLaunchKernelGGL((first_iota ? rs_scatter<KeyT, false, ValT, true> : rs_scatter<KeyT, false, ValT, false>), dim3(nblk), dim3(RS_THREADS), 0, ctx->stream,
+                             kin, vin, kout, vout, n, shift, ctx->hist.as<uint32_t>(), ctx->totals.as<uint32_t>(), nblk); }
         std::swap(kin, kout); std::swap(vin, vout);
     }
     HIPCHK(ctx, hipGetLastError());

@@ -66,19 +66,25 @@ __global__ void __launch_bounds__(256) seed_extract(const uint64_t *__restrict__
 
 // All genomes in one launch, tiled exactly like the radix sort (4096 windows per workgroup), with the digit
 // histogram of the first sort pass accumulated on the way out: saves two launches and one re-read of the keys.
+// sbits != nullptr: no value array.  A window's value is its own index plus its strand bit, and the index is where the key lies: the
+// workgroup writes the strand bits of its tile instead (bit gp of a bitmap of 64-bit words, here as 32-bit halves; all 128 halves of the
+// tile, zero at and behind P) and the first sort pass makes the values from them (rs_scatter IOTA) -- 1/8 byte per window stored
+// instead of 4 or 8, and nothing for that pass to read back but the bits.
 template <typename KeyT, bool SEG, bool NARROW, typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh,
                                                         KeyT *__restrict__ keys, ValT *__restrict__ vals, uint32_t P,
                                                         const uint32_t *__restrict__ seg, uint32_t nseg,
                                                         uint32_t *__restrict__ hist, uint32_t nblk,
                                                         const uint64_t *__restrict__ vmask, int hist_shift,
-                                                        const uint64_t *__restrict__ cmask)
+                                                        const uint64_t *__restrict__ cmask, uint32_t *__restrict__ sbits)
 {
     // A thread takes FOUR CONSECUTIVE windows at a time (four such groups: 4096 windows per workgroup, the sort's tile): their bases come from the
     // same three or four packed words (one set of loads instead of four), and the keys and values leave as 16-byte stores.  With one window per
     // thread and 4-byte stores the kernel ran at 1.6 TB/s, waiting on its own store issue (wait share 0.71), not on the arithmetic.
     __shared__ uint32_t h[256];
+    __shared__ uint32_t sb[4096 / 32];
     h[threadIdx.x] = 0;
+    if (threadIdx.x < 4096 / 32) sb[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * 4096u;
 #pragma unroll 2
@@ -126,13 +132,16 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 if ((vmask || cmask) && window_blocked(vmask ? vmask + tab.mask_off[g] : nullptr, cmask ? cmask + tab.mask_off[g] : nullptr, p, sh.span)) key[j] = ~0ULL;
             }
         }
+        // (a thread's four windows are one nibble of a bitmap half: gp0 - base is a multiple of 4; sf is 0 at and behind P)
+        if (sbits) atomicOr(&sb[(gp0 - base) >> 5], (sf[0] | sf[1] << 1 | sf[2] << 2 | sf[3] << 3) << ((gp0 - base) & 31u));
         if (gp0 + 3 < P) {
             if (sizeof(KeyT) == 4) *reinterpret_cast<uint4 *>(keys + gp0) = make_uint4((uint32_t)key[0], (uint32_t)key[1], (uint32_t)key[2], (uint32_t)key[3]);
             else {
                 reinterpret_cast<ulonglong2 *>(keys + gp0)[0] = make_ulonglong2(key[0], key[1]);
                 reinterpret_cast<ulonglong2 *>(keys + gp0)[1] = make_ulonglong2(key[2], key[3]);
             }
-            if constexpr (sizeof(ValT) == 4)
+            if (sbits) {}
+            else if constexpr (sizeof(ValT) == 4)
                 *reinterpret_cast<uint4 *>(vals + gp0) = make_uint4(gp0 | (sf[0] << 31), (gp0 + 1) | (sf[1] << 31), (gp0 + 2) | (sf[2] << 31), (gp0 + 3) | (sf[3] << 31));
             else {
                 reinterpret_cast<ulonglong2 *>(vals + gp0)[0] = make_ulonglong2(win_make<ValT>(gp0, sf[0]), win_make<ValT>(gp0 + 1, sf[1]));
@@ -142,13 +151,15 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
             for (int j = 0; j < 4; j++) atomicAdd(&h[(uint32_t)((KeyT)key[j] >> hist_shift) & 255u], 1u);
         } else {
             for (int j = 0; j < 4 && gp0 + j < P; j++) {
-                keys[gp0 + j] = (KeyT)key[j]; vals[gp0 + j] = win_make<ValT>(gp0 + j, sf[j]);
+                keys[gp0 + j] = (KeyT)key[j];
+                if (!sbits) vals[gp0 + j] = win_make<ValT>(gp0 + j, sf[j]);
                 atomicAdd(&h[(uint32_t)((KeyT)key[j] >> hist_shift) & 255u], 1u);
             }
         }
     }
     __syncthreads();
     hist[threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
+    if (sbits && threadIdx.x < 4096 / 32) sbits[(size_t)blockIdx.x * (4096 / 32) + threadIdx.x] = sb[threadIdx.x];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -449,6 +460,19 @@ __global__ void __launch_bounds__(256) join_hash(const KeyT *__restrict__ keys, 
         tpos[(size_t)ap * tab.nseq + g] = hit_word(v[r], tab.gpos_off[g]);
         if ((mm[r] & (0u - mm[r])) == gbit[r]) tmask[ap] = mm[r];
     }
+}
+
+// What a finder pass clears before its join, in one launch instead of two fills: the n words from t (its range of the hit table) and the
+// pass's counter block of 16 words.  A thread takes the four words of one 16-byte line of t, those outside [t, t + n) left alone.
+__global__ void __launch_bounds__(256) pass_clear(uint32_t *__restrict__ t, uint32_t n, uint32_t *__restrict__ counters)
+{
+    if (blockIdx.x == 0 && threadIdx.x < 16) counters[threadIdx.x] = 0;
+    const uint32_t head = (uint32_t)((reinterpret_cast<uintptr_t>(t) >> 2) & 3u);          // words between the line's start and t
+    const uint64_t w = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;                    // first word of this thread's line, from t - head
+    if (w >= (uint64_t)head + n) return;
+    uint32_t *line = t - head + w;
+    if (w >= head && w + 4 <= (uint64_t)head + n) *reinterpret_cast<uint4 *>(line) = make_uint4(0u, 0u, 0u, 0u);
+    else for (uint32_t j = 0; j < 4; j++) if (w + j >= head && w + j < (uint64_t)head + n) line[j] = 0;
 }
 
 // hits found by a host-side finder (mauve_extend_hits): record h = {component set, value of genome 0 .. N-1} -> hit table
@@ -1101,6 +1125,7 @@ struct SeedPlan {
     bool compact;       // only the valid windows go into the sort (valid_count / seed_extract_compact)
     bool has_invalid;   // some windows are unusable (placed or ambiguous bases, contig joins) and sit in the sorted list, with all-ones keys
     bool use_summary;   // pairwise finder over several pairs: one run list for all of them (run_summary)
+    bool strand_bitmap; // seed_extract_all writes no value array: the first sort pass makes the values from the window index and a strand bitmap
     int segbits;        // segmented keys: segment id above the mer; ids 0 .. nseg-1, the all-ones id is left to the invalid (all-ones) key
     int full_bits;      // key bits a full sort orders
     // globally sorted bits: 8-bit passes until a bucket averages <= 512 entries; a segmented list sorts at least the
@@ -1135,6 +1160,10 @@ static int seed_plan(mauve_ctx *ctx, const SeedShape &sh, const GenomeTab &tab, 
     pl->tiny = pl->hash_path && !no_tiny() && n <= (uint32_t)TJ_MAX && tab.nseq <= 16 && 2 * sh.weight + pl->segbits <= 32;
     pl->compact = !rq.hits && !pl->tiny && rq.only_seq < 0 && masked && !seg;
     pl->has_invalid = masked && !pl->compact;
+    // Only where seed_extract_all feeds a tiled sort pass (extract's third branch, and bits left to sort: a pass without a sort pass joins
+    // the list as extracted).  The compacted and single-genome extractions, the exports (only_seq), the multiplicity pass and host hits
+    // keep the value array: their values are not their own indices, or nothing would make them.
+    pl->strand_bitmap = !rq.hits && !pl->tiny && !pl->compact && rq.only_seq < 0 && pl->low_bits(n) < pl->full_bits;
     // one pass, or one per genome pair for PairwiseMatchFinder
     const int N = tab.nseq;
     if (rq.mode == MAUVE_MODE_PAIRWISE) {
@@ -1169,6 +1198,7 @@ template <typename KeyT, typename ValT>
 struct SeedPass : SeedState {
     KeyT *keys = nullptr; ValT *vals = nullptr;    // the list the sort takes and leaves
     bool have_hist0 = false;                       // ctx->hist holds the tile histograms of the first sort pass (seed_extract_all)
+    bool iota = false;                             // pl.strand_bitmap took effect: vals holds the strand bitmap, the first sort pass makes the values
     SeedPass(const SeedState &s) : SeedState(s) {}
 };
 
@@ -1191,9 +1221,10 @@ static void launch_narrow_or_not(const SeedShape &sh, F &&launch)
 }
 
 // keys and values of all n windows into keys / vals, the tile histograms of the first sort pass (digit at hshift) into ctx->hist
+// bitmap: no values -- the strand bitmap goes to the front of the vals buffer (see extract)
 template <typename KeyT, bool SEG, typename ValT>
 static int extract_all(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, uint32_t n, const uint32_t *seg, uint32_t nseg,
-                       int hshift, KeyT *keys, ValT *vals)
+                       int hshift, KeyT *keys, ValT *vals, bool bitmap = false)
 {
     const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
     HIPCHK(ctx, ctx->hist.ensure((size_t)nblk * 256 * sizeof(uint32_t)));
@@ -1203,7 +1234,7 @@ static int extract_all(mauve_ctx *ctx, const GenomeSet &gs, const SeedShape &sh,
     KernelTimer t(ctx, MAUVE_K_EXTRACT, n);
     launch_narrow_or_not(sh, [&](auto narrow) {
         hipLaunchKernelGGL((seed_extract_all<KeyT, SEG, decltype(narrow)::value, ValT>), dim3(nblk), dim3(256), 0, ctx->stream, packed, tab, sh, keys,
-                           vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask);
+                           vals, n, seg, nseg, ctx->hist.as<uint32_t>(), nblk, vmask, hshift, cmask, bitmap ? reinterpret_cast<uint32_t *>(vals) : nullptr);
     });
     return MAUVE_OK;
 }
@@ -1237,8 +1268,13 @@ static int extract(SeedPass<KeyT, ValT> &ps)
         if (int rc = seed_counters(ctx, 16, &cw)) return rc;       // (ctx->shadow stays for the pass's wait behind the run detection)
         ps.ns = cw[0];
     } else if (rq.only_seq < 0) {
-        if (int rc = extract_all<KeyT, SEG, ValT>(ctx, ps.gs, ps.sh, ps.tab, n, rq.seg, rq.nseg, ps.pl.low_bits(n), keys, vals)) return rc;
-        ps.ns = n; ps.have_hist0 = true;
+        // The strand bitmap (512 bytes per tile of 4096 windows) lies at the front of valsA, where the values would have gone.  Nothing
+        // else is in that buffer: extraction writes it, the first sort pass reads it and writes valsB, and valsA is written again only by
+        // the second pass, a launch later on the same stream.  It is at most the size of the values except for a list far shorter than a tile.
+        if (ps.pl.strand_bitmap) HIPCHK(ctx, ctx->valsA.ensure(std::max((size_t)n * sizeof(ValT), (size_t)((n + RS_TILE - 1) / RS_TILE) * (RS_TILE / 8))));
+        vals = ps.vals = ctx->valsA.as<ValT>();
+        if (int rc = extract_all<KeyT, SEG, ValT>(ctx, ps.gs, ps.sh, ps.tab, n, rq.seg, rq.nseg, ps.pl.low_bits(n), keys, vals, ps.pl.strand_bitmap)) return rc;
+        ps.ns = n; ps.have_hist0 = true; ps.iota = ps.pl.strand_bitmap;
     } else {
         const int g = rq.only_seq;
         uint32_t nw = ps.tab.nwin[g];
@@ -1323,15 +1359,45 @@ static bool cand_overflow(SeedState &st, uint32_t nc)
     return nc > st.cand_cap;
 }
 
-// extension phase A: run starts from the whole hit table
-template <bool SEG>
-static int launch_runs(SeedState &st)
+// The windows [lo, hi) in which a hit of a finder pass can be anchored.  The joins write tmask only at a hit's anchor, the window of the
+// lowest genome of its component set m (join_hash, mum_join_at), and m has at least two genomes (finder_components):
+//   want != 0 : m == want, so the anchor lies in genome ctz(want)  (the hot path: mauve_align, the LCB extension, the recursion and the
+//               progressive nodes all ask for the full set -- genome 0, a fifth of the windows of five genomes);
+//   want == 0 : m is any subset of `consider` within the set's genomes: from the lowest of them to just before the highest.
+// Hits the host supplies (hits_scatter) may be anchored anywhere.  A pass clears and scans this range only (finder_pass).
+// That leaves stale entries of earlier passes outside it, so every reader of tmask was checked:
+//   mum_runs   looks at [lo - RUNS_HALO, hi): the range and the halo in front of its first tile, which the pass clears as well;
+//   mum_extend reads tmask[ap] at candidates, which mum_runs took from the range, and on its left walk tmask[ap + k], k < 0 -- also in front of
+//              the range, but such a word only counts where k >= kmin (`a`), that is inside the anchor's own genome or gap segment,
+//              which lies in [lo, ap);
+//   tiny_join and the pair groups clear what they scan themselves, and nothing outside this file reads the table.
+// (A range that comes out empty -- a mask beyond the set, a genome shorter than the seed -- has no hit either way: the whole table then.)
+struct WinRange { uint32_t lo, hi; };
+static WinRange anchor_range(const GenomeTab &tab, uint32_t P, const FinderPass &fp, bool host_hits)
 {
-    mauve_ctx *ctx = st.ctx; const uint32_t P = st.P;
-    { KernelTimer t(ctx, MAUVE_K_RUNS, P);
-      hipLaunchKernelGGL((mum_runs<SEG>), dim3((P + RUNS_TILE - 1) / RUNS_TILE), dim3(256), 0, ctx->stream, st.tab,
-                         st.sh.span, st.tmask, st.tpos, P, st.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), st.rq.seg,
-                         st.rq.nseg, st.cand_cap, 0u); }
+    const int N = tab.nseq;
+    const uint32_t in_set = N >= 32 ? 0xffffffffu : (1u << N) - 1u;
+    WinRange r{0u, P};
+    if (host_hits) return r;
+    if (fp.want) {
+        const int g = __builtin_ctz(fp.want);
+        if (g < N) r = {tab.gpos_off[g], tab.gpos_off[g + 1]};
+    } else if (const uint32_t c = fp.consider & in_set)
+        r = {tab.gpos_off[__builtin_ctz(c)], tab.gpos_off[31 - __builtin_clz(c)]};
+    r.hi = std::min(r.hi, P);
+    if (r.lo >= r.hi) r = {0u, P};
+    return r;
+}
+
+// extension phase A: run starts from the windows [r.lo, r.hi) of the hit table
+template <bool SEG>
+static int launch_runs(SeedState &st, WinRange r)
+{
+    mauve_ctx *ctx = st.ctx;
+    { KernelTimer t(ctx, MAUVE_K_RUNS, r.hi - r.lo);
+      hipLaunchKernelGGL((mum_runs<SEG>), dim3((r.hi - r.lo + RUNS_TILE - 1) / RUNS_TILE), dim3(256), 0, ctx->stream, st.tab,
+                         st.sh.span, st.tmask, st.tpos, r.hi, st.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), st.rq.seg,
+                         st.rq.nseg, st.cand_cap, r.lo); }
     HIPCHK(ctx, hipGetLastError());
     return MAUVE_OK;
 }
@@ -1461,7 +1527,7 @@ static int tiny_pass(SeedState &st, const FinderPass &fp)
                          ctx->counters.as<uint32_t>() + 9, SEG ? st.rq.seg : (const uint32_t *)nullptr, st.rq.nseg, ctx->counters.as<uint32_t>(), 0u, P); }
     HIPCHK(ctx, hipGetLastError());
     seed_trace(ctx, "join", st.trace_t0);
-    if (int rc = launch_runs<SEG>(st)) return rc;
+    if (int rc = launch_runs<SEG>(st, WinRange{0u, P})) return rc;
     if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // host work that does not depend on the pass: the kernels above are still running
     const size_t lbytes = ((size_t)cand_cap * 4 + 63) & ~(size_t)63, sbytes = (size_t)cand_cap * 4 * N;
     HIPCHK(ctx, ctx->pin_seed.ensure(64 + lbytes + sbytes));
@@ -1530,7 +1596,7 @@ static int join_overflow_slices(SeedPass<KeyT, ValT> &ps, const FinderPass &fp, 
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
-    if (int rc = launch_runs<SEG>(ps)) return rc;
+    if (int rc = launch_runs<SEG>(ps, anchor_range(ps.tab, ps.P, fp, false))) return rc;
     const uint32_t *cw;
     if (int rc = seed_counters(ctx, 16, &cw)) return rc;
     *nc = cw[1];
@@ -1538,16 +1604,17 @@ static int join_overflow_slices(SeedPass<KeyT, ValT> &ps, const FinderPass &fp, 
     return MAUVE_OK;
 }
 
-// One finder pass that is neither tiny nor part of a pair group: clear the hit table, fill it (host hits, join_hash or mum_join:
-// seed_plan), run detection, extension.
+// One finder pass that is neither tiny nor part of a pair group: clear the hit table where the pass can anchor a hit (anchor_range), fill
+// it (host hits, join_hash or mum_join: seed_plan), run detection over that range, extension.
 template <typename KeyT, bool SEG, typename ValT>
 static int finder_pass(SeedPass<KeyT, ValT> &ps, const FinderPass &fp)
 {
     constexpr bool WIDEV = sizeof(ValT) == 8;
     mauve_ctx *ctx = ps.ctx; const uint32_t P = ps.P, ns = ps.ns; const int N = ps.tab.nseq;
     const HostHits *hh = ps.rq.hits;
-    HIPCHK(ctx, hipMemsetAsync(ps.tmask, 0, (size_t)P * 4, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    const WinRange ar = anchor_range(ps.tab, P, fp, hh != nullptr);
+    const uint32_t clr_lo = ar.lo >= RUNS_HALO ? ar.lo - RUNS_HALO : 0u;       // mum_runs reads the mask words one halo in front of its first tile
+    hipLaunchKernelGGL(pass_clear, dim3((ar.hi - clr_lo + 3) / 1024 + 1), dim3(256), 0, ctx->stream, ps.tmask + clr_lo, ar.hi - clr_lo, ctx->counters.as<uint32_t>());
     if (hh) {
         HIPCHK(ctx, ctx->run_sum.ensure((size_t)hh->n * (N + 1) * 4 + 64));
         HIPCHK(ctx, hipMemcpyAsync(ctx->run_sum.p, hh->rec, (size_t)hh->n * (N + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1571,7 +1638,7 @@ static int finder_pass(SeedPass<KeyT, ValT> &ps, const FinderPass &fp)
                          fp.want, fp.consider, ps.tmask, ps.tpos, P, (int)ps.pl.has_invalid); }
     HIPCHK(ctx, hipGetLastError());
     seed_trace(ctx, "join", ps.trace_t0);
-    if (int rc = launch_runs<SEG>(ps)) return rc;
+    if (int rc = launch_runs<SEG>(ps, ar)) return rc;
     if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }     // host work that does not depend on the pass: the kernels above are still running
     const uint32_t *cw;
     if (int rc = seed_counters(ctx, 48, &cw)) return rc;     // run counters + join_hash's overflow count
@@ -1604,7 +1671,7 @@ static int seedpass_stages(const SeedState &st0)
     if (ps.ns == 0) { if (rq.n_matches) *rq.n_matches = 0; return MAUVE_OK; }
     ps.L = ps.pl.low_bits(ps.ns);
     if (!rq.hits && !ps.pl.tiny)
-        if (int rc = sort_pairs<KeyT, ValT>(ctx, ps.ns, ps.pl.full_bits, &ps.keys, &ps.vals, ctx->keysB.as<KeyT>(), ctx->valsB.as<ValT>(), ps.have_hist0, -1, ps.L)) return rc;
+        if (int rc = sort_pairs<KeyT, ValT>(ctx, ps.ns, ps.pl.full_bits, &ps.keys, &ps.vals, ctx->keysB.as<KeyT>(), ctx->valsB.as<ValT>(), ps.have_hist0, -1, ps.L, ps.iota)) return rc;
     seed_trace(ctx, "sort", ps.trace_t0);
     if (rq.enumerate) return export_enumerator(ps);
     if (rq.out_keys) return export_sorted_list(ps);

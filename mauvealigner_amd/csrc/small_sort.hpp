@@ -53,23 +53,39 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total,
 // ever predicated off (all tiles but the last) -- the loads, ballots and stores compile without exec-mask branches.
 // hnext (small engine only): tile-major histogram of the next pass (digit at shift + 8, tiles of 1 << tile_log2 keys),
 // which every written key is added to; hbits: bits of a counter index there (8 + bits of the tile number).
-template <typename KeyT, int ITEMS, bool FULL, typename ValT = uint32_t>
+// IOTA (the seed pass's first sort pass, radix_sort.hip): there is no vals_in.  The value of the key at index x is x itself plus one
+// strand bit in the top bit of ValT, bit x of the bitmap sbits (64-bit words; tile_base is a multiple of 64).  The 64 items (i, lane 0..63)
+// of a wave are 64 consecutive indices from a multiple of 64, so their bits are one word: lane j < ITEMS fetches the word of item j -- one
+// coalesced load per wave -- and item i reads it from lane i.
+template <typename KeyT, int ITEMS, bool FULL, typename ValT = uint32_t, bool IOTA = false>
 __device__ __forceinline__ void rs_scatter_tile(const KeyT *__restrict__ keys_in, const ValT *__restrict__ vals_in,
                                                 KeyT *__restrict__ keys_out, ValT *__restrict__ vals_out,
                                                 uint32_t tile_base, uint32_t tile_n, int shift, KeyT *s_keys, ValT *s_vals,
                                                 uint32_t (*wcount)[256], const uint32_t *gbase, uint32_t *tstart, uint32_t *scan,
-                                                uint32_t *__restrict__ hnext = nullptr, int tile_log2 = 0, int hbits = 0)
+                                                uint32_t *__restrict__ hnext = nullptr, int tile_log2 = 0, int hbits = 0,
+                                                const uint64_t *__restrict__ sbits = nullptr)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // load (wave-striped: wave w owns [w*64*ITEMS, (w+1)*64*ITEMS), item i of lane l is index i*64+l)
     KeyT k[ITEMS]; ValT v[ITEMS]; uint32_t rank[ITEMS];
     const uint32_t wbase = wave * (64 * ITEMS);
+    uint32_t sb_lo = 0, sb_hi = 0;
+    if (IOTA) {
+        // (every word of a tile exists, also behind tile_n: the bitmap is whole tiles long, zero beyond the last key)
+        const uint64_t w = lane < ITEMS ? sbits[(size_t)((tile_base + wbase) >> 6) + (uint32_t)lane] : 0ULL;
+        sb_lo = (uint32_t)w; sb_hi = (uint32_t)(w >> 32);
+    }
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const uint32_t li = wbase + i * 64 + lane;
         const bool ok = FULL || li < tile_n;
         k[i] = ok ? keys_in[tile_base + li] : (KeyT)0;
-        v[i] = ok ? vals_in[tile_base + li] : (ValT)0;
+        if (IOTA) {
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)sb_lo, i), hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)sb_hi, i);
+            const uint32_t half = lane < 32 ? lo : hi;
+            v[i] = ok ? (ValT)(tile_base + li) | ((ValT)((half >> (lane & 31)) & 1u) << (8 * sizeof(ValT) - 1)) : (ValT)0;
+        } else
+            v[i] = ok ? vals_in[tile_base + li] : (ValT)0;
     }
     // wave-level multisplit ranking, stable in (i, lane) order.  peers = lanes of row i with the same digit, built
     // as two 32-bit halves from eight ballots (one 3-input bit op per half and bit).  The wave owns
