@@ -79,12 +79,19 @@ struct PinnedBuf {
 // Seed pattern decomposed into runs of contiguous care positions (kernel argument, by value).
 // K' ("digit-reversed forward mer"): care offset t_j contributes code << 2j, so that
 //   reverse-complement mer = ~K' (masked) and forward mer = digit_reverse(K').
+// Run i (care offsets t0 .. t0 + len - 1, the digits j .. j + len - 1 of K') lies 2 * (t0 - j) bits above its place in K': K' is the OR over
+// the runs of (window >> shift) under the run's mask in place.  The tables are whole 32-bit words, so that the scalar unit loads them once per
+// kernel (seed_dev.hpp: SeedRuns; byte-wide members cost a vector load each, gfx950 has no scalar byte load); entries behind nruns are zero
+// and contribute nothing.
+constexpr int SEED_RUN_GROUP = 4;                                  // the run loops leave after a whole group of runs
+constexpr int SEED_RUNS_NARROW = 16;                               // a span of 32 holds no more runs
+constexpr int SEED_RUNS_MAX = ((MAUVE_MAX_SEED_SPAN + 1) / 2 + SEED_RUN_GROUP - 1) / SEED_RUN_GROUP * SEED_RUN_GROUP;
 struct SeedShape {
     int span, weight, nruns;
     uint64_t keymask;          // (1 << 2*weight) - 1
-    uint8_t run_src[32];       // bit offset of the run in the window (2 * first care offset)
-    uint8_t run_bits[32];      // 2 * run length
-    uint8_t run_dst[32];       // bit offset in K'
+    uint32_t run_shift[SEED_RUNS_NARROW];   // one-word windows (seed_narrow): shift, and
+    uint32_t run_mask[SEED_RUNS_NARROW];    // ... the mask in place; both zero for any other seed
+    uint32_t run_wide[SEED_RUNS_MAX];       // every seed: shift | bit offset in K' << 8 | 2 * run length << 16 (the 64-bit mask is made from the two)
     uint64_t care_lo, care_hi; // 2-bit-expanded care mask of the window (offset t -> bits 2t, 2t+1)
 };
 

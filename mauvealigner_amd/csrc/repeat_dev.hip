@@ -21,8 +21,9 @@ template <typename KeyT, typename ValT>
 __global__ void __launch_bounds__(256) rm_extract(const uint64_t *__restrict__ G, const uint64_t *__restrict__ VM, const uint64_t *__restrict__ CM,
                                                   SeedShape sh, uint32_t nw, uint32_t gpos0, KeyT *__restrict__ keys, ValT *__restrict__ vals)
 {
+    const SeedRuns<false> runs(sh);
     for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < nw; p += gridDim.x * 256u) {
-        const MerKey m = mer_at<false>(G, p, sh);
+        const MerKey m = mer_at<false>(G, p, runs);
         keys[p] = window_blocked(VM, CM, p, sh.span) ? (KeyT)~0ULL : (KeyT)m.key;      // (no canonical mer is all ones: min(F, R) is never all T)
         vals[p] = win_make<ValT>(gpos0 + p, m.strand);
     }

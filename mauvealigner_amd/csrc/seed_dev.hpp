@@ -7,13 +7,6 @@
 // ------------------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t bits_from128(uint64_t lo, uint64_t hi, int start, int nbits)
-{
-    uint64_t v;
-    if (start >= 64) v = hi >> (start - 64);
-    else v = start ? ((lo >> start) | (hi << (64 - start))) : lo;
-    return nbits >= 64 ? v : (v & ((1ULL << nbits) - 1ULL));
-}
 // bits [r, r + 64) of the word pair w1:w0, r < 64
 __device__ __forceinline__ uint64_t funnel64(uint64_t w0, uint64_t w1, int r) { return r ? ((w0 >> r) | (w1 << (64 - r))) : w0; }
 
@@ -69,25 +62,62 @@ __device__ __forceinline__ WinDigits window_digits(const uint64_t *__restrict__ 
     const uint64_t w0 = G[q], w1 = G[q + 1], w2 = NARROW ? 0ULL : G[q + 2];
     return {funnel64(w0, w1, r), NARROW ? 0ULL : funnel64(w1, w2, r)};
 }
-// 2. K' = the seed's runs of digits, packed; forward mer = digit reverse of K', reverse mer = ~K' (masked).  The smaller one is the key,
-// strand = 1 when that is the reverse mer (a mer that is its own reverse complement: strand 0).
+// The seed's run table in registers: a kernel makes one at its entry, in front of its window loops, and hands it to canonical_mer / mer_at.
+// Every index below is a constant once the loops are unrolled, so the words are scalar loads from the kernel-argument segment that no window
+// waits for.  (Read where they are used, inside a loop over the runs, every trip of every window waits for its own loads: the run count is
+// a run-time value.)
 template <bool NARROW>
-__device__ __forceinline__ MerKey canonical_mer(const WinDigits &d, const SeedShape &sh)
+struct SeedRuns {
+    static constexpr int N = NARROW ? SEED_RUNS_NARROW : SEED_RUNS_MAX;
+    uint32_t w[N], m[NARROW ? N : 1];       // NARROW: shift and mask; else the packed word of SeedShape::run_wide
+    int nruns, weight; uint64_t keymask;
+    __device__ __forceinline__ explicit SeedRuns(const SeedShape &sh) : nruns(sh.nruns), weight(sh.weight), keymask(sh.keymask)
+    {
+        m[0] = 0;
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            if constexpr (NARROW) { w[i] = sh.run_shift[i]; m[i] = sh.run_mask[i]; }
+            else w[i] = sh.run_wide[i];
+        }
+    }
+};
+// 2. K' = the seed's runs of digits, packed; forward mer = digit reverse of K', reverse mer = ~K' (masked).  The smaller one is the key,
+// strand = 1 when that is the reverse mer (a mer that is its own reverse complement: strand 0).  The loop over the runs is unrolled over the
+// whole table and left, wave-uniformly, after a group of SEED_RUN_GROUP runs: the table's zero entries behind the last run add nothing.
+template <bool NARROW>
+__device__ __forceinline__ MerKey canonical_mer(const WinDigits &d, const SeedRuns<NARROW> &R)
 {
     if constexpr (NARROW) {
         uint32_t kp = 0;
-        for (int i = 0; i < sh.nruns; i++) kp |= ((uint32_t)(d.lo >> sh.run_src[i]) & ((1u << sh.run_bits[i]) - 1u)) << sh.run_dst[i];
-        const uint32_t f = digit_reverse32(kp, sh.weight), r = (~kp) & (uint32_t)sh.keymask;
+#pragma unroll
+        for (int i = 0; i < SeedRuns<NARROW>::N; i++) {
+            if (i && i % SEED_RUN_GROUP == 0 && i >= R.nruns) break;
+            kp |= (uint32_t)(d.lo >> R.w[i]) & R.m[i];
+        }
+        const uint32_t f = digit_reverse32(kp, R.weight), r = (~kp) & (uint32_t)R.keymask;
         return {r < f ? r : f, r < f};
     } else {
         uint64_t kp = 0;
-        for (int i = 0; i < sh.nruns; i++) kp |= bits_from128(d.lo, d.hi, sh.run_src[i], sh.run_bits[i]) << sh.run_dst[i];
-        const uint64_t f = digit_reverse(kp, sh.weight), r = (~kp) & sh.keymask;
+#pragma unroll
+        for (int i = 0; i < SeedRuns<NARROW>::N; i++) {
+            if (i && i % SEED_RUN_GROUP == 0 && i >= R.nruns) break;
+            // The word is unpacked here, by the scalar unit (it is wave-uniform), for every window anew: the empty statement keeps the compiler
+            // from moving the unpacked values -- nine scalars a run -- in front of the window loops, where they do not fit the scalar
+            // registers (more than 200 of them spilled into vector lanes).
+            uint32_t w = R.w[i];
+            asm volatile("" : "+s"(w));
+            const uint32_t s = w & 0xffu, dst = (w >> 8) & 0xffu, bits = w >> 16;
+            const uint64_t mask = ((1ULL << bits) - 1ULL) << dst;                                        // bits <= 62
+            const bool up = s >= 64; const int r = (int)(s & 63u);
+            const uint64_t a = up ? d.hi : d.lo, b = up ? 0ULL : d.hi;
+            kp |= ((a >> r) | ((b << 1) << (63 - r))) & mask;                                            // bits [s, s + 64) of hi:lo
+        }
+        const uint64_t f = digit_reverse(kp, R.weight), r = (~kp) & R.keymask;
         return {r < f ? r : f, r < f};
     }
 }
 template <bool NARROW>
-__device__ __forceinline__ MerKey mer_at(const uint64_t *__restrict__ G, uint32_t p, const SeedShape &sh) { return canonical_mer<NARROW>(window_digits<NARROW>(G, p), sh); }
+__device__ __forceinline__ MerKey mer_at(const uint64_t *__restrict__ G, uint32_t p, const SeedRuns<NARROW> &R) { return canonical_mer<NARROW>(window_digits<NARROW>(G, p), R); }
 
 // genome of a global window index.  gpos_off[i] for i > nseq is all ones (build_tab), so up to eight genomes need no
 // loop: seven compares against values the scalar unit loads once per kernel.
@@ -100,6 +130,24 @@ __device__ __forceinline__ int genome_of(uint32_t gpos, const GenomeTab &t)
     } else
         for (int i = 1; i < t.nseq; i++) g += (gpos >= t.gpos_off[i]) ? 1 : 0;
     return g;
+}
+// ... and that genome's window range [lo, hi) and first packed word.  Up to eight genomes: the same seven compares pick the three values out
+// of the scalar copies of the table, no memory access (indexed by a lane's genome, they are gathers from the kernel-argument segment that
+// the window's own loads wait for); above eight, the indexed form.
+struct GenomeAt { int g; uint32_t lo, hi, word; };               // (word: below 2^32, build_tab -- half the scalars and selects of the 64-bit offset)
+__device__ __forceinline__ GenomeAt genome_at(uint32_t gpos, const GenomeTab &t)
+{
+    if (t.nseq <= 8) {
+        GenomeAt a = {0, t.gpos_off[0], t.gpos_off[1], (uint32_t)t.word_off[0]};
+#pragma unroll
+        for (int i = 1; i < 8; i++) {
+            const bool in = gpos >= t.gpos_off[i];
+            a.g += in ? 1 : 0; a.lo = in ? t.gpos_off[i] : a.lo; a.hi = in ? t.gpos_off[i + 1] : a.hi; a.word = in ? (uint32_t)t.word_off[i] : a.word;
+        }
+        return a;
+    }
+    const int g = genome_of(gpos, t);
+    return {g, t.gpos_off[g], t.gpos_off[g + 1], (uint32_t)t.word_off[g]};
 }
 
 // A sort value: global window index | strand flag.  The narrow form (uint32_t) keeps the flag in bit 31, so a pass over it holds fewer

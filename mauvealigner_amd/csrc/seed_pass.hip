@@ -50,17 +50,18 @@ __global__ void __launch_bounds__(256) seed_extract(const uint64_t *__restrict__
                                                     ValT *__restrict__ vals, uint32_t out_base,
                                                     const uint32_t *__restrict__ seg, uint32_t nseg)
 {
-    uint32_t n = tab.nwin[g];
+    const uint32_t n = tab.nwin[g], goff = tab.gpos_off[g];
     const uint64_t *G = packed + tab.word_off[g];
+    const SeedRuns<false> runs(sh);
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
-        const MerKey m = mer_at<false>(G, p, sh);
+        const MerKey m = mer_at<false>(G, p, runs);
         uint64_t key = m.key;
         if (SEG) {
             uint32_t k;
             key = window_segment(seg, nseg, g, p, sh.span, &k) ? (((uint64_t)k << (2 * sh.weight)) | key) : ~0ULL;
         }
         keys[out_base + p] = (KeyT)key;
-        vals[out_base + p] = win_make<ValT>(tab.gpos_off[g] + p, m.strand);
+        vals[out_base + p] = win_make<ValT>(goff + p, m.strand);
     }
 }
 
@@ -87,16 +88,18 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
     if (threadIdx.x < 4096 / 32) sb[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * 4096u;
+    const SeedRuns<NARROW> runs(sh);
 #pragma unroll 2
     for (int i = 0; i < 4; i++) {
         const uint32_t gp0 = base + i * 1024 + threadIdx.x * 4;
         if (gp0 >= P) break;
-        const int g0 = genome_of(gp0, tab);
-        const bool together = gp0 + 3 < P && gp0 + 3 < tab.gpos_off[g0 + 1];       // all four in the buffer and in one genome
+        const GenomeAt at0 = genome_at(gp0, tab);
+        const int g0 = at0.g;
+        const bool together = gp0 + 3 < P && gp0 + 3 < at0.hi;                        // all four in the buffer and in one genome
         uint64_t key[4]; uint32_t sf[4];
         if (together) {
-            const uint32_t p0 = gp0 - tab.gpos_off[g0];
-            const uint64_t *G = packed + tab.word_off[g0];
+            const uint32_t p0 = gp0 - at0.lo;
+            const uint64_t *G = packed + at0.word;
             const uint32_t q = p0 >> 5; const int r0 = (p0 & 31) * 2;                 // p0 is a multiple of 4 only relative to gp0: r0 is any even offset
             const uint64_t w0 = G[q], w1 = G[q + 1], w2 = G[q + 2], w3 = NARROW ? 0ULL : G[q + 3];
 #pragma unroll
@@ -104,7 +107,7 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 const int r = r0 + 2 * j;                                             // 0 .. 68
                 uint64_t a0 = w0, a1 = w1, a2 = w2; int rr = r;
                 if (r >= 64) { a0 = w1; a1 = w2; a2 = w3; rr = r - 64; }
-                const MerKey m = canonical_mer<NARROW>({funnel64(a0, a1, rr), NARROW ? 0ULL : funnel64(a1, a2, rr)}, sh);
+                const MerKey m = canonical_mer<NARROW>({funnel64(a0, a1, rr), NARROW ? 0ULL : funnel64(a1, a2, rr)}, runs);
                 key[j] = m.key; sf[j] = m.strand;
             }
         } else {
@@ -113,8 +116,8 @@ __global__ void __launch_bounds__(256) seed_extract_all(const uint64_t *__restri
                 const uint32_t gp = gp0 + j;
                 key[j] = ~0ULL; sf[j] = 0;
                 if (gp >= P) continue;
-                const int g = genome_of(gp, tab);
-                const MerKey m = mer_at<NARROW>(packed + tab.word_off[g], gp - tab.gpos_off[g], sh);
+                const GenomeAt at = genome_at(gp, tab);
+                const MerKey m = mer_at<NARROW>(packed + at.word, gp - at.lo, runs);
                 key[j] = m.key; sf[j] = m.strand;
             }
         }
@@ -214,11 +217,12 @@ __global__ void __launch_bounds__(256) seed_extract_compact(const uint64_t *__re
     for (int i = 0; i < 16; i++) ok |= (window_valid(first + i, P, tab, sh.span, vmask, cmask) ? 1u : 0u) << i;
     uint32_t total;
     uint32_t o = tile_off[blockIdx.x] + block_excl_scan((uint32_t)__popc(ok), &total, lds);
+    const SeedRuns<NARROW> runs(sh);
     for (int i = 0; i < 16; i++) {
         if (!(ok >> i & 1)) continue;
         const uint32_t gp = first + i;
-        const int g = genome_of(gp, tab);
-        const MerKey m = mer_at<NARROW>(packed + tab.word_off[g], gp - tab.gpos_off[g], sh);
+        const GenomeAt at = genome_at(gp, tab);
+        const MerKey m = mer_at<NARROW>(packed + at.word, gp - at.lo, runs);
         keys[o] = (KeyT)m.key; vals[o] = win_make<ValT>(gp, m.strand);
         o++;
     }
@@ -486,30 +490,24 @@ __global__ void __launch_bounds__(256) pass_clear(uint32_t *__restrict__ t, uint
 constexpr int TJ_SLOTS = 16384;                  // 128 KB of LDS: key word + genome sets per slot
 constexpr int TJ_MAX = 9216;                     // load factor <= 0.5625
 constexpr int TJ_ROWS = TJ_MAX / 1024;
-template <bool LOCAL = false>
-__global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh, uint32_t P,
-                                                  const uint64_t *__restrict__ vmask, const uint64_t *__restrict__ cmask, int mode, uint32_t want_mask,
-                                                  uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos, uint32_t *__restrict__ err_cnt,
-                                                  const uint32_t *__restrict__ seg, uint32_t nseg, uint32_t *__restrict__ counters, uint32_t clr_lo, uint32_t clr_hi)
+constexpr uint32_t TJ_EMPTY = 0xffffffffu;       // never a canonical mer (the smaller of a mer and its reverse complement)
+// the thread's windows, one per row: key (TJ_EMPTY: no valid window), hit-table word and genome bit
+template <bool LOCAL, bool NARROW>
+__device__ __forceinline__ void tiny_extract(const uint64_t *__restrict__ packed, const GenomeTab &tab, const SeedShape &sh, uint32_t P,
+                                             const uint64_t *__restrict__ vmask, const uint64_t *__restrict__ cmask, const uint32_t *__restrict__ seg,
+                                             uint32_t nseg, int tid, uint32_t (&key)[TJ_ROWS], uint32_t (&v)[TJ_ROWS], uint32_t (&gbit)[TJ_ROWS])
 {
-    extern __shared__ uint32_t tj_lds[];
-    uint32_t *skey = tj_lds, *som = tj_lds + TJ_SLOTS;
-    constexpr uint32_t EMPTY = 0xffffffffu;       // never a canonical mer (the smaller of a mer and its reverse complement)
-    const int tid = threadIdx.x;
-    // the pass's clears, here instead of two 5 us fill launches: the counter block and the slice of the hit table (the barriers below order them
-    // before this workgroup's own stores to the table)
-    if (counters && tid < 16) counters[tid] = 0;
-    for (uint32_t i = clr_lo + tid; i < clr_hi; i += 1024) tmask[i] = 0;
-    for (int i = tid; i < TJ_SLOTS; i += 1024) { skey[i] = EMPTY; som[i] = 0; }
-    uint32_t v[TJ_ROWS], slot[TJ_ROWS], gbit[TJ_ROWS], key[TJ_ROWS];
+    const SeedRuns<NARROW> runs(sh);
 #pragma unroll
     for (int r = 0; r < TJ_ROWS; r++) {
         const uint32_t gp = (uint32_t)r * 1024u + (uint32_t)tid;
-        key[r] = EMPTY; v[r] = 0; gbit[r] = 0;
-        if (!window_valid(gp, P, tab, sh.span, vmask, cmask)) continue;
-        const int g = genome_of(gp, tab);
-        const uint32_t p = gp - tab.gpos_off[g];
-        const MerKey m = seed_narrow(sh) ? mer_at<true>(packed + tab.word_off[g], p, sh) : mer_at<false>(packed + tab.word_off[g], p, sh);
+        key[r] = TJ_EMPTY; v[r] = 0; gbit[r] = 0;
+        if (gp >= P) continue;
+        const GenomeAt at = genome_at(gp, tab);
+        const int g = at.g;
+        const uint32_t p = gp - at.lo;
+        if (window_blocked(vmask ? vmask + tab.mask_off[g] : nullptr, cmask ? cmask + tab.mask_off[g] : nullptr, p, sh.span)) continue;      // (window_valid, the genome looked up once)
+        const MerKey m = mer_at<NARROW>(packed + at.word, p, runs);
         uint32_t k = (uint32_t)m.key;
         if (seg) {                                  // segmented set (a batch of recursion gaps): the gap id rides above the mer, no window across gaps
             uint32_t sk;
@@ -518,6 +516,26 @@ __global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ p
         }
         key[r] = k; v[r] = (LOCAL ? p : gp) | (m.strand << 31); gbit[r] = 1u << g;
     }
+}
+template <bool LOCAL = false>
+__global__ void __launch_bounds__(1024) tiny_join(const uint64_t *__restrict__ packed, GenomeTab tab, SeedShape sh, uint32_t P,
+                                                  const uint64_t *__restrict__ vmask, const uint64_t *__restrict__ cmask, int mode, uint32_t want_mask,
+                                                  uint32_t *__restrict__ tmask, uint32_t *__restrict__ tpos, uint32_t *__restrict__ err_cnt,
+                                                  const uint32_t *__restrict__ seg, uint32_t nseg, uint32_t *__restrict__ counters, uint32_t clr_lo, uint32_t clr_hi)
+{
+    extern __shared__ uint32_t tj_lds[];
+    uint32_t *skey = tj_lds, *som = tj_lds + TJ_SLOTS;
+    constexpr uint32_t EMPTY = TJ_EMPTY;
+    const int tid = threadIdx.x;
+    // the pass's clears, here instead of two 5 us fill launches: the counter block and the slice of the hit table (the barriers below order them
+    // before this workgroup's own stores to the table)
+    if (counters && tid < 16) counters[tid] = 0;
+    for (uint32_t i = clr_lo + tid; i < clr_hi; i += 1024) tmask[i] = 0;
+    for (int i = tid; i < TJ_SLOTS; i += 1024) { skey[i] = EMPTY; som[i] = 0; }
+    uint32_t v[TJ_ROWS], slot[TJ_ROWS], gbit[TJ_ROWS], key[TJ_ROWS];
+    // (one run table at a time: the two of them together do not fit the scalar registers)
+    if (seed_narrow(sh)) tiny_extract<LOCAL, true>(packed, tab, sh, P, vmask, cmask, seg, nseg, tid, key, v, gbit);
+    else tiny_extract<LOCAL, false>(packed, tab, sh, P, vmask, cmask, seg, nseg, tid, key, v, gbit);
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < TJ_ROWS; r++) {
@@ -1077,14 +1095,17 @@ bool make_seed_shape(uint64_t pattern, SeedShape *sh)
         if (((pattern >> t) & 1) != ((pattern >> (span - 1 - t)) & 1)) return false;
     if (!(pattern & 1)) return false;
     sh->span = span; sh->weight = w; sh->keymask = (1ULL << (2 * w)) - 1ULL;
+    const bool narrow = seed_narrow(*sh);
     int j = 0, nr = 0;
     for (int t = 0; t < span;) {
         if (!((pattern >> (span - 1 - t)) & 1)) { t++; continue; }
         int t0 = t;
         while (t < span && ((pattern >> (span - 1 - t)) & 1)) t++;
         int len = t - t0;
-        if (nr >= 32) return false;
-        sh->run_src[nr] = (uint8_t)(2 * t0); sh->run_bits[nr] = (uint8_t)(2 * len); sh->run_dst[nr] = (uint8_t)(2 * j);
+        if (nr >= (narrow ? SEED_RUNS_NARROW : SEED_RUNS_MAX)) return false;       // (cannot happen: runs are at least two offsets apart)
+        const uint32_t shift = (uint32_t)(2 * (t0 - j));
+        if (narrow) { sh->run_shift[nr] = shift; sh->run_mask[nr] = (uint32_t)(((1ULL << (2 * len)) - 1ULL) << (2 * j)); }
+        sh->run_wide[nr] = shift | (uint32_t)(2 * j) << 8 | (uint32_t)(2 * len) << 16;
         nr++; j += len;
     }
     sh->nruns = nr;
@@ -1105,6 +1126,7 @@ static int build_tab(mauve_ctx *ctx, const GenomeSet &gs, int span, GenomeTab *t
         tab->gpos_off[g] = (uint32_t)tot; tab->nwin[g] = (uint32_t)nw; tab->word_off[g] = gs.word_off[g];
         tab->mask_off[g] = (gs.vmask || gs.cmask) ? gs.mask_off[g] : 0;
         tot += nw;
+        if (gs.word_off[g] >> 32) { ctx->err = "seed pass: a genome starts 2^32 words or more into its buffer"; return MAUVE_ERR_LIMIT; }     // (genome_at; the total limit below keeps every set far under it)
         if (gs.lens[g] >= MAUVE_MAX_GENOME_LEN) { ctx->err = "seed pass: a genome holds 2^31 bases or more (per-genome limit)"; return MAUVE_ERR_LIMIT; }
         if (tot >= MAUVE_MAX_TOTAL_LEN) { ctx->err = "seed pass: the genomes together hold 2^32 - 2^20 windows or more (total limit)"; return MAUVE_ERR_LIMIT; }
     }
