@@ -335,13 +335,28 @@ __device__ __forceinline__ uint32_t chunk_bound(const KeyT *__restrict__ keys, u
     const uint32_t start = c * (uint32_t)HJ_T;
     if (c == 0) return 0u;
     if (start >= n) return n;
-    const uint64_t h0 = (uint64_t)keys[start - 1] >> L;                  // the bucket the edge falls into (or just behind)
-    uint32_t res = HJ_NONE;
-    for (int step = 0; step < 4 && res == HJ_NONE; step++) {              // 256 entries, 64 per probe
+    // 256 entries, 64 per probe, in two steps: the first probe together with the edge's own entry, then -- no boundary there -- the loads of
+    // the other three together (a bucket of a few hundred entries has its boundary two or three probes out: one probe after the other, that
+    // was as many dependent round trips).  An index at or past n is clamped for the load and counts as a boundary; the first boundary in
+    // probe order is taken.  (All four at once costs the lists with short buckets three probes of traffic they never look at: measured,
+    // profiles/run_tiles_summary.md.)
+    auto probe = [&](int step, KeyT k, uint64_t h0) -> uint32_t {
         const uint32_t idx = start + (uint32_t)step * 64u + (uint32_t)lane;
-        const bool bnd = idx >= n || ((uint64_t)keys[idx] >> L) != h0;
-        const uint64_t b = __ballot(bnd);
-        if (b) res = start + (uint32_t)step * 64u + (uint32_t)(__ffsll((unsigned long long)b) - 1);
+        const uint64_t b = __ballot(idx >= n || ((uint64_t)k >> L) != h0);
+        return b ? start + (uint32_t)step * 64u + (uint32_t)(__ffsll((unsigned long long)b) - 1) : HJ_NONE;
+    };
+    const KeyT k0 = keys[min(start + (uint32_t)lane, n - 1u)];
+    const uint64_t h0 = (uint64_t)keys[start - 1] >> L;                  // the bucket the edge falls into (or just behind)
+    uint32_t res = probe(0, k0, h0);
+    if (res == HJ_NONE) {
+        KeyT k[4];
+#pragma unroll
+        for (int step = 1; step < 4; step++) k[step] = keys[min(start + (uint32_t)step * 64u + (uint32_t)lane, n - 1u)];
+#pragma unroll
+        for (int step = 3; step >= 1; step--) {
+            const uint32_t r = probe(step, k[step], h0);
+            if (r != HJ_NONE) res = r;
+        }
     }
     if (res == HJ_NONE) {
         // long bucket: first index in (lo, hi] whose high bits differ (keys[lo] still belongs to the bucket, index n counts)
@@ -699,10 +714,11 @@ __global__ void __launch_bounds__(256) enum_write(const KeyT *__restrict__ keys,
 // same-mask hit on the same diagonal at p-d, d <= span, cannot be the leftmost hit of its cluster (the
 // left walk of S4 never jumps over an agreeing offset, and that hit agrees).  Everything else is a
 // candidate for phase B.  all != 0 (no extension): every hit is a candidate.
-constexpr int RUNS_ITEMS = 16;
-constexpr uint32_t RUNS_TILE = 256u * RUNS_ITEMS, RUNS_HALO = 64 /* >= MAUVE_MAX_SEED_SPAN */;
+// The windows a thread takes (ITEMS: 4, 8 or 16; a tile is 256 * ITEMS windows) are chosen per launch, runs_items below: a tile ends in one
+// returning atomic on one counter, which the largest launches must keep rare, and the small ones need more workgroups than 4096 windows each give.
+constexpr uint32_t RUNS_HALO = 64 /* >= MAUVE_MAX_SEED_SPAN */;
+constexpr uint32_t runs_tile(int items) { return 256u * (uint32_t)items; }
 static_assert(RUNS_HALO >= MAUVE_MAX_SEED_SPAN && RUNS_HALO == 64, "mum_runs looks back at most one span, and reads the mask word 64 positions in front of every lane");
-static_assert(RUNS_ITEMS <= 32, "one bit per item in the hit / pending / flag words");
 
 // same generalized diagonal: every component of hit p sits d windows after (forward) / before (reverse) the
 // corresponding component of hit q = p - d, with the same relative strands
@@ -721,12 +737,14 @@ __device__ __forceinline__ bool same_diagonal(const uint32_t *__restrict__ rp, c
     return true;
 }
 
-template <bool SEG>
+template <bool SEG, int RUNS_ITEMS>
 __device__ __forceinline__ void mum_runs_body(const GenomeTab &tab, int span, const uint32_t *__restrict__ tmask,
                                               const uint32_t *__restrict__ tpos, uint32_t P, int all,
                                               uint32_t *__restrict__ cand, uint32_t *__restrict__ counters,
                                               const uint32_t *__restrict__ seg, uint32_t nseg, uint32_t p0, uint32_t cand_cap)
 {
+    static_assert(RUNS_ITEMS >= 1 && RUNS_ITEMS <= 32, "one bit per item in the hit / pending / flag words");
+    constexpr uint32_t RUNS_TILE = runs_tile(RUNS_ITEMS);
     __shared__ uint32_t lds[8];
     __shared__ uint32_t s_base;
     __shared__ uint32_t s_mask[RUNS_HALO + RUNS_TILE];
@@ -794,7 +812,7 @@ __device__ __forceinline__ void mum_runs_body(const GenomeTab &tab, int span, co
         // (32-bit offsets from a wave-uniform base keep the sixteen address pairs out of the register file)
         const uint32_t base_h = base >= RUNS_HALO ? base - RUNS_HALO : 0u;
         const uint32_t *tb = tpos + (size_t)base_h * N;
-        constexpr int RB = 8;                                 // items per batch of loads
+        constexpr int RB = RUNS_ITEMS < 8 ? RUNS_ITEMS : 8;   // items per batch of loads
 #pragma unroll
         for (int i0 = 0; i0 < RUNS_ITEMS; i0 += RB) {
             if (!__any((pend >> i0) & ((1u << RB) - 1u))) continue;
@@ -850,23 +868,24 @@ __device__ __forceinline__ void mum_runs_body(const GenomeTab &tab, int span, co
     for (int it = 0; it < RUNS_ITEMS; it++)
         if (flags >> it & 1) { if (o < cand_cap) cand[o] = base + it * 256 + threadIdx.x; o++; }     // never past the list: counters[1] still counts, the host refuses a list that outgrew its buffer
 }
-template <bool SEG>
+template <bool SEG, int ITEMS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) mum_runs(GenomeTab tab, int span, const uint32_t *__restrict__ tmask,
                                                 const uint32_t *__restrict__ tpos, uint32_t P, int all,
                                                 uint32_t *__restrict__ cand, uint32_t *__restrict__ counters,
                                                 const uint32_t *__restrict__ seg, uint32_t nseg, uint32_t cand_cap, uint32_t p0 = 0)
 {
-    mum_runs_body<SEG>(tab, span, tmask, tpos, P, all, cand, counters, seg, nseg, p0, cand_cap);
+    mum_runs_body<SEG, ITEMS>(tab, span, tmask, tpos, P, all, cand, counters, seg, nseg, p0, cand_cap);
 }
 // Several passes of the pairwise finder at once: pairs with DIFFERENT lower genomes write disjoint slices of the hit table, so a group of
 // them shares the table, one candidate list and one counter (mum_extend tells the pairs apart by the hit's mask).  blockIdx.y = pair.
 struct PairGroup { int n; int ga[MAUVE_MAX_SEQ], gb[MAUVE_MAX_SEQ]; uint32_t lo[MAUVE_MAX_SEQ], hi[MAUVE_MAX_SEQ]; };
+template <int ITEMS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) mum_runs_group(GenomeTab tab, int span, const uint32_t *__restrict__ tmask, const uint32_t *__restrict__ tpos, PairGroup grp, int all,
                                                       uint32_t *__restrict__ cand, uint32_t *__restrict__ counters, uint32_t cand_cap)
 {
     const uint32_t lo = grp.lo[blockIdx.y], hi = grp.hi[blockIdx.y];
-    if (lo + blockIdx.x * RUNS_TILE >= hi) return;                     // (workgroup-uniform: the grid covers the longest slice)
-    mum_runs_body<false>(tab, span, tmask, tpos, hi, all, cand, counters, nullptr, 0u, lo, cand_cap);
+    if (lo + blockIdx.x * runs_tile(ITEMS) >= hi) return;              // (workgroup-uniform: the grid covers the longest slice)
+    mum_runs_body<false, ITEMS>(tab, span, tmask, tpos, hi, all, cand, counters, nullptr, 0u, lo, cand_cap);
 }
 template <typename ValT = uint32_t>
 __global__ void __launch_bounds__(256) join_pair_group(const ValT *__restrict__ vals, GenomeTab tab, const uint32_t *__restrict__ rstart,
@@ -1073,6 +1092,8 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
 bool seed_trace_on() { static const bool v = getenv("MAUVE_TRACE") != nullptr; return v; }
 // a pass of a few thousand windows takes the hash join like any other
 static bool no_tiny() { static const bool v = getenv("MAUVE_NO_TINY") != nullptr; return v; }
+// MAUVE_RUNS_ITEMS=4|8|16: that mum_runs / mum_runs_group instantiation for every launch (0: the rule, runs_items)
+static int runs_items_env() { static const int v = [] { const char *e = getenv("MAUVE_RUNS_ITEMS"); const int x = e ? atoi(e) : 0; return x == 4 || x == 8 || x == 16 ? x : 0; }(); return v; }
 // shrinks the compacted lists so that the capacity checks can be seen to fire (0: off)
 static uint32_t list_cap_env() { static const uint32_t v = getenv("MAUVE_LIST_CAP") ? (uint32_t)strtoul(getenv("MAUVE_LIST_CAP"), nullptr, 10) : 0u; return v; }
 // candidates from which the canonical order is made on the device (below: the host sorts; tests force the device path)
@@ -1411,15 +1432,38 @@ static WinRange anchor_range(const GenomeTab &tab, uint32_t P, const FinderPass 
     return r;
 }
 
+// Windows per thread of a run-detection launch over `windows` windows (the longest slice of a pair group), from that size and the
+// device's compute units alone.  Measured per launch size in profiles/run_tiles_summary.md: 16 (tiles of 4096) only where a compute unit
+// has RUNS_CU_16 windows or more -- there the one counter every tile ends on is the limit, and a smaller tile doubles the atomics on it;
+// 8 from RUNS_CU_8 windows per compute unit; 4 below, where tiles of 4096 windows leave most of the device without a workgroup.
+constexpr uint64_t RUNS_CU_16 = 131072, RUNS_CU_8 = 6144;
+static int runs_items(const mauve_ctx *ctx, uint64_t windows)
+{
+    if (const int forced = runs_items_env()) return forced;
+    const uint64_t per_cu = windows / (uint64_t)std::max(ctx->cus, 1);
+    return per_cu >= RUNS_CU_16 ? 16 : (per_cu >= RUNS_CU_8 ? 8 : 4);
+}
+// f(std::integral_constant<int, ITEMS>) for the instantiation that runs_items chose
+template <typename F>
+static void with_runs_items(int items, F &&f)
+{
+    if (items == 16) f(std::integral_constant<int, 16>());
+    else if (items == 8) f(std::integral_constant<int, 8>());
+    else f(std::integral_constant<int, 4>());
+}
+
 // extension phase A: run starts from the windows [r.lo, r.hi) of the hit table
 template <bool SEG>
 static int launch_runs(SeedState &st, WinRange r)
 {
     mauve_ctx *ctx = st.ctx;
     { KernelTimer t(ctx, MAUVE_K_RUNS, r.hi - r.lo);
-      hipLaunchKernelGGL((mum_runs<SEG>), dim3((r.hi - r.lo + RUNS_TILE - 1) / RUNS_TILE), dim3(256), 0, ctx->stream, st.tab,
-                         st.sh.span, st.tmask, st.tpos, r.hi, st.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), st.rq.seg,
-                         st.rq.nseg, st.cand_cap, r.lo); }
+      with_runs_items(runs_items(ctx, r.hi - r.lo), [&](auto items) {
+          constexpr int ITEMS = decltype(items)::value;
+          hipLaunchKernelGGL((mum_runs<SEG, ITEMS>), dim3((r.hi - r.lo + runs_tile(ITEMS) - 1) / runs_tile(ITEMS)), dim3(256), 0, ctx->stream, st.tab,
+                             st.sh.span, st.tmask, st.tpos, r.hi, st.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), st.rq.seg,
+                             st.rq.nseg, st.cand_cap, r.lo);
+      }); }
     HIPCHK(ctx, hipGetLastError());
     return MAUVE_OK;
 }
@@ -1513,8 +1557,11 @@ static int pairwise_passes(SeedPass<KeyT, ValT> &ps)
         HIPCHK(ctx, hipGetLastError());
         seed_trace(ctx, "join", ps.trace_t0);
         { KernelTimer t(ctx, MAUVE_K_RUNS, slices);
-          hipLaunchKernelGGL(mum_runs_group, dim3((maxslice + RUNS_TILE - 1) / RUNS_TILE, (uint32_t)grp.n), dim3(256), 0, ctx->stream, tab, ps.sh.span, ps.tmask, ps.tpos, grp,
-                             ps.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), ps.cand_cap); }
+          with_runs_items(runs_items(ctx, maxslice), [&](auto items) {
+              constexpr int ITEMS = decltype(items)::value;
+              hipLaunchKernelGGL(mum_runs_group<ITEMS>, dim3((maxslice + runs_tile(ITEMS) - 1) / runs_tile(ITEMS), (uint32_t)grp.n), dim3(256), 0, ctx->stream, tab, ps.sh.span, ps.tmask,
+                                 ps.tpos, grp, ps.rq.extend ? 0 : 1, ctx->cand.as<uint32_t>(), ctx->counters.as<uint32_t>(), ps.cand_cap);
+          }); }
         HIPCHK(ctx, hipGetLastError());
         if (ctx->shadow) { std::function<void()> f; f.swap(ctx->shadow); f(); }
         if (int rc = seed_counters(ctx, 16, &cw)) return rc;
