@@ -792,10 +792,11 @@ int chain_device_core(mauve_ctx *c, int N, int64_t min_weight, bool collinear, i
 // list on the virtual genomes.  Overlap elimination of the whole list equals the elimination gap by gap (matches of
 // different gaps lie in different segments of every virtual genome, so they never share an overlap cluster), the LCB
 // nodes are confined to their gaps, and the collinear rule (one collinear chain per gap) runs on the host
-// per gap over the compact graph -- nearly every gap has a single node.  Out: cropped records (hl, hs: int32, list
-// order) and survive[i] for every match of the list.
+// per gap over the compact graph -- nearly every gap has a single node.  Every record and the graph come back; out, as
+// from chain_device_gaps_compact: the SURVIVORS' cropped records (hl, hs: int32) and the gap of each (hgap: the segment
+// of its genome-0 start, ch_init_seg), in list order; *ns_out of them.
 int chain_device_gaps(mauve_ctx *c, int N, int64_t maxlen, const uint32_t *seg0_dev, uint32_t nseg, const int32_t **hl_out, const int32_t **hs_out,
-                      std::vector<uint8_t> &survive)
+                      const uint32_t **hgap_out, uint32_t *ns_out)
 {
     ChainGraphHost G;
     {   // page-locked room for the graph (at most one node per match) AND the records behind it, before the graph lands there
@@ -845,9 +846,15 @@ int chain_device_gaps(mauve_ctx *c, int N, int64_t maxlen, const uint32_t *seg0_
             }
             n0 = n1;
         }
-        survive.assign((size_t)n, 0);
-        for (uint32_t i = 0; i < n; i++) survive[i] = hl[i] > 0 && node_ok[(size_t)hnode[i]];
-        *hl_out = hl; *hs_out = hs;
+        // the survivors to the front of the block, each array in its place: the write index never passes the read index
+        uint32_t ns = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            if (hl[i] <= 0 || !node_ok[(size_t)hnode[i]]) continue;
+            hl[ns] = hl[i]; hgap[ns] = hgap[i];
+            for (int g = 0; g < N; g++) hs[(size_t)ns * N + g] = hs[(size_t)i * N + g];
+            ns++;
+        }
+        *hl_out = hl; *hs_out = hs; *hgap_out = hgap; *ns_out = ns;
     }
     return MAUVE_OK;
 }

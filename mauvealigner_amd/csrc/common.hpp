@@ -501,7 +501,9 @@ int chain_device_gaps_compact(mauve_ctx *c, int N, int64_t maxlen, const uint32_
                               const uint32_t **hgap_out, uint32_t *ns_out);
 int chain_device_core(mauve_ctx *c, int N, int64_t min_weight, bool collinear, int64_t &n_lcb, const mauve_scoring *sp_scoring = nullptr);
 int chain_device_gaps(mauve_ctx *c, int N, int64_t maxlen, const uint32_t *seg0_dev, uint32_t nseg, const int32_t **hl_out, const int32_t **hs_out,
-                      std::vector<uint8_t> &survive);
+                      const uint32_t **hgap_out, uint32_t *ns_out);
+// recursive anchoring of the long gaps of `chains` (N genomes; gmap: their resident genomes, nullptr = 0 .. N-1), recursive.cpp
+int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector<MatchVec> &chains, int N, const int *gmap);
 int chain_device_copy_back(mauve_ctx *c, int N, MatchVec &m, std::vector<int64_t> &match_lcb);
 int chain_order_device(mauve_ctx *c, int N, int64_t nl, int64_t min_gap, int64_t *na_out, int64_t *n_rec_out);
 int extend_lcbs_device(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw, int N, const int32_t **alen_io, const int32_t **ast_io,

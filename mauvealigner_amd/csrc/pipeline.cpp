@@ -17,8 +17,6 @@ inline uint8_t base_at(const uint64_t *w, int64_t i) { return (uint8_t)((w[(size
 
 }  // namespace
 
-int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector<MatchVec> &chains, int N, const int *gmap);
-
 // LCB extension (lcb_extension, mauveAligner.cpp:95; SetMaxExtensionIterations :687-690), frozen replacement
 // up to max_extension_iters rounds, each with a seed two weights lighter than the last.  A round
 // searches N-way MEMs only where no LCB lies -- one masked seed pass over the resident genomes, the mask being the

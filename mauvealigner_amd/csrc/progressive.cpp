@@ -29,8 +29,6 @@
 #include <cstring>
 #include <map>
 
-int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector<MatchVec> &chains, int N, const int *gmap);
-
 namespace {
 
 const bool g_trace = getenv("MAUVE_TRACE") != nullptr;      // read once, not in the timed path

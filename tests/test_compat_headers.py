@@ -456,3 +456,16 @@ def test_host_chain_steps():
                         os.path.join(ROOT, "tests", "cpp", "host_chain_test.cpp"), "-o", exe], check=True)
         r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and r.stdout.strip() == "OK", r.stdout + r.stderr
+
+
+def test_recursion_host_steps():
+    """csrc/recursion_host.hpp (the pure steps of the recursive anchoring's host side): the map from a record inside a
+    gap to real coordinates on both strands, the writer and the parser of the sharded exchange's message with every
+    refusal and its text, and the in-place merge of new anchors into a chain, on hand cases with the expected numbers
+    written out.  Host-only C++, plain g++."""
+    with tempfile.TemporaryDirectory() as td:
+        exe = os.path.join(td, "recursion_host_test")
+        subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "mauvealigner_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "cpp", "recursion_host_test.cpp"), "-o", exe], check=True)
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout.strip() == "OK", r.stdout + r.stderr

@@ -518,7 +518,8 @@ print("OK")
 def test_recursion_gaps_chained_on_the_device():
     """The N-way matches of a whole recursion batch are overlap-eliminated and reduced to one collinear chain per gap on
     the device (chain_device_gaps), with the per-gap greedy step on the compact graph; MAUVE_HOST_GAP_CHAIN keeps the
-    host loop.  MAUVE_CANON_DEVICE_MIN=1 sends small lists down the device path too."""
+    host loop, MAUVE_GAP_CHAIN_ALL_BACK the device route that copies every record back.  MAUVE_CANON_DEVICE_MIN=1 sends
+    small lists down the device path too."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MAUVE_TRACE="1", MAUVE_CANON_DEVICE_MIN="1")
@@ -537,6 +538,14 @@ def test_recursion_gaps_chained_on_the_device():
     r = subprocess.run([sys.executable, "-c", GAPCHAIN_SCRIPT % {"root": root}], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr[-3000:]
     assert not [l for l in r.stderr.splitlines() if "per-gap chaining" in l and "(device" in l]
+    # the device route that copies every record and the graph back (chain_device_gaps: the fall-back of the survivors-only
+    # route), forced for every batch
+    del env["MAUVE_HOST_GAP_CHAIN"]
+    env["MAUVE_GAP_CHAIN_ALL_BACK"] = "1"
+    r = subprocess.run([sys.executable, "-c", GAPCHAIN_SCRIPT % {"root": root}], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr[-3000:]
+    assert len([l for l in r.stderr.splitlines() if "per-gap chaining" in l and "(device; " in l]) >= 4, r.stderr[-3000:]
+    assert not [l for l in r.stderr.splitlines() if "survivors only" in l], r.stderr[-3000:]
 
 
 def test_align_matches_given_list(ctx):
