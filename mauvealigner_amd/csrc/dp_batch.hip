@@ -817,19 +817,34 @@ __device__ __forceinline__ int32_t wave_prefix_sum(int32_t v)
 
 constexpr int DP3_R = 4, DP3_BAND = 64 * DP3_R;           // rows (A) / columns (B) of one band
 // rows (A) / columns (B) a lane holds: as few as cover the dimension with 64 lanes (a tiny problem keeps 4: fewer bytes)
-__host__ __device__ __forceinline__ int32_t dp3_rows_per_lane(int64_t x) { return x <= 32 ? 4 : (x <= 64 ? 1 : (x <= 128 ? 2 : 4)); }
+// (129..192 runs three: a line of the sweep costs its instruction count, and the fourth row of every lane would be a row of nothing)
+__host__ __device__ __forceinline__ constexpr int32_t dp3_rows_per_lane(int64_t x) { return x <= 32 ? 4 : (x <= 64 ? 1 : (x <= 128 ? 2 : (x <= 192 ? 3 : 4))); }
 // stride of a traceback line: four bytes per lane that holds something, in 16-byte units; whole bands beyond one
-__host__ __device__ __forceinline__ int64_t dp3_pad(int64_t x)
+__host__ __device__ __forceinline__ constexpr int64_t dp3_pad(int64_t x)
 {
     if (x > DP3_BAND) return (x + DP3_BAND - 1) / DP3_BAND * DP3_BAND;
     const int64_t R = dp3_rows_per_lane(x);
     return (4 * ((x + R - 1) / R) + 15) & ~(int64_t)15;
 }
 // ... and its largest value over all dimensions up to x (the host sizes for a bound of the profile length)
-__host__ __device__ __forceinline__ int64_t dp3_pad_bound(int64_t x) { return x <= 32 ? ((x + 15) & ~(int64_t)15) : (x <= DP3_BAND ? DP3_BAND : (x + DP3_BAND - 1) / DP3_BAND * DP3_BAND); }
-__host__ __device__ __forceinline__ bool dp3_orient_b(int64_t m, int64_t n)    // cost: steps x bands
+__host__ __device__ __forceinline__ constexpr int64_t dp3_pad_bound(int64_t x) { return x <= 32 ? ((x + 15) & ~(int64_t)15) : (x <= DP3_BAND ? DP3_BAND : (x + DP3_BAND - 1) / DP3_BAND * DP3_BAND); }
+// the host sizing (dp3_tb_need, DpSizing, dpf_size_desc) knows the bound only: no rule for the rows per lane may make a line longer than it
+constexpr bool dp3_pad_within_bound(int64_t upto) { for (int64_t x = 1; x <= upto; x++) if (dp3_pad(x) > dp3_pad_bound(x)) return false; return true; }
+static_assert(dp3_pad_within_bound(1024), "dp3_pad(x) <= dp3_pad_bound(x): the traceback of a step is sized by the bound");
+// Time per line of the one-wave sweeps with R = 1, 2, 3, 4 rows (orientation A) / columns (B) per lane, in units of 10 ns: single-interval launches on
+// an MI355X, the slope of the kernel time over the number of lines at a lane dimension of 64 R (tools/sweep/dp_line_cost.py; the raw figures are in
+// profiles/dp_rows_summary.md).  A line of B costs more than a line of A at every R -- it derives the profile row's coefficients and picks
+// a base per column -- so there is a row of the table per orientation.
+__host__ __device__ __forceinline__ constexpr int64_t dp3_line_cost(bool orient_b, int32_t R)
 {
-    return m * ((n + DP3_BAND - 1) / DP3_BAND) < (n + 1) * ((m + DP3_BAND - 1) / DP3_BAND);
+    return orient_b ? (R == 1 ? 52 : (R == 2 ? 54 : (R == 3 ? 62 : 66))) : (R == 1 ? 27 : (R == 2 ? 41 : (R == 3 ? 52 : 58)));
+}
+// The orientation of a step on one wave, by cost: lines x bands x time per line.  Both orientations compute the same cells with the same tie rules
+// for every interval dp3_admissible lets in (the invariant of the scan sweeps, above), so the choice changes the time of a step and nothing else.
+__host__ __device__ __forceinline__ constexpr bool dp3_orient_b(int64_t m, int64_t n)
+{
+    const int64_t ca = dp3_line_cost(false, m > DP3_BAND ? DP3_R : dp3_rows_per_lane(m)), cb = dp3_line_cost(true, n > DP3_BAND ? DP3_R : dp3_rows_per_lane(n));
+    return m * ((n + DP3_BAND - 1) / DP3_BAND) * cb < (n + 1) * ((m + DP3_BAND - 1) / DP3_BAND) * ca;
 }
 // traceback bytes of a step whose profile has at most m rows (either orientation), and parked boundary entries
 __host__ __device__ __forceinline__ int64_t dp3_tb_need(int64_t m, int64_t n)
@@ -1380,10 +1395,12 @@ __device__ __forceinline__ void dp3_sweep(const Dp3Walk &W, int lane, int32_t m,
     if (!W.orient_b) {
         if (W.R == 1) dp_sweep_a<1, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
         else if (W.R == 2) dp_sweep_a<2, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+        else if (W.R == 3) dp_sweep_a<3, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
         else dp_sweep_a<4, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
     } else {
         if (W.R == 1) dp_sweep_b<1, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
         else if (W.R == 2) dp_sweep_b<2, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
+        else if (W.R == 3) dp_sweep_b<3, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
         else dp_sweep_b<4, 1>(nullptr, lane, 0, m, n, Pc, seq, sc, krows, rowbuf, tbp, pad, alone, fM, fX, fY);
     }
 }
