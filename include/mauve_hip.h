@@ -707,6 +707,45 @@ void mauve_repeat_score_ppv(const mauve_repeat_score_totals *t, double out[4]);
 /* IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760; format mfa2xmfa.cpp:64-115).
    Two-phase: buf == NULL returns the needed size (including NUL) in *len. */
 int mauve_write_xmfa(mauve_ctx *ctx, const char *const *names, char *buf, int64_t *len);
+/* ---- the alignment as text, written on the device: IntervalList::WriteStandardAlignment (mauveAligner.cpp:746-760), the per-LCB files
+        of --output-alignment (mauveAligner.cpp:764-781) and the writing half of xmfa2maf (xmfa2maf.cpp:46-82), on the coordinate index in
+        force and the resident genomes.  Frozen form DESIGN.md S23.  Unlike mauve_write_xmfa it writes whatever the index describes -- the
+        context's result, a caller's alignment, a projection made the index in force -- and any column ranges of it.
+        Blocks: one per range (range_iv, range_col, range_len)[n_range], the form and the checks of mauve_extract_select; range_iv == NULL:
+        one per interval, all its columns.  They are written in the order given; overlapping ranges repeat text.
+        Rows: genome g (ascending) has a row in a block iff it has a residue in the range; with k0 / k1 residues of its interval row in
+        front of the range's first column / behind its last one, the row covers lo = left + k0 .. hi = left + k1 - 1, on the reverse
+        strand hi = right - k0, lo = right - k1 + 1.  The cells are the S15 cells.  A block without a row is left out whole.
+        MAUVE_TEXT_XMFA (wrap >= 1, default 80): "#FormatVersion Mauve1", per genome "#Sequence{g+1}File\t{names[g]}",
+          "#Sequence{g+1}Entry\t{g+1}", "#Sequence{g+1}Format\tFastA"; per row "> {g+1}:{lo}-{hi} {+|-} {deflines[g]}" and the cells in
+          lines of wrap; "=" behind a block's rows.  A NULL name is the empty string, deflines == NULL means names.  On whole intervals
+          of the context's result with wrap 80 these are the bytes of mauve_write_xmfa, without its trailing NUL.
+        MAUVE_TEXT_MAF (wrap = 0): "##maf version=1 program=progressiveMauve"; per block "a", per row
+          "s {src} {start} {size} {strand} {srcSize} {cells}", an empty line.  The contig table has the form of
+          mauve_set_genomes_contigs (n_contigs[g] 0-based ascending starts per genome, the first 0, concatenated in contig_starts; NULL:
+          every genome is one contig), contig_names flat in the same order or NULL.  src = names[g].contig_name, names[g] without contig
+          names; size = hi - lo + 1, srcSize = the contig's length, start = lo - contig start - 1, on the reverse strand srcSize minus the
+          local hi.  A row whose ends lie in different contigs makes the call return MAUVE_ERR_ARG (the text names the range and the
+          genome; no text is kept): split the ranges at the joins (the applyBreakpoints pass of the tool is not part of the call).
+        mauve_alignment_text lays the text out and writes it into a device buffer the context keeps: *n_bytes its length (int64: 2^31
+        bytes or more are legal), *n_blocks the blocks written.  mauve_alignment_text_fetch copies the slice [offset, offset + len) of it
+        (page-locked destinations directly; buf == NULL with len == 0 is legal) and block_off[n_range + 1] when asked: block r is the
+        bytes block_off[r] .. block_off[r + 1], block_off[0] the header's length, block_off[n_range] = n_bytes, equal neighbours for a
+        block left out.  Slices stream a large text through a small buffer; block_off cuts per-LCB files.
+        MAUVE_ERR_ARG: a bad format, wrap < 1 for XMFA, wrap != 0 or a contig table that does not ascend from 0 inside its genome for
+        MAF, a contig table for XMFA, the range errors of mauve_extract_select, a slice outside the text.  MAUVE_ERR_LIMIT: ranges x
+        (nseq + 2) of 2^31 or more.  MAUVE_ERR_STATE: as for mauve_extract_select; a fetch without a text -- a later
+        mauve_coord_index*, mauve_project_index, mauve_set_genomes* or text call ends the one before. ---- */
+#define MAUVE_TEXT_XMFA 0
+#define MAUVE_TEXT_MAF 1
+typedef struct { int32_t format; int32_t wrap; } mauve_text_params;
+void mauve_default_text_params(int format, mauve_text_params *p);             /* wrap 80 for XMFA, 0 for MAF */
+int mauve_alignment_text(mauve_ctx *ctx, const mauve_text_params *p, const char *const *names, const char *const *deflines,
+                         const int64_t *n_contigs, const int64_t *contig_starts, const char *const *contig_names,
+                         int64_t n_range, const int64_t *range_iv, const int64_t *range_col, const int64_t *range_len,
+                         int64_t *n_bytes, int64_t *n_blocks);
+int mauve_alignment_text_fetch(mauve_ctx *ctx, int64_t offset, int64_t len, char *buf,
+                               int64_t *block_off /* n_range+1 or NULL */);
 
 /* ---- measurement -------------------------------------------------------------------------------
    Per-kernel HIP-event timing on the context's stream (bench.py roofline).  Kernel ids: */

@@ -42,6 +42,7 @@ EXPORTS = [
     "mauve_repeat_matches", "mauve_repeat_fetch",
     "mauve_map_ranges", "mauve_map_ranges_fetch", "mauve_range_overlaps",
     "mauve_repeat_score", "mauve_repeat_score_ppv",
+    "mauve_default_text_params", "mauve_alignment_text", "mauve_alignment_text_fetch",
 ]
 
 
@@ -66,6 +67,13 @@ class HmmParams(C.Structure):
 
 class ExtractParams(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("keep", C.c_int32 * 32), ("require", C.c_uint32), ("drop_empty", C.c_int32), ("polymorphic", C.c_int32)]
+
+
+class TextParams(C.Structure):
+    _fields_ = [("format", C.c_int32), ("wrap", C.c_int32)]
+
+
+TEXT_XMFA, TEXT_MAF = 0, 1
 
 
 class ProjectParams(C.Structure):
@@ -1017,6 +1025,79 @@ class Context:
             require = sum(1 << int(g) for g in require)
         self.extract_select(keep, require, drop_empty, polymorphic, ranges)
         return self.extract_fetch(out)
+
+    # ---- the alignment as XMFA / MAF text ----
+    @staticmethod
+    def _c_strings(items):
+        """a list of str / bytes / None -> a char* array (None entries stay NULL); None -> NULL"""
+        if items is None:
+            return None
+        enc = [None if s is None else (s if isinstance(s, bytes) else str(s).encode()) for s in items]
+        return (C.c_char_p * max(len(enc), 1))(*enc)
+
+    def alignment_text(self, fmt="xmfa", names=None, deflines=None, contigs=None, contig_names=None, ranges=None, wrap=None):
+        """mauve_alignment_text: the text of the index in force (ranges as for extract_select, None = every interval whole) into a device
+        buffer the context keeps -> (n_bytes, n_blocks).  fmt "xmfa" (wrap: letters per line, None = 80) or "maf" (contigs: per genome
+        the 0-based contig starts, contig_names: per genome the names of its contigs; None = every genome is one contig)."""
+        if isinstance(fmt, str):
+            if fmt not in ("xmfa", "maf"):
+                raise ValueError("alignment_text: fmt is 'xmfa' or 'maf'")
+            fmt = TEXT_MAF if fmt == "maf" else TEXT_XMFA
+        N = self.nseq
+        for what, lst in (("names", names), ("deflines", deflines), ("contigs", contigs), ("contig_names", contig_names)):
+            if lst is not None and len(lst) != N:
+                raise ValueError("alignment_text: %s must have one entry per genome" % what)
+        p = TextParams()
+        self.L.mauve_default_text_params.restype = None
+        self.L.mauve_default_text_params(C.c_int(int(fmt)), C.byref(p))
+        if wrap is not None:
+            p.wrap = int(wrap)
+        n_c = c_st = None
+        if contigs is not None:
+            per = [np.ascontiguousarray(x, np.int64).reshape(-1) for x in contigs]
+            n_c = np.array([len(x) for x in per], np.int64)
+            c_st = np.concatenate(per + [np.zeros(1, np.int64)])
+        flat = None
+        if contig_names is not None:
+            if contigs is None:
+                raise ValueError("alignment_text: contig_names go with contigs")
+            flat = [s for per_g in contig_names for s in per_g]
+            if len(flat) != int(n_c.sum()):
+                raise ValueError("alignment_text: contig_names must name every contig")
+        n_range, args_r = self._range_args(ranges, "alignment_text")
+        nb, nk = C.c_int64(0), C.c_int64(0)
+        self._tx_shape = None
+        self.L.mauve_alignment_text.argtypes = [C.c_void_p, C.POINTER(TextParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        a_names, a_def, a_cn = self._c_strings(names), self._c_strings(deflines), self._c_strings(flat)
+        self._chk(self.L.mauve_alignment_text(self.h, C.byref(p), a_names, a_def, None if n_c is None else n_c.ctypes.data, None if c_st is None else c_st.ctypes.data, a_cn,
+                                              *args_r, C.byref(nb), C.byref(nk)), "mauve_alignment_text")
+        self._tx_shape = (nb.value, n_range)
+        return nb.value, nk.value
+
+    def alignment_text_fetch(self, offset=0, length=None, out=None, want_block_off=False):
+        """mauve_alignment_text_fetch: the slice [offset, offset + length) of the text in force (length None = to its end) -> bytes, or with
+        out (a uint8 array of at least that length, e.g. from pinned_empty: copied without staging) the view out[:length]; with
+        want_block_off -> (slice, block_off int64 [n_range + 1])"""
+        if getattr(self, "_tx_shape", None) is None:
+            n_bytes, n_range = 0, 0                                  # (the library refuses: no text in force)
+        else:
+            n_bytes, n_range = self._tx_shape
+        if length is None:
+            length = max(n_bytes - offset, 0)
+        length = int(length)
+        if out is None:
+            buf = np.empty(max(length, 1), np.uint8)
+        else:
+            buf = out
+            if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous or len(buf) < length:
+                raise ValueError("alignment_text_fetch: out must be a contiguous uint8 array of at least %d bytes" % length)
+        boff = np.zeros(n_range + 1, np.int64) if want_block_off else None
+        self.L.mauve_alignment_text_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        self._chk(self.L.mauve_alignment_text_fetch(self.h, C.c_int64(int(offset)), C.c_int64(length), buf.ctypes.data if length else None,
+                                                    boff.ctypes.data if want_block_off else None), "mauve_alignment_text_fetch")
+        res = buf[:length] if out is not None else buf[:length].tobytes()
+        return (res, boff) if want_block_off else res
 
     # ---- pairwise column statistics (DESIGN.md S16) ----
     def pair_stats(self, pairs=None, ranges=None, per_range=False, out=None):

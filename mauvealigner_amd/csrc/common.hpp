@@ -288,6 +288,10 @@ struct mauve_ctx {
         int64_t n_sel = 0, n_range = 0;
         int n_keep = 0; int32_t keep[MAUVE_MAX_SEQ] = {0};
     } ex;
+    // alignment text (text_dev.hip): the XMFA or MAF text of the last mauve_alignment_text stays on the device for its fetches, with
+    // block_off [n_range + 1]; it belongs to the index and the genomes it was made on (an index call clears `valid`, genome_gen tells an upload)
+    struct AlignText { bool valid = false; uint64_t genome_gen = 0; int64_t n_bytes = 0, n_range = 0, n_blocks = 0; } tx;
+    DevBuf tx_work, tx_rows, tx_text, tx_boff;  // the flag words, ranges and tables; row records, slot bytes and their scan; the text; block_off
     DevBuf ex_work, ex_bits, ex_sel, ex_mat;   // the flag word, ranges and their scan; selection words and their scan; sel_iv | sel_col | range_off; the matrix (padded pitch)
     // pairwise column statistics (pairstat_dev.hip): no state between calls, work buffers apart from the selection's
     DevBuf ps_work, ps_out;              // the flag word, ranges, their units' scan, the pair lists; the records

@@ -316,7 +316,7 @@ extern "C" {
 int mauve_coord_index(mauve_ctx *c)
 {
     if (!c) return MAUVE_ERR_ARG;
-    c->co.valid = false; c->ex.valid = false; c->exc.valid = false; c->fm.valid = false;      // (a selection, DESIGN.md S15, an excursion result, S18, and a range map, S21, belong to the index they were made on)
+    c->co.valid = false; c->ex.valid = false; c->exc.valid = false; c->fm.valid = false; c->tx.valid = false;      // (a selection, DESIGN.md S15, an excursion result, S18, a range map, S21, and a text, S23, belong to the index they were made on)
     AlnView A;
     if (const int rc = aln_from_context(c, "coord_index", false, c->bb_cols, &A)) return rc;
     if (const int rco = coord_check_offsets(c, "coord_index", A.n_iv, A.col_off)) return rco;
@@ -326,7 +326,7 @@ int mauve_coord_index(mauve_ctx *c)
 int mauve_coord_index_alignment(mauve_ctx *c, int nseq, int64_t n_iv, const int64_t *left, const int64_t *right, const int8_t *reverse, const int64_t *col_off, const uint32_t *cols)
 {
     if (!c) return MAUVE_ERR_ARG;
-    c->co.valid = false; c->ex.valid = false; c->exc.valid = false; c->fm.valid = false;      // (a selection, DESIGN.md S15, an excursion result, S18, and a range map, S21, belong to the index they were made on)
+    c->co.valid = false; c->ex.valid = false; c->exc.valid = false; c->fm.valid = false; c->tx.valid = false;      // (a selection, DESIGN.md S15, an excursion result, S18, a range map, S21, and a text, S23, belong to the index they were made on)
     return coord_index_arrays(c, "coord_index", c->co, c->co_index, nseq, n_iv, left, right, reverse, col_off, cols);
 }
 

@@ -370,7 +370,7 @@ int mauve_project_index(mauve_ctx *c)
     if (!R.valid) { c->err = "project_index: no projection in this context (mauve_project first)"; return MAUVE_ERR_STATE; }
     if (R.N != c->nseq) { c->err = "project_index: the projection is over " + std::to_string(R.N) + " genomes, the context holds " + std::to_string(c->nseq); return MAUVE_ERR_STATE; }
     if (R.genome_gen != c->genome_gen) { c->err = "project_index: the genomes were replaced after the projected index was built"; return MAUVE_ERR_STATE; }
-    c->co.valid = false; c->ex.valid = false; c->exc.valid = false; c->fm.valid = false;      // (a selection, DESIGN.md S15, an excursion result, S18, and a range map, S21, belong to the index they were made on)
+    c->co.valid = false; c->ex.valid = false; c->exc.valid = false; c->fm.valid = false; c->tx.valid = false;      // (a selection, DESIGN.md S15, an excursion result, S18, a range map, S21, and a text, S23, belong to the index they were made on)
     HIPCHK(c, hipSetDevice(c->device));
     return coord_index_device(c, "project_index", AlnView{R.N, R.n_iv, R.left.data(), R.right.data(), R.reverse.data(), R.col_off.data(), c->pj_cols.as<uint32_t>()});
 }
