@@ -12,6 +12,8 @@
  * text.  A context is thread-compatible (one thread at a time); there are no hidden globals.
  * Coordinates follow libMems: signed 1-based starts, negative = reverse strand, 0 = NO_MATCH
  * (SeedMatchEnumerator.h:83,127-141; sortContigs.cpp:46).
+ * Environment: the MAUVE_* switches are read once, when the process creates its first context; INTEGRATION.md,
+ * "Environment switches", lists them and says which few are part of the supported interface.
  */
 #ifndef MAUVE_HIP_H
 #define MAUVE_HIP_H

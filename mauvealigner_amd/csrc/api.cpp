@@ -263,8 +263,8 @@ int mauve_ctx_create(int device, mauve_ctx **out)
     mauve_ctx *c = new (std::nothrow) mauve_ctx();
     if (!c) { g_create_err = "out of host memory"; return MAUVE_ERR_ARG; }
     c->device = device;
-    if (const char *sp = getenv("MAUVE_SCHEDULE")) {            // A/B hook: how the host waits in hipStreamSynchronize (spin | yield | block)
-        const unsigned f = !strcmp(sp, "spin") ? hipDeviceScheduleSpin : !strcmp(sp, "yield") ? hipDeviceScheduleYield : hipDeviceScheduleBlockingSync;
+    if (const int sched = switches().schedule) {                // how the host waits in hipStreamSynchronize (the process's first call of switches(): the table is filled here)
+        const unsigned f = sched == 1 ? hipDeviceScheduleSpin : sched == 2 ? hipDeviceScheduleYield : hipDeviceScheduleBlockingSync;
         (void)hipSetDevice(device); (void)hipSetDeviceFlags(f); (void)hipGetLastError();
     }
     if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -351,8 +351,7 @@ int mauve_set_shard_rccl(mauve_ctx *c, int rank, int world, void *nccl_comm)
     if (world < 1 || !nccl_comm) return world <= 1 ? MAUVE_OK : (c->err = "set_shard_rccl: a communicator is required", MAUVE_ERR_ARG);
     if (rank < 0 || rank >= world) { c->err = "set_shard_rccl: rank outside the world"; return MAUVE_ERR_ARG; }
     if (!rccl_api().ok) { c->err = "set_shard_rccl: no RCCL in this process (ncclAllGather not found, librccl.so.1 not loadable)"; return MAUVE_ERR_STATE; }
-    static const bool single = getenv("MAUVE_SHARD_SINGLE") != nullptr;
-    if (world == 1 && !single) return MAUVE_OK;                 // one rank: nothing to deal out
+    if (world == 1 && !switches().shard_single) return MAUVE_OK;                 // one rank: nothing to deal out
     c->shard_rank = rank; c->shard_world = world; c->shard_comm = nccl_comm; c->shard_on = true;
     return MAUVE_OK;
 }

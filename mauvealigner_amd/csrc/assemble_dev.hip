@@ -223,7 +223,7 @@ int match_sp_scores(mauve_ctx *c, const MatchVec &m, const int *gmap, const mauv
 // columns stay in c->res_cols, the anchor table where the chain stage left it, until materialize_result.
 int assemble_device(mauve_ctx *c, int64_t na64, int64_t cells, mauve_align_sizes *sizes, bool host_chains)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     AlignState &S = c->ast; AlignResult &R = c->res;
     const int N = S.N; const int64_t nl = S.nl; const uint32_t na = (uint32_t)na64;
     const mauve_ctx::DpFrontOut &fo = c->dpf_out;

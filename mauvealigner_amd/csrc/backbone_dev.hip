@@ -253,7 +253,7 @@ int bb_collect(mauve_ctx *c, const AlnView &A, const std::vector<BbIv> &ivs, uin
         HIPCHK(c, hipMemcpyAsync(a.ivs, ivs.data(), ivs.size() * sizeof(BbIv), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(a.count, 0, 64, c->stream));
         const uint32_t gy = std::min<uint32_t>(max_pairs, 64);        // one wave per (chunk, pair): with few pairs, too, every resident wave works
-        static const bool column_scan = getenv("MAUVE_BB_COLUMN_SCAN") != nullptr;
+        const bool column_scan = switches().bb_column_scan;
         if (!column_scan) hipLaunchKernelGGL(bb_chunk_last, dim3(chunks), dim3(64), 0, c->stream, A.d_cols, a.ivs, (uint32_t)ivs.size(), max_pairs, a.last);
         hipLaunchKernelGGL(bb_pair_gaps, dim3(chunks, gy), dim3(64), 0, c->stream, A.d_cols, a.ivs, (uint32_t)ivs.size(), island_gap, a.rec, (uint32_t)cap, a.count,
                            column_scan ? (const uint8_t *)nullptr : a.last, max_pairs);
@@ -300,7 +300,7 @@ int backbone_run(mauve_ctx *c, const AlnView &A, int64_t island_gap)
     std::vector<BbIv> ivs; uint32_t chunks = 0, max_pairs = 0;
     if (!bb_intervals(A.N, A.n_iv, A.left, A.col_off, ivs, &chunks, &max_pairs)) { c->err = "backbone: interval too long"; return MAUVE_ERR_LIMIT; }
     if (ivs.empty()) { B.valid = true; return MAUVE_OK; }
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     const double tb0 = now_ms();
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<BbRec> recs, islands; std::vector<uint32_t> tile_cnt;

@@ -630,7 +630,7 @@ __global__ void __launch_bounds__(256) ch_sp_scores(const uint64_t *__restrict__
 
 int chain_device_graph(mauve_ctx *c, int N, int64_t maxlen_in, const uint32_t *seg0, uint32_t nseg, ChainGraphHost *G, bool graph_to_host, const mauve_scoring *sp_scoring)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     const double t0 = now_ms();
     const int64_t nm = c->dev_rec_n;
     if (nm <= 0 || nm >= (1LL << 31)) { c->err = "chain_device: no device-resident match list"; return MAUVE_ERR_STATE; }
@@ -661,8 +661,8 @@ int chain_device_graph(mauve_ctx *c, int N, int64_t maxlen_in, const uint32_t *s
     uint32_t *cnt = c->ch_cnt.as<uint32_t>();                     // (layout: CH_CNT_ALIVE)
     const int64_t *rlen = c->sorted_rec.as<int64_t>(), *rst = rlen + n;
     const uint32_t blocks = (n + 255) / 256;
-    static const int big_max = []() { const char *e = getenv("MAUVE_CH_BIG_MAX"); const int v = e ? atoi(e) : 2048; return v < 1 ? 1 : v; }();        // cluster size the one-lane kernel still takes (tests lower it)
-    static const int cl_max = []() { const char *e = getenv("MAUVE_CH_CL_MAX"); const int v = e ? atoi(e) : CH_CL_MAX; return v < 1 ? 1 : (v > CH_CL_MAX ? CH_CL_MAX : v); }();   // (tests lower it)
+    const int big_max = switches().ch_big_max;                   // cluster size the one-lane kernel still takes (tests lower it)
+    const int cl_set = switches().ch_cl_max, cl_max = cl_set && cl_set < CH_CL_MAX ? cl_set : CH_CL_MAX;   // (tests lower it; 0: not set)
     // the graph arrays are sized for the worst case K = n
     HIPCHK(c, c->ch_graph.ensure((size_t)n * (8 + 4 + (size_t)N * 4 * 3 + 4) + 8 + (size_t)n * (8 + 4 + (size_t)N * 8) + 64));     // the arrays + their packed copy
     unsigned long long *weight = c->ch_graph.as<unsigned long long>();
@@ -765,7 +765,7 @@ int chain_device_graph(mauve_ctx *c, int N, int64_t maxlen_in, const uint32_t *s
 // c->ch_len / c->ch_st, final LCB id per match behind them).  chain_device_copy_back brings them to the host.
 int chain_device_core(mauve_ctx *c, int N, int64_t min_weight, bool collinear, int64_t &n_lcb, const mauve_scoring *sp_scoring)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     int64_t maxlen = 1; for (int g = 0; g < N; g++) maxlen = std::max<int64_t>(maxlen, c->lens[(size_t)g]);
     ChainGraphHost G;
     int rc = chain_device_graph(c, N, maxlen, nullptr, 0, &G, true, sp_scoring);
@@ -866,7 +866,7 @@ int chain_device_gaps(mauve_ctx *c, int N, int64_t maxlen, const uint32_t *seg0_
 int chain_device_gaps_compact(mauve_ctx *c, int N, int64_t maxlen, const uint32_t *seg0_dev, uint32_t nseg, const int32_t **hl_out, const int32_t **hs_out,
                               const uint32_t **hgap_out, uint32_t *ns_out)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     ChainGraphHost G;
     int rc = chain_device_graph(c, N, maxlen, seg0_dev, nseg, &G, false);
     if (rc) return rc;
@@ -923,7 +923,7 @@ int chain_device_gaps_compact(mauve_ctx *c, int N, int64_t maxlen, const uint32_
 // the cropped list and its labels back to the host (dead records stay in the list with length 0 / LCB -1)
 int chain_device_copy_back(mauve_ctx *c, int N, MatchVec &m, std::vector<int64_t> &match_lcb)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     const double t2 = now_ms();
     const uint32_t n = (uint32_t)c->dev_rec_n;
     const int32_t *len = c->ch_len.as<int32_t>(), *lcb = len + 2 * (size_t)n;

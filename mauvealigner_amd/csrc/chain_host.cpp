@@ -250,7 +250,7 @@ void host_eliminate_overlaps(MatchVec &m, ChainOrders *orders, bool compact)
 {
     const int N = m.N;
     const size_t n = m.size();
-    static const bool trace_on = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace_on = switches().trace;
     const bool trace = trace_on && n >= 1000;          // per-gap calls of the recursion stay quiet
     const double te0 = trace ? now_ms() : 0;
     static thread_local ElimScratch S;
@@ -457,7 +457,7 @@ void host_lcb_chain(const MatchVec &m, int64_t min_weight, bool collinear, std::
     match_lcb.assign(n, -1);
     n_lcb = 0;
     if (n == 0) return;
-    static const bool trace_on = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace_on = switches().trace;
     const bool trace = trace_on && n >= 1000;
     const double tl0 = trace ? now_ms() : 0;
     // per-genome order of the matches and its inverse

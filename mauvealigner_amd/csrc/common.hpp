@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include <functional>
+#include "switches.hpp"
 #include "workers.hpp"
 #include "host_chain.hpp"
 #include "backbone_host.hpp"
@@ -477,11 +478,9 @@ int sort_pairs_u64(mauve_ctx *ctx, uint32_t n, int key_bits, uint64_t **keys_io,
 // seed_finish.hip once the ncand candidate records of all finder passes are in ctx->mlen / mstart (on_host: in ctx->sdh.hl / hs
 // already): the guide tree's per-pair sums (ctx->pair_sums_only) or the match list in canonical order.
 int seed_finish(mauve_ctx *ctx, const GenomeSet &gs, const SeedRequest &rq, uint32_t ncand, bool on_host, double &trace_t0);
-bool seed_trace_on();                    // MAUVE_TRACE
-uint32_t canon_device_min();             // candidates from which the canonical order is made on the device (below: the host sorts)
 inline void seed_trace(mauve_ctx *ctx, const char *label, double &t0)
 {
-    if (!seed_trace_on()) return;
+    if (!switches().trace) return;
     (void)hipStreamSynchronize(ctx->stream);
     const double t = now_ms();
     fprintf(stderr, "[trace] %-22s +%.3f ms\n", label, t - t0);

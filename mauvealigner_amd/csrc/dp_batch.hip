@@ -1793,17 +1793,6 @@ private:
     int64_t mmin = 0, mmax = 0, nmax = 0, rneed = 0, crows = 0;       // crows: the longest profile the class estimate expects
 };
 
-// Which intervals get a workgroup (dp_step_big) instead of a wave: candidates (a step with several bands) whose single-wave estimate is
-// at least MAUVE_DP_WIDE_MIN scan steps, at most MAUVE_DP_BIG_MAX of them.
-static int dp_class_mode()
-{
-    static const int m = []() { const char *e = getenv("MAUVE_DP_CLASS"); return !e ? 0 : (!strcmp(e, "bound") ? 1 : (!strcmp(e, "wild") ? 2 : 0)); }();
-    return m;
-}
-static int64_t dp_wide_min() { static const int64_t f = getenv("MAUVE_DP_WIDE_MIN") ? atoll(getenv("MAUVE_DP_WIDE_MIN")) : 1024; return f; }
-static int64_t dp_big_max() { static const int64_t m = getenv("MAUVE_DP_BIG_MAX") ? atoll(getenv("MAUVE_DP_BIG_MAX")) : 256; return m; }
-static bool dp_wide_on() { static const bool o = getenv("MAUVE_DP_NO_WIDE") == nullptr; return o; }   // A/B switch: the workgroup entries all through the stripe pipeline
-
 // the DP launches: the workgroup-per-interval kernels (dp_step_wide, dp_step_big) beside dp_step2 (wave / sub-wave per interval),
 // over the positions [a, b) of the launch list [workgroup | one wave | G = 16 | G = 8 | G = 4]; tb_base is
 // subtracted from the traceback offsets (rounds, below)
@@ -1818,8 +1807,8 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
     clip(full.first_c, full.n_c, cl.first_c, cl.n_c);
     clip(full.first_s32, full.n_s32, cl.first_s32, cl.n_s32);
     clip(full.first_s16, full.n_s16, cl.first_s16, cl.n_s16);
-    static const bool no_scan = getenv("MAUVE_DP_NOSCAN") != nullptr;     // A/B switch: anti-diagonal sweep for the one-wave class too
-    cl.scan = no_scan ? 0 : 1;
+    const Switches &sw = switches();
+    cl.scan = sw.dp_noscan ? 0 : 1;                                      // A/B switch: anti-diagonal sweep for the one-wave class too
     // intervals per workgroup: DP2_WAVES waves x {1, 4, 8, 16}
     const int64_t wpb = DP2_WAVES, cap = 256 * 16;
     cl.blocks_med = (uint32_t)std::min<int64_t>((cl.n_med + wpb - 1) / wpb, cap);
@@ -1841,13 +1830,12 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
     if (bn) {
         HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        const bool wide = dp_wide_on();
+        const bool wide = !sw.dp_no_wide;                                // A/B switch: the workgroup entries all through the stripe pipeline
         // the wide sweep runs 8 waves x 4 rows per lane (16 waves x 2 rows took the same time per line -- the sweep is bound by vector issue, not by the
         // number of waves -- and the 128-register budget of a 1024-thread workgroup made it spill: it is no longer built)
         // the first entries of the list (the largest intervals) get a CLUSTER of up to DPW_KMAX workgroups each (dp_interval_wide); few enough that all
         // of them are resident at once beside the rest.  MAUVE_DP_CLUSTER=0: off (A/B), =n: that many entries
-        static const int64_t cl_max = getenv("MAUVE_DP_CLUSTER") ? atoll(getenv("MAUVE_DP_CLUSTER")) : 32;
-        const int64_t n_cl = wide ? std::min<int64_t>(bn, cl_max) : 0;
+        const int64_t n_cl = wide ? std::min<int64_t>(bn, sw.dp_cluster) : 0;
         unsigned long long *flags = nullptr;
         if (n_cl) {
             HIPCHK(ctx, ctx->dp_wflags.ensure((size_t)n_cl * DPW_FLAGS * 8));
@@ -1876,16 +1864,11 @@ static int dp_launch_steps(mauve_ctx *ctx, int nseq, int64_t a, int64_t b, int64
 // hundred gaps near max_gapped_len, or profiles of many genomes -- would ask for more than any allocation gives.
 // The launch list is cut into rounds whose traceback fits the budget (MAUVE_DP_TB_BUDGET bytes, default 8 GiB); the
 // rounds run one after the other over the same buffer.  tb_list: cumulative traceback bytes in LIST order (n + 1).
-static int64_t dp_tb_budget()
-{
-    static const int64_t b = getenv("MAUVE_DP_TB_BUDGET") ? atoll(getenv("MAUVE_DP_TB_BUDGET")) : (8LL << 30);
-    return std::max<int64_t>(b, 1 << 16);
-}
 static int dp_launch_rounds(mauve_ctx *ctx, int nseq, int64_t n_iv, int64_t n_big, int64_t big_len, const DpClasses &cl, const int64_t *d_seq_off,
                             const int64_t *d_tb_off, const int64_t *d_rows_off, const DpScoring &sc, const int64_t *tb_list, int *rounds_out,
                             int64_t band_from)
 {
-    const int64_t budget = dp_tb_budget();
+    const int64_t budget = switches().dp_tb_budget;
     int rounds = 0;
     for (int64_t a = 0; a < n_iv;) {
         int64_t b = a + 1;
@@ -1917,7 +1900,7 @@ static int dp_ensure_batch(mauve_ctx *ctx, int64_t total, int64_t tbt, int64_t r
     HIPCHK(ctx, ctx->dp_prof_mask.ensure((size_t)(total + 1) * 4));
     HIPCHK(ctx, ctx->dp_prof2_cnt.ensure((size_t)(total + 1) * 4));
     HIPCHK(ctx, ctx->dp_prof2_mask.ensure((size_t)(total + 1) * 4));
-    HIPCHK(ctx, ctx->dp_tb.ensure((size_t)std::min<int64_t>(tbt, dp_tb_budget()) + 64));
+    HIPCHK(ctx, ctx->dp_tb.ensure((size_t)std::min<int64_t>(tbt, switches().dp_tb_budget) + 64));
     HIPCHK(ctx, ctx->dp_rows.ensure((size_t)(rwt + 1) * 4));
     HIPCHK(ctx, ctx->dp_score.ensure((size_t)total + 16));           // reversed-ops scratch
     HIPCHK(ctx, ctx->dp_cols.ensure((size_t)(total + 1) * 4));
@@ -1941,7 +1924,8 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     if (cells) *cells = 0;
     col_off[0] = 0;
     if (n_iv == 0) return MAUVE_OK;
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const Switches &sw = switches();
+    const bool trace = sw.trace;
     const double td0 = now_ms();
     const int64_t total = seq_off[n_iv * nseq];
     // per-interval scratch: traceback and parked rows (DpSizing)
@@ -1952,8 +1936,6 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     is_big.assign((size_t)n_iv, 0); est.assign((size_t)n_iv, 0);
     int64_t est_total = 0;
     const int64_t band_from = ctx->dp_band_from;
-    static const bool no_mw = getenv("MAUVE_DP_ONE_WAVE") != nullptr;     // A/B switch for the workgroup path
-    static const bool no_groups = getenv("MAUVE_DP_NO_GROUPS") != nullptr; // A/B switch for the sub-wave path
     std::vector<uint8_t> &cls = H.cls; cls.assign((size_t)n_iv, 1);
     int64_t tbt = 0, rwt = 0;
     // per-interval figures on the host helpers, then one sequential prefix
@@ -1963,7 +1945,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
         for (int64_t iv = b; iv < e; iv++) {
             int64_t longest = 0;
             for (int g = 0; g < nseq; g++) longest = std::max(longest, seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g]);
-            DpSizing z(band_from, no_mw, no_groups, dp_class_mode(), longest);
+            DpSizing z(band_from, sw.dp_one_wave, sw.dp_no_groups, sw.dp_class, longest);
             for (int g = 0; g < nseq; g++) z.add(seq_off[iv * nseq + g + 1] - seq_off[iv * nseq + g]);
             need_v[(size_t)iv] = z.need; nmax_v[(size_t)iv] = z.rows(); est[(size_t)iv] = z.est; is_big[(size_t)iv] = z.cand(); cls[(size_t)iv] = z.cls();
         }
@@ -1987,12 +1969,12 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     }
     // workgroup-per-interval entries first (still largest first), one-wave entries after them
     // A 16-wave workgroup takes half a CU's wave slots, so it is for the tail of the launch: intervals that would keep ONE wave busy for
-    // dp_wide_min() scan steps or more (the rest of the launch is over by then), the largest dp_big_max() of them.
+    // MAUVE_DP_WIDE_MIN scan steps or more (the rest of the launch is over by then), the largest MAUVE_DP_BIG_MAX of them.
     int64_t n_big = 0;
     {
         for (int64_t k = 0; k < n_iv; k++) {          // lst is largest first
             uint8_t &b = is_big[(size_t)lst[(size_t)k]];
-            if (b == 1 && (n_big >= dp_big_max() || est[(size_t)lst[(size_t)k]] < dp_wide_min())) b = 0;
+            if (b == 1 && (n_big >= sw.dp_big_max || est[(size_t)lst[(size_t)k]] < sw.dp_wide_min)) b = 0;
             n_big += b != 0;
         }
     }
@@ -2016,7 +1998,7 @@ static int dp_core(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes,
     tbt = 0;
     for (int64_t k = 0; k < n_iv; k++) { const int64_t iv = lst[(size_t)k]; tb_off[iv] = tbt; tb_list[(size_t)k] = tbt; tbt += need_v[(size_t)iv]; }
     tb_list[(size_t)n_iv] = tbt; tb_off[n_iv] = tbt;
-    const bool one_round = tbt <= dp_tb_budget();
+    const bool one_round = tbt <= sw.dp_tb_budget;
 
     { int rce = dp_ensure_batch(ctx, total, tbt, rwt); if (rce) return rce; }
     HIPCHK(ctx, ctx->dp_off.ensure((size_t)(n_iv * nseq + 1 + 3 * (n_iv + 1)) * sizeof(int64_t)));
@@ -2291,6 +2273,7 @@ static int dpf_work_area(mauve_ctx *ctx, uint32_t na, int N, DpFrontWork &W)
 struct DpFrontRun { int64_t n_big; DpClasses cl; int rounds; double t_sized; };
 static int dpf_run(mauve_ctx *ctx, const DpFrontWork &W, int N, uint32_t n_dp, const DpScoring &sc, DpFrontTotals *ht, DpFrontRun &R)
 {
+    const Switches &sw = switches();
     const uint32_t nbd = (n_dp + TILE - 1) / TILE, nbs = (n_dp * (uint32_t)N + TILE - 1) / TILE, blk_d = (n_dp + 255) / 256;
     DpFrontTotals *tot = W.tot;
     hipLaunchKernelGGL((vscan_partial<int64_t, DescLen>), dim3(nbs), dim3(256), 0, ctx->stream, DescLen{W.desc}, n_dp * (uint32_t)N, W.bsum);
@@ -2304,7 +2287,7 @@ static int dpf_run(mauve_ctx *ctx, const DpFrontWork &W, int N, uint32_t n_dp, c
     int rc = sort_pairs_u32(ctx, n_dp, 6, &ok, &ov, W.k2, W.v2, MAUVE_K_MISC);
     if (rc) return rc;
     uint32_t *fk = ok == W.k1 ? W.k2 : W.k1, *fv = ov == W.v1 ? W.v2 : W.v1;        // free pair
-    const DpBigPick bp{ov, W.cand, W.cls, W.est, tot, fk, dp_wide_min(), (uint32_t)dp_big_max()};
+    const DpBigPick bp{ov, W.cand, W.cls, W.est, tot, fk, sw.dp_wide_min, (uint32_t)sw.dp_big_max};
     hipLaunchKernelGGL((cmp_count<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, W.bcnt);
     hipLaunchKernelGGL((cmp_write<DpBigPick>), dim3(nbd), dim3(256), 0, ctx->stream, bp, W.bcnt);
     uint32_t *ck = fk, *cv = ov;
@@ -2330,7 +2313,7 @@ static int dpf_run(mauve_ctx *ctx, const DpFrontWork &W, int N, uint32_t n_dp, c
     rc = dp_ensure_batch(ctx, total, tbt, rwt);
     if (rc) return rc;
     std::vector<int64_t> &tb_list = ctx->dph.tb_list; tb_list.clear();
-    if (tbt > dp_tb_budget()) {                                         // several rounds: the host needs the cumulative bytes to cut them
+    if (tbt > sw.dp_tb_budget) {                                                 // several rounds: the host needs the cumulative bytes to cut them
         tb_list.resize((size_t)n_dp + 1);
         HIPCHK(ctx, hipMemcpy(tb_list.data(), tb_list_dev, ((size_t)n_dp + 1) * 8, hipMemcpyDeviceToHost));
     }
@@ -2362,8 +2345,8 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na64, const int32_t *h_le
 {
     // stay: 0 = host anchors, results to the host; 1 = device anchors used in place, results stay; 2 = host anchors, results stay
     const bool stay_on_device = stay != 0, anchors_in_place = stay == 1;
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
-    static const bool no_mw = getenv("MAUVE_DP_ONE_WAVE") != nullptr, no_groups = getenv("MAUVE_DP_NO_GROUPS") != nullptr;
+    const Switches &sw = switches();
+    const bool trace = sw.trace;
     const double t0 = now_ms();
     *n_dp_out = 0; *code_total_out = 0; if (cells) *cells = 0;
     dcol_off.assign(1, 0); dscore.clear();
@@ -2391,7 +2374,7 @@ int dp_run_from_anchors(mauve_ctx *ctx, int N, int64_t na64, const int32_t *h_le
     hipLaunchKernelGGL((cmp_count<DpSlots>), dim3(nb), dim3(256), 0, ctx->stream, sl, W.bcnt);
     hipLaunchKernelGGL((cmp_write<DpSlots>), dim3(nb), dim3(256), 0, ctx->stream, sl, W.bcnt);
     hipLaunchKernelGGL(dpf_desc, dim3(blocks), dim3(256), 0, ctx->stream, alen, ast, N, anchor_of, tot, W.desc, W.sizing(),
-                       (int)no_mw, (int)no_groups, ctx->dp_band_from, dp_class_mode());
+                       (int)sw.dp_one_wave, (int)sw.dp_no_groups, ctx->dp_band_from, sw.dp_class);
     // the launch covers na (>= n_dp) slots and the kernel stops at n_dp, a device value; the scans that follow run over exactly
     // n_dp entries, so the small totals block is read back first
     HIPCHK(ctx, hipGetLastError());
@@ -2481,8 +2464,8 @@ __global__ void __launch_bounds__(256) dpf_rotate_desc(DpSeqDesc *__restrict__ d
 int dp_run_from_desc(mauve_ctx *ctx, int N, int64_t n_iv, const DpSeqDesc *h_desc, const mauve_scoring *scoring, uint32_t *cols, int64_t *col_off, int64_t *score,
                      int64_t *cells, int64_t *sp, int64_t n_orig = -1, const int32_t *cbase = nullptr)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
-    static const bool no_mw = getenv("MAUVE_DP_ONE_WAVE") != nullptr, no_groups = getenv("MAUVE_DP_NO_GROUPS") != nullptr;
+    const Switches &sw = switches();
+    const bool trace = sw.trace;
     const double t0 = now_ms();
     if (cells) *cells = 0;
     col_off[0] = 0;
@@ -2511,8 +2494,8 @@ int dp_run_from_desc(mauve_ctx *ctx, int N, int64_t n_iv, const DpSeqDesc *h_des
         hipLaunchKernelGGL(dpf_rotate_desc, dim3((uint32_t)((n_orig + 255) / 256)), dim3(256), 0, ctx->stream, desc, N, (uint32_t)n_orig, d_cb);
     }
     HIPCHK(ctx, hipMemsetAsync(tot, 0, 256, ctx->stream));
-    hipLaunchKernelGGL(dpf_size_desc, dim3((n_dp + 255) / 256), dim3(256), 0, ctx->stream, desc, N, n_dp, tot, W.sizing(), (int)no_mw, (int)no_groups,
-                       ctx->dp_band_from, dp_class_mode());
+    hipLaunchKernelGGL(dpf_size_desc, dim3((n_dp + 255) / 256), dim3(256), 0, ctx->stream, desc, N, n_dp, tot, W.sizing(), (int)sw.dp_one_wave, (int)sw.dp_no_groups,
+                       ctx->dp_band_from, sw.dp_class);
     const DpScoring sc = dp_scoring_of(scoring);
     DpFrontRun R;
     rc = dpf_run(ctx, W, N, n_dp, sc, ht, R);
@@ -2592,10 +2575,8 @@ int dp_batch_run(mauve_ctx *ctx, int nseq, int64_t n_iv, const uint8_t *codes, c
     return dp_core(ctx, nseq, n_iv, codes, nullptr, seq_off, scoring, cols, col_off, score, cells);
 }
 
-static bool dp_desc_host() { static const bool h = getenv("MAUVE_DP_DESC_HOST") != nullptr; return h; }
-static int64_t dp_desc_min() { static const int64_t m = getenv("MAUVE_DP_DESC_MIN") ? atoll(getenv("MAUVE_DP_DESC_MIN")) : 2048; return m; }
 // does a batch of n_total rows take the device front (where the rotated candidates can be made on the device)?
-bool dp_desc_rotations_on_device(int64_t n_total) { return !dp_desc_host() && n_total >= dp_desc_min(); }
+bool dp_desc_rotations_on_device(int64_t n_total) { return !switches().dp_desc_host && n_total >= switches().dp_desc_min; }
 int dp_batch_run_desc_rot(mauve_ctx *ctx, int nseq, int64_t n_orig, const DpSeqDesc *desc, const int32_t *cbase, int64_t n_total, const mauve_scoring *scoring,
                           int64_t *col_off, int64_t *score, int64_t *cells, int64_t *sp)
 {
@@ -2682,7 +2663,7 @@ int dp_batch_run_desc(mauve_ctx *ctx, int nseq, int64_t n_iv, const DpSeqDesc *d
     }
     // large batches: sizing, order and result offsets on the device (dp_run_from_desc); small ones keep the host loops (fewer launches).
     // MAUVE_DP_DESC_HOST: A/B switch
-    if (!dp_desc_host() && n_iv >= dp_desc_min()) return dp_run_from_desc(ctx, nseq, n_iv, desc, scoring, cols, col_off, score, cells, sp);
+    if (!switches().dp_desc_host && n_iv >= switches().dp_desc_min) return dp_run_from_desc(ctx, nseq, n_iv, desc, scoring, cols, col_off, score, cells, sp);
     seq_off.resize((size_t)(n_iv * nseq + 1));
     int64_t t = 0;
     for (int64_t i = 0; i < n_iv * nseq; i++) { seq_off[(size_t)i] = t; t += desc[i].len; }

@@ -171,7 +171,7 @@ int rec_gap_flags_device(mauve_ctx *c, const int32_t *alen, const int32_t *ast, 
 int extend_lcbs_device(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw, int N, const int32_t **alen_io, const int32_t **ast_io,
                        const int32_t **alcb_io, int64_t *na_io, int64_t *nl_io, int64_t *n_rec_io, std::vector<int64_t> &lcb_weight)
 {
-    static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+    const bool trace = switches().trace;
     const double t0 = now_ms();
     const uint32_t na = (uint32_t)*na_io; const int64_t nl0 = *nl_io;
     const int32_t *alen = *alen_io, *ast = *ast_io, *alcb = *alcb_io;
@@ -312,7 +312,7 @@ int extend_lcbs_device(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
             uw[(size_t)T.n + i] = ext.len(i) * N;
         }
         host_lcb_chain(U, lcbw, p->collinear != 0, ul, nl2, nullptr, uw.data());
-        static const bool force_decline = getenv("MAUVE_EXT_DECLINE") != nullptr;      // test knob: hand the first round that finds matches back as if an LCB had died
+        const bool force_decline = switches().ext_decline;      // test knob: hand the first round that finds matches back as if an LCB had died
         for (int64_t l = 0; l < T.n; l++)
             if (ul[(size_t)l] < 0 || force_decline) {
                 // an old LCB died in the re-chaining of the units (--collinear, which goes down to ONE LCB, is kept off this route; anything else that

@@ -35,7 +35,7 @@ static int extend_lcbs(mauve_ctx *c, const mauve_params *p, int w, int64_t lcbw,
         const uint64_t pe = mauve_get_seed(w_e, 0);
         if (!pe) break;
         const int64_t span_e = mauve_seed_length(pe);
-        static const bool trace = getenv("MAUVE_TRACE") != nullptr;
+        const bool trace = switches().trace;
         const double tr0 = now_ms();
         // LCB extents
         std::vector<int64_t> lo((size_t)nl * N, 0), hi((size_t)nl * N, 0);
@@ -201,13 +201,10 @@ int seed_family_matches(mauve_ctx *c, const GenomeSet &gs, int w, int mode, uint
         seed_matches_to_vec(c, n, nm, cur);
         const double tm0 = now_ms();
         if (k == 0) out.d.swap(cur.d); else host_merge_matches(out, cur);
-        static const bool trace = getenv("MAUVE_TRACE") != nullptr;
-        if (trace) fprintf(stderr, "[trace] seed family: seed %d gave %lld matches, merge %.3f ms\n", order[k], (long long)nm, now_ms() - tm0);
+        if (switches().trace) fprintf(stderr, "[trace] seed family: seed %d gave %lld matches, merge %.3f ms\n", order[k], (long long)nm, now_ms() - tm0);
     }
     return MAUVE_OK;
 }
-
-static const bool g_trace_pipeline = getenv("MAUVE_TRACE") != nullptr;     // read once, not in the timed path
 
 // ---- the whole path in three phases, so that the DP intervals of one alignment can be sharded over ranks ----
 // begin : seed pass, chaining, recursive anchoring, interval descriptors        (every rank, deterministic)
@@ -257,17 +254,15 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     // ---- seed pass: N-way multi-MUMs (the multiplicity filter is pushed into the join) ----
     // In its shadow (the host would otherwise wait for the kernels): bring the column buffer back to the
     // "all anchors" state, i.e. undo the gap ranges the previous call wrote (see align_finish).
-    static const bool no_shadow = getenv("MAUVE_NO_SHADOW") != nullptr;        // A/B switch
-    if (R.cols_fill == full && !R.cols_dirty.empty() && !no_shadow)
+    if (R.cols_fill == full && !R.cols_dirty.empty())
         c->shadow = [c, full]() { restore_cols(c->res, full); };
     int64_t nm = 0;
     int rc = MAUVE_OK;
     // LCB extension without taking the chains off the device (extend_dev.hip): plain genomes, length-weighted LCBs.  MAUVE_HOST_EXTEND: A/B switch
-    static const bool host_extend = getenv("MAUVE_HOST_EXTEND") != nullptr;
     const bool do_extend = p->extend_lcbs && p->lcb_scoring == MAUVE_LCB_SCORE_LENGTH;      // (score-weighted LCBs are not extended: the rule counts columns)
     // (collinear: the greedy step runs down to ONE node, so an old LCB can lose against the new matches -- the unit-level re-chaining
     //  of extend_dev.hip assumes old LCBs survive; that rare option takes the host rounds)
-    const bool ext_on_device = do_extend && !host_extend && !c->has_invalid && !c->has_contigs && !p->collinear;
+    const bool ext_on_device = do_extend && !switches().host_extend && !c->has_invalid && !c->has_contigs && !p->collinear;
     bool chains_ready = false;                       // S.chains filled from the device anchors (extension done there, recursion to follow on the host)
     MatchVec family(N);
     if (!given && p->seed_family) {
@@ -277,7 +272,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
         const double tf0 = now_ms();
         rc = seed_family_matches(c, main_genome_set(c), w, p->mode, full, family);
         if (rc) return rc;
-        if (g_trace_pipeline) fprintf(stderr, "[trace] seed family: three searches + merges %.3f ms, %zu matches\n", now_ms() - tf0, family.size());
+        if (switches().trace) fprintf(stderr, "[trace] seed family: three searches + merges %.3f ms, %zu matches\n", now_ms() - tf0, family.size());
         given = &family;
     }
     if (given) {
@@ -307,9 +302,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
         // so that overlap elimination, LCBs, extension and the tail run on the device as they do after a search (chain_dev.hip; a
         // list the device chain declines -- MAUVE_ERR_LIMIT -- falls back to the host chain below).  Same threshold as the seed pass's
         // device sort; MAUVE_GIVEN_ON_HOST: A/B switch.
-        static const int64_t dev_min = getenv("MAUVE_CANON_DEVICE_MIN") ? atol(getenv("MAUVE_CANON_DEVICE_MIN")) : 16384;
-        static const bool given_on_host = getenv("MAUVE_GIVEN_ON_HOST") != nullptr;
-        if (!given_on_host && nm >= dev_min && nm < (1LL << 31) && p->lcb_scoring == MAUVE_LCB_SCORE_LENGTH) {
+        if (!switches().given_on_host && nm >= switches().canon_device_min && nm < (1LL << 31) && p->lcb_scoring == MAUVE_LCB_SCORE_LENGTH) {
             const size_t rb = (size_t)nm * (1 + (size_t)N) * 8;
             HIPCHK(c, c->sorted_rec.ensure(rb + 64));
             HIPCHK(c, c->pin_tab.ensure(rb + 64));
@@ -321,8 +314,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
             c->dev_rec_n = nm; c->match_nseq = N;
         }
     } else {
-        static const bool host_tail_env = getenv("MAUVE_HOST_TAIL") != nullptr;
-        c->lazy_matches_ok = want_tail && !host_tail_env && (!do_extend || ext_on_device);     // the list may stay in HBM (device tail below)
+        c->lazy_matches_ok = want_tail && !switches().host_tail && (!do_extend || ext_on_device);     // the list may stay in HBM (device tail below)
         rc = seedpass_run(c, main_genome_set(c), pat, p->mode, full, 1, nullptr, 0, &nm);
         c->lazy_matches_ok = false;
         c->shadow = nullptr;
@@ -339,9 +331,8 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     MatchVec &m = S.m; m.N = N;
     const int64_t lcbw = p->lcb_weight >= 0 ? p->lcb_weight : (int64_t)3 * w * N;
     std::vector<int64_t> &match_lcb = S.match_lcb; int64_t nl = 0;
-    static const bool host_chain = getenv("MAUVE_HOST_CHAIN") != nullptr;
     if (p->lcb_scoring != MAUVE_LCB_SCORE_LENGTH && p->lcb_scoring != MAUVE_LCB_SCORE_SP) { c->err = "align: unknown lcb_scoring"; return MAUVE_ERR_ARG; }
-    bool on_device = !host_chain && nm > 0 && c->dev_rec_n == nm && p->lcb_scoring == MAUVE_LCB_SCORE_LENGTH;   // score weights: host chain
+    bool on_device = !switches().host_chain && nm > 0 && c->dev_rec_n == nm && p->lcb_scoring == MAUVE_LCB_SCORE_LENGTH;   // score weights: host chain
     double t1b = t1;
     if (on_device) {
         rc = chain_device_core(c, N, lcbw, p->collinear != 0, nl);
@@ -351,8 +342,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
             // The chains can stay on the device when nothing on the host has to look at them: no LCB extension, and no
             // inter-anchor gap long enough for the recursion (counted on the device).  The DP front end and the assembly
             // then run there too (mauve_align), and the host sees only the per-LCB rows.
-            static const bool host_tail = getenv("MAUVE_HOST_TAIL") != nullptr;      // A/B switch
-            if (want_tail && !host_tail && (!do_extend || ext_on_device) && nl > 0) {
+            if (want_tail && !switches().host_tail && (!do_extend || ext_on_device) && nl > 0) {
                 int64_t na = 0, nrec = 0;
                 rc = chain_order_device(c, N, nl, p->min_recursive_gap, &na, &nrec);
                 if (rc) return rc;
@@ -374,7 +364,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
                     if (c->pf.live) HIPCHK(c, hipEventRecord(c->ev_io_fork, c->stream));      // both bulk tables are final behind this point (mauve_align_prefetch)
                     const double t2 = now_ms();
                     c->stage.chain_ms = t2 - t1;
-                    if (g_trace_pipeline) fprintf(stderr, "[trace] chain: on the device %.3f ms, %lld anchors in %lld LCBs stay there\n", t2 - t1, (long long)na, (long long)nl);
+                    if (switches().trace) fprintf(stderr, "[trace] chain: on the device %.3f ms, %lld anchors in %lld LCBs stay there\n", t2 - t1, (long long)na, (long long)nl);
                     S.t_dp0 = t2;
                     S.open = true;
                     return MAUVE_OK;
@@ -411,12 +401,11 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
                         a = e;
                     }
                     chains_ready = true;
-                    if (g_trace_pipeline) fprintf(stderr, "[trace] chain (device): %lld extended anchors to the host (recursion to follow)\n", (long long)na);
+                    if (switches().trace) fprintf(stderr, "[trace] chain (device): %lld extended anchors to the host (recursion to follow)\n", (long long)na);
                     S.dv_len = S.dv_st = S.dv_lcb = nullptr; S.lw_from_host = false;
                 }
             }
-            static const bool no_keep = getenv("MAUVE_NO_KEEP_MUMS") != nullptr;      // A/B switch
-            if (c->matches_pending && chains_ready && !no_keep && c->dev_rec_n == c->n_matches) {
+            if (c->matches_pending && chains_ready && c->dev_rec_n == c->n_matches) {
                 // the chains came over as anchors; nothing on the host reads the match list before the caller fetches it: it stays in HBM,
                 // set aside while the recursion's passes use the seed workspace (back in place for the assembly: assemble_device)
                 std::swap(c->sorted_rec, c->sorted_rec_keep);
@@ -441,9 +430,8 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     }
     if (!on_device) {
         seed_matches_to_vec(c, N, nm, m);
-        static const bool elim_compact = getenv("MAUVE_ELIM_COMPACT") != nullptr;       // A/B switch; default: dead records stay in m, with lcb -1 below
         const int64_t minw_sp = p->lcb_weight >= 0 ? p->lcb_weight : sp_default_min_weight(w, N, &p->scoring);
-        rc = host_chain_lcbs(c, p, m, nullptr, lcbw, minw_sp, match_lcb, nl, &S.match_weight, elim_compact, &t1b);
+        rc = host_chain_lcbs(c, p, m, nullptr, lcbw, minw_sp, match_lcb, nl, &S.match_weight, false, &t1b);      // (not compact: dead records stay in m, with lcb -1 below)
         if (rc) return rc;
     }
     if (do_extend && !chains_ready) {
@@ -464,7 +452,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     }
     const double t2 = now_ms();
     c->stage.chain_ms = t2 - t1;
-    if (g_trace_pipeline) fprintf(stderr, "[trace] chain: eliminate_overlaps %.3f ms, lcb %.3f ms\n", t1b - t1, t2 - t1b);
+    if (switches().trace) fprintf(stderr, "[trace] chain: eliminate_overlaps %.3f ms, lcb %.3f ms\n", t1b - t1, t2 - t1b);
 
     // ---- recursive anchoring ----
     if (p->recursive) {
@@ -481,7 +469,7 @@ static int align_begin(mauve_ctx *c, const mauve_params *p, bool device_front = 
     // (mauve_align, device_front: the interval table is made on the device, dp_run_from_anchors)
     if (!device_front) host_gap_table(chains, N, nullptr, p->gapped, dp_len_limit(p), S.gaps, S.desc, S.n_dp, S.code_total);
     S.t_dp0 = now_ms();
-    if (g_trace_pipeline) fprintf(stderr, "[trace] interval table: %.3f ms (%lld gaps, %lld dp)\n", S.t_dp0 - t3, (long long)S.gaps.size(), (long long)S.n_dp);
+    if (switches().trace) fprintf(stderr, "[trace] interval table: %.3f ms (%lld gaps, %lld dp)\n", S.t_dp0 - t3, (long long)S.gaps.size(), (long long)S.n_dp);
     S.open = true;
     return MAUVE_OK;
 }
@@ -639,7 +627,7 @@ static int align_finish(mauve_ctx *c, const uint32_t *dcols, const int64_t *dcol
     R.sz.n_gap_dp = n_dp; R.sz.n_dp_cells = cells;
     *sizes = R.sz;
     const double t5 = now_ms();
-    if (g_trace_pipeline) fprintf(stderr, "[trace] assemble: layout %.3f ms, restore %.3f, anchors+gaps %.3f, unaligned+sizes %.3f\n", ta1 - t4, ta2 - ta1, ta3 - ta2, t5 - ta3);
+    if (switches().trace) fprintf(stderr, "[trace] assemble: layout %.3f ms, restore %.3f, anchors+gaps %.3f, unaligned+sizes %.3f\n", ta1 - t4, ta2 - ta1, ta3 - ta2, t5 - ta3);
     c->stage.assemble_ms = t5 - t4;
     c->stage.total_ms = t5 - S.t0;
     S.open = false;
@@ -679,16 +667,14 @@ static int align_begin_lcbs(mauve_ctx *c, const mauve_params *p, std::vector<Mat
     return MAUVE_OK;
 }
 
-// the interval table is on the host (align_begin without device_front): DP of all its intervals into ctx->pin_dcols, host assembly;
-// shadow: the anchor table is filled while the DP kernels run
-static int align_dp_finish(mauve_ctx *c, mauve_align_sizes *sizes, bool shadow)
+// the interval table is on the host (align_begin without device_front): DP of all its intervals into ctx->pin_dcols, host assembly
+static int align_dp_finish(mauve_ctx *c, mauve_align_sizes *sizes)
 {
     AlignState &S = c->ast;
     HIPCHK(c, c->pin_dcols.ensure(((size_t)S.code_total + 1) * sizeof(uint32_t)));
     uint32_t *dcols = c->pin_dcols.as<uint32_t>();
     S.dcol_off.assign((size_t)S.n_dp + 1, 0); S.dscore.assign((size_t)S.n_dp + 1, 0);
     int64_t cells = 0;
-    if (shadow && S.n_dp) c->shadow = [c]() { fill_anchor_table(c); };
     const int rc = align_dp(c, nullptr, S.n_dp, dcols, S.dcol_off.data(), S.dscore.data(), &cells);
     c->shadow = nullptr;
     if (rc) return rc;
@@ -715,7 +701,6 @@ static int kept_mums_to_host(mauve_ctx *c)
 static int align_tail_host_chains(mauve_ctx *c, mauve_align_sizes *sizes)
 {
     AlignState &S = c->ast;
-    static const bool no_shadow = getenv("MAUVE_NO_SHADOW") != nullptr;
     int64_t cells = 0;
     int rc;
     // the anchors in chain order as flat int32 records (page-locked), then everything up to the DP columns on the device
@@ -733,10 +718,9 @@ static int align_tail_host_chains(mauve_ctx *c, mauve_align_sizes *sizes)
             }
         }
     }
-    if (!no_shadow && na) c->shadow = [c]() { fill_anchor_table(c); };               // runs while the DP kernels do
+    if (na) c->shadow = [c]() { fill_anchor_table(c); };               // runs while the DP kernels do
     c->dp_band_from = dp_band_from_of(&S.p);
-    static const bool host_tail = getenv("MAUVE_HOST_TAIL") != nullptr;
-    if (!host_tail && na >= 2) {
+    if (!switches().host_tail && na >= 2) {
         // The chains were on the host (recursion, LCB extension, a small or tied list), but nothing after them has to be:
         // the anchors go up, the DP results stay in HBM and the interval table is assembled there (assemble_dev.hip).
         rc = dp_run_from_anchors(c, N, na, h_len, h_st, h_lcb, S.p.gapped, dp_len_limit(&S.p), &S.p.scoring, nullptr, &S.n_dp, &S.code_total,
@@ -811,9 +795,7 @@ static int align_whole(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *s
     { const int rs = refuse_scoring_params(c, p, "align"); if (rs) return rs; }
     if (c->nseq < 2) { c->err = "align: at least two genomes required"; return MAUVE_ERR_STATE; }
     HIPCHK(c, hipSetDevice(c->device));
-    static const bool host_front = getenv("MAUVE_HOST_DP_FRONT") != nullptr;      // A/B switch
-    static const bool no_shadow = getenv("MAUVE_NO_SHADOW") != nullptr;
-    int rc = align_begin(c, p, !host_front, nullptr, !host_front);
+    int rc = align_begin(c, p, true, nullptr, true);
     if (rc) return rc;
     AlignState &S = c->ast;
     int64_t cells = 0;
@@ -831,7 +813,6 @@ static int align_whole(mauve_ctx *c, const mauve_params *p, mauve_align_sizes *s
         if (rc || rc_pf) return rc ? rc : rc_pf;
         return assemble_device(c, S.n_anchor, cells, sizes);
     }
-    if (host_front) return align_dp_finish(c, sizes, !no_shadow);
     return align_tail_host_chains(c, sizes);
 }
 
@@ -943,7 +924,7 @@ int mauve_align_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const in
     if (rc) return rc;
     rc = align_begin(c, p, false, &mv);
     if (rc) return rc;
-    return align_dp_finish(c, sizes, false);
+    return align_dp_finish(c, sizes);
 }
 
 int mauve_align_begin_matches(mauve_ctx *c, const mauve_params *p, int64_t n, const int64_t *length, const int64_t *start, int64_t *n_dp,

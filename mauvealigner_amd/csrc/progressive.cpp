@@ -31,8 +31,6 @@
 
 namespace {
 
-const bool g_trace = getenv("MAUVE_TRACE") != nullptr;      // read once, not in the timed path
-
 // The bases of one genome that no block has taken yet: an ordered map start -> end of free stretches (1-based,
 // inclusive, disjoint).  Blocks are carved out one by one; a position is identified by the start of the stretch it lies
 // in (0 = placed already).
@@ -198,20 +196,17 @@ int node_chain(Prog &P, NodeWork &W)
     mauve_ctx *c = P.c; const mauve_params *p = P.p;
     const int n = W.n;
     MatchVec &m = W.m;
-    static const bool host_chain_env = getenv("MAUVE_HOST_CHAIN") != nullptr;
     const bool sp = p->lcb_scoring == MAUVE_LCB_SCORE_SP;    // the matches' scores are summed on the device too (ch_sp_scores, on the cropped records)
     int rc = MAUVE_ERR_LIMIT;
-    if (!host_chain_env && !p->seed_family && n == P.N && W.nm > 0 && c->dev_rec_n == W.nm && (!sp || n <= 16)) {
+    if (!switches().host_chain && !p->seed_family && n == P.N && W.nm > 0 && c->dev_rec_n == W.nm && (!sp || n <= 16)) {
         rc = chain_device(c, n, sp ? W.minw_sp : W.lcbw, p->collinear != 0, m, W.match_lcb, W.nl, sp ? &p->scoring : nullptr);
         if (rc && rc != MAUVE_ERR_LIMIT) return rc;
     }
     if (rc) { rc = host_chain_lcbs(c, p, m, W.gm.data(), W.lcbw, W.minw_sp, W.match_lcb, W.nl, nullptr, true); if (rc) return rc; }
-    if (g_trace) {
+    if (switches().trace) {
         int64_t surv = 0; for (size_t i = 0; i < m.size(); i++) if (W.match_lcb[i] >= 0) surv++;
         fprintf(stderr, "[trace] node %d (n=%d, w=%d): %lld n-way matches, %zu after overlap elimination, %lld lcbs, %lld anchors\n", W.node, n, W.w,
                 (long long)W.nm, m.size(), (long long)W.nl, (long long)surv);
-        if (getenv("MAUVE_TRACE_MATCHES"))
-            for (size_t i = 0; i < m.size(); i++) { fprintf(stderr, "[trace]   m %zu len %lld lcb %lld:", i, (long long)m.len(i), (long long)W.match_lcb[i]); for (int j = 0; j < n; j++) fprintf(stderr, " %lld", (long long)m.st(i)[j]); fprintf(stderr, "\n"); }
     }
     return MAUVE_OK;
 }
@@ -405,7 +400,7 @@ int node_refine(Prog &P, NodeWork &W)
     const double tr2 = now_ms();
     rc = refine_pick(P, W, F);
     if (rc) return rc;
-    if (g_trace) fprintf(stderr, "[trace] node %d: refinement: %lld candidate alignments of %lld intervals, %lld replaced; candidates %.3f ms, batch %.3f, pick + fetch + remap %.3f\n", W.node,
+    if (switches().trace) fprintf(stderr, "[trace] node %d: refinement: %lld candidate alignments of %lld intervals, %lld replaced; candidates %.3f ms, batch %.3f, pick + fetch + remap %.3f\n", W.node,
                          (long long)nc, (long long)n_dp, (long long)F.replaced, tr1 - tr0, tr2 - tr1, now_ms() - tr2);
     return MAUVE_OK;
 }
@@ -488,7 +483,7 @@ int prog_node(Prog &P, int node)
     if (rc) return rc;
     P.n_gap_dp += W.n_dp; P.n_cells += W.cells;
     { const double tn4 = now_ms(); P.t_seed += W.tn1 - W.tn0; P.t_chain += W.tn2 - W.tn1; P.t_rec += W.tn3 - W.tn2; P.t_dp += tn4 - W.tn3; }
-    if (g_trace) {
+    if (switches().trace) {
         int64_t big = 0; for (const DpSeqDesc &d : W.desc) big = std::max(big, d.len);
         fprintf(stderr, "[trace] node %d (n=%d, pool %lld): seed %.1f ms (%lld mums), chain %.1f, recursion %.1f, dp %.1f ms (%lld intervals, %lld cells, longest side %lld)\n",
                 node, W.n, (long long)W.rest_len, W.tn1 - W.tn0, (long long)W.nm, W.tn2 - W.tn1, W.tn3 - W.tn2, now_ms() - W.tn3, (long long)W.n_dp, (long long)W.cells, (long long)big);
@@ -496,7 +491,7 @@ int prog_node(Prog &P, int node)
     const double tb0 = now_ms();
     node_blocks(P, W);
     P.t_blocks += now_ms() - tb0;
-    if (g_trace) fprintf(stderr, "[trace] node %d: blocks %.1f ms\n", node, now_ms() - tb0);
+    if (switches().trace) fprintf(stderr, "[trace] node %d: blocks %.1f ms\n", node, now_ms() - tb0);
     rc = prog_node(P, P.left[node]);
     if (rc) return rc;
     return prog_node(P, P.right[node]);
@@ -659,7 +654,7 @@ static int progressive_core(mauve_ctx *c, const mauve_params *p, mauve_align_siz
             for (int64_t &v : P.bpd) v = mx ? v * 1000000 / mx : 0;
         }
     }
-    const bool trace = g_trace;
+    const bool trace = switches().trace;
     const double tg1 = now_ms();
     if (trace) fprintf(stderr, "[trace] progressive: guide tree %.1f ms\n", tg1 - t0);
     if (tree_left) std::copy(P.left.begin(), P.left.end(), tree_left);

@@ -133,9 +133,6 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter(const KeyT *__restrict_
                                                            nullptr, 0, 0, reinterpret_cast<const uint64_t *>(vals_in));
 }
 
-// MAUVE_SMALL_SORT=0: sorts of up to SS_CAP pairs take the tiled path too (read once, when it is first asked for)
-static bool small_sort_on() { static const bool v = [] { const char *e = getenv("MAUVE_SMALL_SORT"); return !(e && e[0] == '0'); }(); return v; }
-
 template <typename KeyT, typename ValT>
 int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **vals_io, KeyT *keys_alt, ValT *vals_alt, bool have_hist0,
                int timer_id, int shift_lo, bool iota)
@@ -143,7 +140,7 @@ int sort_pairs(mauve_ctx *ctx, uint32_t n, int key_bits, KeyT **keys_io, ValT **
     const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scan = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCAN,
               k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
     if (iota && !(have_hist0 && shift_lo < key_bits)) { ctx->err = "sort_pairs: values from the strand bitmap need a first tiled pass"; return MAUVE_ERR_ARG; }
-    if (small_sort_on() && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
+    if (switches().small_sort && !have_hist0 && n >= 1 && n <= SS_CAP) {      // small sort: device-sized tiles, one launch per digit pass
         HIPCHK(ctx, ctx->hist.ensure(ss_ws_words(n) * sizeof(uint32_t)));
         small_sort<KeyT>(ctx->stream, n, key_bits, shift_lo, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),
                          [&](bool scatter, auto &&launch) { KernelTimer t(ctx, scatter ? k_scat : k_hist, n); launch(); });
@@ -197,7 +194,7 @@ int sort_pairs_u32_batch(mauve_ctx *ctx, uint32_t S, uint32_t n, size_t seg_stri
 {
     if (S == 0 || n == 0) return MAUVE_OK;
     if (S > 65535u || seg_stride < n) { ctx->err = "sort_pairs_u32_batch: bad segment layout"; return MAUVE_ERR_ARG; }
-    if (small_sort_on() && n <= SS_CAP) {
+    if (switches().small_sort && n <= SS_CAP) {
         const int k_hist = timer_id >= 0 ? timer_id : MAUVE_K_SORT_HIST, k_scat = timer_id >= 0 ? timer_id : MAUVE_K_SORT_SCATTER;
         HIPCHK(ctx, ctx->hist.ensure(ss_ws_words_batch(S, n) * sizeof(uint32_t)));
         small_sort_batch<uint32_t>(ctx->stream, S, n, seg_stride, key_bits, 0, keys_io, vals_io, keys_alt, vals_alt, ctx->hist.as<uint32_t>(),

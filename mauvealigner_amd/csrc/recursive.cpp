@@ -19,8 +19,6 @@
 
 namespace {
 
-const bool g_trace = getenv("MAUVE_TRACE") != nullptr;      // read once, not in the timed path
-
 // Virtual genomes of one recursion batch, built on the device from the resident packed genomes: thread (g, j)
 // writes packed word j of virtual genome g -- 32 bases, each looked up through the segment table (which gap it
 // belongs to) and the gap's source range; reverse gaps are read backwards and complemented.  Pad words are zero.
@@ -312,16 +310,17 @@ void rec_chain_host(const mauve_ctx *c, const RecBatch &B, int64_t nm, RecSurviv
     MatchVec loc(N);                     // reused from gap to gap (thousands of gaps per batch)
     ChainOrders orders;
     std::vector<int64_t> ml;
+    const bool trace = switches().trace;
     for (int64_t i = 0; i < nm;) {
         const uint32_t k = (uint32_t)(std::upper_bound(seg0, seg0 + K + 1, (uint32_t)(c->match_start[(size_t)i * N] - 1)) - seg0) - 1;
         i = rec_gap_matches(c, B, i, nm, k, loc);
         if (loc.empty()) continue;
-        const double te0 = g_trace ? now_ms() : 0;
+        const double te0 = trace ? now_ms() : 0;
         host_eliminate_overlaps(loc, &orders);
-        const double te1 = g_trace ? now_ms() : 0;
+        const double te1 = trace ? now_ms() : 0;
         int64_t nl = 0;
         host_lcb_chain(loc, 0, true, ml, nl, &orders);
-        if (g_trace) { T.t_elim += te1 - te0; T.t_lcb += now_ms() - te1; }
+        if (trace) { T.t_elim += te1 - te0; T.t_lcb += now_ms() - te1; }
         for (size_t q = 0; q < loc.size(); q++) {
             if (ml[q] < 0) continue;
             int32_t st[MAUVE_MAX_SEQ];                           // back into the virtual genomes
@@ -339,14 +338,13 @@ void rec_chain_host(const mauve_ctx *c, const RecBatch &B, int64_t nm, RecSurviv
 // route like any other.)
 int rec_batch_chain(mauve_ctx *c, const RecBatch &B, int level, RecSurvivors &S, RecTrace &T)
 {
-    static const bool host_gaps = getenv("MAUVE_HOST_GAP_CHAIN") != nullptr;      // A/B switch
-    static const bool old_gaps = getenv("MAUVE_GAP_CHAIN_ALL_BACK") != nullptr;   // A/B switch: the device chain that copies every record and graph back
+    const bool host_gaps = switches().host_gap_chain, old_gaps = switches().gap_chain_all_back;      // A/B switches
     int64_t nm = 0;
     c->lazy_matches_ok = !host_gaps && !old_gaps;     // a large batch is chained where its list is: no host copy of it
     int rc = seedpass_run(c, B.vs, mauve_get_seed(B.w, 0), MAUVE_MODE_MEM, full_mask(B.N), 1, c->rec_seg.as<uint32_t>(), B.K, &nm);
     c->lazy_matches_ok = false;
     if (rc) return rc;
-    if (g_trace) fprintf(stderr, "[trace] recursion level %d weight %d: %u gaps, %lld bases, %lld matches, %.3f ms\n", level, B.w, B.K,
+    if (switches().trace) fprintf(stderr, "[trace] recursion level %d weight %d: %u gaps, %lld bases, %lld matches, %.3f ms\n", level, B.w, B.K,
                          (long long)B.vs.lens[0], (long long)nm, now_ms() - T.t_batch);
     T.t_chain = now_ms();
     if (!host_gaps && nm > 0 && c->dev_rec_n == nm) {
@@ -424,7 +422,7 @@ int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector
     WorkList work(N);
     rec_work_list(c, p, w0, chains, work);
     std::vector<MatchVec> found(chains.size(), MatchVec(N));
-    if (g_trace) fprintf(stderr, "[trace] recursion: work list of %zu gaps built in %.3f ms\n", work.size(), now_ms() - t_stage0);
+    if (switches().trace) fprintf(stderr, "[trace] recursion: work list of %zu gaps built in %.3f ms\n", work.size(), now_ms() - t_stage0);
 
     for (int level = 1; work.size(); level++) {
         std::map<int, std::vector<size_t>> classes;     // seed weight -> gaps of this level
@@ -449,12 +447,12 @@ int recursive_anchoring(mauve_ctx *c, const mauve_params *p, int w0, std::vector
             if (!rc) rec_emit(B, S, L, shard_msg);
             rc = rec_exchange(c, B, rc, shard_msg, L);
             if (rc) return rc;
-            if (g_trace) fprintf(stderr, "[trace]   per-gap chaining %.3f ms (%s; eliminate %.3f, lcb %.3f)\n", now_ms() - T.t_chain, T.route, T.t_elim, T.t_lcb);
+            if (switches().trace) fprintf(stderr, "[trace]   per-gap chaining %.3f ms (%s; eliminate %.3f, lcb %.3f)\n", now_ms() - T.t_chain, T.route, T.t_elim, T.t_lcb);
         }
         work.d.swap(next.d);
     }
     const double tm0 = now_ms();
     rec_merge_found(chains, found);
-    if (g_trace) fprintf(stderr, "[trace] recursion: merge into chains %.3f ms, whole stage %.3f ms\n", now_ms() - tm0, now_ms() - t_stage0);
+    if (switches().trace) fprintf(stderr, "[trace] recursion: merge into chains %.3f ms, whole stage %.3f ms\n", now_ms() - tm0, now_ms() - t_stage0);
     return MAUVE_OK;
 }

@@ -270,7 +270,7 @@ int rm_pass(const RmPass &P)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint32_t nrec = std::min(ht[2], ncand);
     seed_trace(c, "repeat map: extension", t0);
-    if (seed_trace_on()) {
+    if (switches().trace) {
         std::vector<uint32_t> hr(ncand);
         HIPCHK(c, hipMemcpy(hr.data(), rounds, (size_t)ncand * 4, hipMemcpyDeviceToHost));
         uint64_t sum = 0; uint32_t mx = 0;

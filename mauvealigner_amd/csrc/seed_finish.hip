@@ -413,6 +413,6 @@ int seed_finish(mauve_ctx *ctx, const GenomeSet &gs, const SeedRequest &rq, uint
     }
     if (ncand == 0) return MAUVE_OK;
     // ---- canonical order (first component, |start|, mask, starts, length) ----
-    if (ncand >= canon_device_min()) return canon_device(ctx, gs, rq, ncand, trace_t0);
+    if (ncand >= (uint32_t)switches().canon_device_min) return canon_device(ctx, gs, rq, ncand, trace_t0);
     return canon_host(ctx, gs.nseq, rq, ncand, on_host, trace_t0);
 }

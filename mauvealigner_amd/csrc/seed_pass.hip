@@ -1087,23 +1087,12 @@ __global__ void __launch_bounds__(256) mum_extend(const uint64_t *__restrict__ p
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// The switches that tests and tools set ("Seed pass host side", names who sets which).  Each is read once, when it
-// is first asked for -- not when the library is loaded: a test sets MAUVE_CANON_DEVICE_MIN after it has opened its context.
-bool seed_trace_on() { static const bool v = getenv("MAUVE_TRACE") != nullptr; return v; }
-// a pass of a few thousand windows takes the hash join like any other
-static bool no_tiny() { static const bool v = getenv("MAUVE_NO_TINY") != nullptr; return v; }
-// MAUVE_RUNS_ITEMS=4|8|16: that mum_runs / mum_runs_group instantiation for every launch (0: the rule, runs_items)
-static int runs_items_env() { static const int v = [] { const char *e = getenv("MAUVE_RUNS_ITEMS"); const int x = e ? atoi(e) : 0; return x == 4 || x == 8 || x == 16 ? x : 0; }(); return v; }
-// shrinks the compacted lists so that the capacity checks can be seen to fire (0: off)
-static uint32_t list_cap_env() { static const uint32_t v = getenv("MAUVE_LIST_CAP") ? (uint32_t)strtoul(getenv("MAUVE_LIST_CAP"), nullptr, 10) : 0u; return v; }
-// candidates from which the canonical order is made on the device (below: the host sorts; tests force the device path)
-uint32_t canon_device_min() { static const uint32_t v = getenv("MAUVE_CANON_DEVICE_MIN") ? (uint32_t)atol(getenv("MAUVE_CANON_DEVICE_MIN")) : 16384u; return v; }
+// The switches that tests and tools set are fields of switches() (switches.hpp; DESIGN.md section 4, "Seed pass host side", names who sets which).
 // Index width of a seed pass: wide values when the pass has 2^31 windows or more; MAUVE_WIDE_INDEX=1 forces them for every
 // pass (test switch: small inputs take the wide kernels against the oracle).  Every other pass runs the narrow instantiations.
 bool seedpass_wide(int64_t total_windows)
 {
-    static const bool force = [] { const char *e = getenv("MAUVE_WIDE_INDEX"); return e && e[0] == '1' && e[1] == 0; }();
-    return force || total_windows >= (1LL << 31);
+    return switches().wide_index || total_windows >= (1LL << 31);
 }
 
 bool make_seed_shape(uint64_t pattern, SeedShape *sh)
@@ -1200,7 +1189,7 @@ static int seed_plan(mauve_ctx *ctx, const SeedShape &sh, const GenomeTab &tab, 
     if (seg) while (pl->segbits < 32 && (1ull << pl->segbits) <= (uint64_t)rq.nseg) pl->segbits++;
     if (seg && 2 * sh.weight + pl->segbits > 64) { ctx->err = "recursive anchoring: segment id and mer do not fit 64 bits"; return MAUVE_ERR_LIMIT; }
     pl->full_bits = seg ? 2 * sh.weight + pl->segbits : ((masked && rq.only_seq >= 0) ? key_type_bits : 2 * sh.weight);
-    pl->tiny = pl->hash_path && !no_tiny() && n <= (uint32_t)TJ_MAX && tab.nseq <= 16 && 2 * sh.weight + pl->segbits <= 32;
+    pl->tiny = pl->hash_path && !switches().no_tiny && n <= (uint32_t)TJ_MAX && tab.nseq <= 16 && 2 * sh.weight + pl->segbits <= 32;
     pl->compact = !rq.hits && !pl->tiny && rq.only_seq < 0 && masked && !seg;
     pl->has_invalid = masked && !pl->compact;
     // Only where seed_extract_all feeds a tiled sort pass (extract's third branch, and bits left to sort: a pass without a sort pass joins
@@ -1439,7 +1428,7 @@ static WinRange anchor_range(const GenomeTab &tab, uint32_t P, const FinderPass 
 constexpr uint64_t RUNS_CU_16 = 131072, RUNS_CU_8 = 6144;
 static int runs_items(const mauve_ctx *ctx, uint64_t windows)
 {
-    if (const int forced = runs_items_env()) return forced;
+    if (const int forced = switches().runs_items) return forced;
     const uint64_t per_cu = windows / (uint64_t)std::max(ctx->cus, 1);
     return per_cu >= RUNS_CU_16 ? 16 : (per_cu >= RUNS_CU_8 ? 8 : 4);
 }
@@ -1479,7 +1468,7 @@ static int launch_extend(SeedState &st, uint32_t blocks, uint32_t ncand, int32_t
                        ctx->cand.as<uint32_t>(), ncand, st.rq.extend, o_len, o_start, st.rq.seg, st.rq.nseg, st.vmask, st.cmask, ncand_dev, counters_out);
     HIPCHK(ctx, hipGetLastError());
 #ifdef MAUVE_EXT_STATS
-    if (seed_trace_on()) {
+    if (switches().trace) {
         unsigned long long h[8]; hipStreamSynchronize(ctx->stream);
         hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ext_stats), sizeof h); unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_ext_stats), z, sizeof z);
         fprintf(stderr, "[trace]   extend stats: %llu rounds, %llu waves, wave time mean %.1f us max %.1f us (setup %.1f, left walk %.1f, right walk %.1f), most rounds of a wave %llu\n", h[0], h[4],
@@ -1512,7 +1501,7 @@ template <typename KeyT, typename ValT>
 static int pairwise_passes(SeedPass<KeyT, ValT> &ps)
 {
     constexpr bool WIDEV = sizeof(ValT) == 8;
-    mauve_ctx *ctx = ps.ctx; const GenomeTab &tab = ps.tab; const uint32_t P = ps.P, ns = ps.ns, list_cap = list_cap_env();
+    mauve_ctx *ctx = ps.ctx; const GenomeTab &tab = ps.tab; const uint32_t P = ps.P, ns = ps.ns, list_cap = switches().list_cap;
     const std::vector<FinderPass> &passes = ps.passes;
     const size_t cap = (size_t)ns / 2 + 1;
     const uint32_t run_cap = list_cap ? std::min<uint32_t>((uint32_t)cap, list_cap) : (uint32_t)cap;
@@ -1568,7 +1557,7 @@ static int pairwise_passes(SeedPass<KeyT, ValT> &ps)
         const uint32_t nc = cw[1];
         if (cand_overflow(ps, nc)) return MAUVE_ERR_LIMIT;
         seed_trace(ctx, "runs", ps.trace_t0);
-        if (seed_trace_on()) fprintf(stderr, "[trace]   %u candidates of %u windows (%d pairs at once)\n", nc, slices, grp.n);
+        if (switches().trace) fprintf(stderr, "[trace]   %u candidates of %u windows (%d pairs at once)\n", nc, slices, grp.n);
         if (nc == 0) continue;
         if (int rc = extend_candidates<false, WIDEV>(ps, nc, 256 * 8)) return rc;
     }
@@ -1601,7 +1590,7 @@ static int tiny_pass(SeedState &st, const FinderPass &fp)
     const size_t lbytes = ((size_t)cand_cap * 4 + 63) & ~(size_t)63, sbytes = (size_t)cand_cap * 4 * N;
     HIPCHK(ctx, ctx->pin_seed.ensure(64 + lbytes + sbytes));
     char *pin = ctx->pin_seed.as<char>();
-    const bool host_out = cand_cap < canon_device_min();
+    const bool host_out = cand_cap < (uint32_t)switches().canon_device_min;
     if (!host_out) { HIPCHK(ctx, ctx->mlen.ensure((size_t)cand_cap * 4 + 4)); HIPCHK(ctx, ctx->mstart.ensure((size_t)cand_cap * 4 * N + 4)); }
     int32_t *o_len = host_out ? reinterpret_cast<int32_t *>(pin + 64) : ctx->mlen.as<int32_t>();
     int32_t *o_st = host_out ? reinterpret_cast<int32_t *>(pin + 64 + lbytes) : ctx->mstart.as<int32_t>();
@@ -1616,7 +1605,7 @@ static int tiny_pass(SeedState &st, const FinderPass &fp)
     if (reinterpret_cast<const uint32_t *>(pin)[9]) { ctx->err = "tiny_join: anchor out of range (internal error)"; return MAUVE_ERR_HIP; }
     if (cand_overflow(st, nc)) return MAUVE_ERR_LIMIT;
     seed_trace(ctx, "runs + extend (one round trip)", st.trace_t0);
-    if (seed_trace_on()) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
+    if (switches().trace) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
     ctx->sdh.hl.assign(reinterpret_cast<const int32_t *>(pin + 64), reinterpret_cast<const int32_t *>(pin + 64) + nc);
     ctx->sdh.hs.assign(reinterpret_cast<const int32_t *>(pin + 64 + lbytes), reinterpret_cast<const int32_t *>(pin + 64 + lbytes) + (size_t)nc * N);
     st.cand_total = nc; st.records_on_host = true;
@@ -1669,7 +1658,7 @@ static int join_overflow_slices(SeedPass<KeyT, ValT> &ps, const FinderPass &fp, 
     const uint32_t *cw;
     if (int rc = seed_counters(ctx, 16, &cw)) return rc;
     *nc = cw[1];
-    if (seed_trace_on()) fprintf(stderr, "[trace]   join_hash handed back %u range(s)\n", novf);
+    if (switches().trace) fprintf(stderr, "[trace]   join_hash handed back %u range(s)\n", novf);
     return MAUVE_OK;
 }
 
@@ -1717,7 +1706,7 @@ static int finder_pass(SeedPass<KeyT, ValT> &ps, const FinderPass &fp)
     if (novf) if (int rc = join_overflow_slices<KeyT, SEG, ValT>(ps, fp, novf, &nc)) return rc;
     if (cand_overflow(ps, nc)) return MAUVE_ERR_LIMIT;
     seed_trace(ctx, "runs", ps.trace_t0);
-    if (seed_trace_on()) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
+    if (switches().trace) fprintf(stderr, "[trace]   %u candidates of %u windows\n", nc, P);
     if (nc == 0) return MAUVE_OK;
     // six waves per SIMD fit (77 registers); two rounds of workgroups even out the candidates' different lengths (measured: 5 .. 8 per compute unit
     // within 5 % of each other, 12 .. 14 another 10 % faster)
@@ -1733,7 +1722,7 @@ static int seedpass_stages(const SeedState &st0)
     constexpr bool WIDEV = sizeof(ValT) == 8;
     SeedPass<KeyT, ValT> ps(st0);
     mauve_ctx *ctx = ps.ctx; const SeedRequest &rq = ps.rq; const uint32_t P = ps.P; const int N = ps.tab.nseq;
-    if (seed_trace_on()) fprintf(stderr, "[trace] seed pass: %u windows, %d-bit keys, %s window index (%d-bit values)\n", P, (int)sizeof(KeyT) * 8,
+    if (switches().trace) fprintf(stderr, "[trace] seed pass: %u windows, %d-bit keys, %s window index (%d-bit values)\n", P, (int)sizeof(KeyT) * 8,
                                   WIDEV ? "wide" : "narrow", (int)sizeof(ValT) * 8);
     if (int rc = seed_plan(ctx, ps.sh, ps.tab, rq, P, ps.vmask || ps.cmask, SEG, (int)sizeof(KeyT) * 8, &ps.pl, &ps.passes)) return rc;
     if (int rc = extract<KeyT, SEG, ValT>(ps)) return rc;
@@ -1751,7 +1740,7 @@ static int seedpass_stages(const SeedState &st0)
     ps.tmask = ctx->posmask.as<uint32_t>(); ps.tpos = ctx->hit_pos.as<uint32_t>();
     ps.cand_cap = P / 2 + 1;                                     // a hit needs >= 2 entries
     HIPCHK(ctx, ctx->cand.ensure((size_t)ps.cand_cap * 4));
-    if (list_cap_env()) ps.cand_cap = std::min(ps.cand_cap, list_cap_env());
+    if (switches().list_cap) ps.cand_cap = std::min(ps.cand_cap, switches().list_cap);
     ctx->sdh.hl.clear(); ctx->sdh.hs.clear();                    // (host scratch kept across calls)
     if (ps.pl.tiny) {
         if (int rc = tiny_pass<SEG, WIDEV>(ps, ps.passes[0])) return rc;
@@ -1922,7 +1911,7 @@ static_assert(RP_TILE == RS_TILE, "the multiplicity pass sorts with the histogra
 template <typename KeyT, typename ValT>
 static int rp_windows(mauve_ctx *c, const GenomeSet &gs, const SeedShape &sh, const GenomeTab &tab, uint32_t n)
 {
-    if (seed_trace_on()) fprintf(stderr, "[trace] multiplicity pass: %u windows, %s window index (%d-bit values)\n", n, sizeof(ValT) == 8 ? "wide" : "narrow", (int)sizeof(ValT) * 8);
+    if (switches().trace) fprintf(stderr, "[trace] multiplicity pass: %u windows, %s window index (%d-bit values)\n", n, sizeof(ValT) == 8 ? "wide" : "narrow", (int)sizeof(ValT) * 8);
     if (int rc = ensure_sort_buffers<KeyT, ValT>(c, n)) return rc;
     KeyT *keys = c->keysA.as<KeyT>(); ValT *vals = c->valsA.as<ValT>();
     if (int rc = extract_all<KeyT, false, ValT>(c, gs, sh, tab, n, nullptr, 0u, 0, keys, vals)) return rc;

@@ -16,11 +16,11 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
-#include <cstdlib>
 #include <mutex>
 #include <thread>
 #include <type_traits>
 #include <vector>
+#include "switches.hpp"
 
 class SpinPool {
 public:
@@ -43,8 +43,8 @@ public:
         // Opt-in.  On the bench host (16-CPU cgroup share of a 256-thread box) helpers cut the assembly from 0.8 to
         // 0.45 ms but the single-threaded stages of the same call ran 20 % slower whenever the process had more
         // runnable threads, a net loss; so the default is the calling thread alone.
-        if (const char *e = getenv("MAUVE_HOST_THREADS")) { const int v = atoi(e); return v < 1 ? 1 : (v > 16 ? 16 : v); }
-        return 1;
+        const int v = switches().host_threads;         // MAUVE_HOST_THREADS, 1..16; 0: not set
+        return v ? v : 1;
     }
 
     void arm()
