@@ -3,10 +3,7 @@
 // for wide values, a histogram made on the way in and a partial sort.
 #pragma once
 #include "common.hpp"
-#include "small_sort.hpp"
-
-constexpr int RS_ITEMS = 16;                     // (RS_THREADS, the tile ranking rs_scatter_tile: small_sort.hpp)
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;   // 4096 keys per workgroup
+#include "small_sort.hpp"      // RS_ITEMS, RS_TILE
 
 // Stable LSD passes over bits [shift_lo, key_bits) of the n pairs in *keys_io / *vals_io, which point at the result on return (the
 // alternates after an odd number of passes).  have_hist0: the tile histograms of the first pass are already in ctx->hist.

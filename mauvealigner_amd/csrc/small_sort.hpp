@@ -29,6 +29,8 @@
 
 constexpr int RS_THREADS = 256;
 constexpr int RS_WAVES = RS_THREADS / 64;
+constexpr int RS_ITEMS = 16;                     // keys per thread of the main sort (tiled_sort.hpp) ...
+constexpr int RS_TILE = RS_THREADS * RS_ITEMS;   // ... 4096 keys per workgroup: seed_extract_all lays the first pass's histograms out by it
 
 // block-wide exclusive scan of one value per thread (256 threads); returns the exclusive prefix, *total
 // receives the block sum.  One global atomic per block instead of one per wave keeps a single output
